@@ -2,6 +2,7 @@
 """bench.py -- headline benchmark of the MI355X ray tracer.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scene tenthousand] [--width 1920 --height 1080 --spp 16]
+                    [--full] [--dump-outputs DIR]
 
 One step = one frame of the hot path (trace + resolve, scene and BVH resident in HBM, the reference's own scene file):
 BASELINE.json's headline workload, `tenthousand.txt` at 1920x1080, 16 samples per pixel.  With N > 1 (launched by
@@ -22,11 +23,15 @@ roofline     = the bytes of the records rank 0's trace-kernel launch requests --
                kernel is in `limiter`: the busiest unit of the committed rocprofv3 --pmc passes of THIS build
                (profiles/*pmc_trace_kernel*.json carry a hash of csrc/; a summary of another build is marked stale and not used
                for `traffic`).
-configs      = (N = 1) the other BASELINE configurations on this GPU, a few frames each: spiral 1080p16, redchair 4K64,
+configs      = (--full, N = 1) the other BASELINE configurations on this GPU, a few frames each: spiral 1080p16, redchair 4K64,
                the synthetic 1 M spheres + 1 M triangles scene at 4K x 256 spp (whole frame on one GPU) -- ms/frame,
                Mrays/s, node visits per ray, algorithmic roofline fraction.
-cpu_baseline = the CPU oracle (oracle/, a port of the reference's algorithm) on one host core over a bounded
-               sub-sample of the same workload (every `step`-th pixel in x and y), N = 1 only.
+cpu_baseline = (--full) the CPU oracle (oracle/, a port of the reference's algorithm) on one host core over a bounded
+               sub-sample of the same workload (every `step`-th pixel in x and y), N = 1 only; null without --full.
+
+A plain run sets up, warms up, times the K steps and prints the line; what takes runs of its own (configs, cpu_baseline)
+is measured only with --full.  --dump-outputs DIR writes what the last timed step computed -- the 8-bit RGBA frame a
+caller receives (rank 0) -- to DIR/frame_rgba8.npy as float32, rows x width x 4 (see dump_outputs()).
 """
 import argparse
 import glob
@@ -40,6 +45,26 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
 HEADLINE = ("tenthousand", 1920, 1080, 16)
+
+
+DUMP_LIMIT = 64 << 20      # bytes of --dump-outputs files at most
+
+
+def dump_outputs(dirname, frame):
+    """--dump-outputs: `frame` (uint8, rows x width x 4) as float32 in DIR/frame_rgba8.npy.  A frame whose float32 copy would
+    exceed DUMP_LIMIT is written as a fixed, seeded sample of its pixels instead: frame_rgba8_sample.npy (pixels x 4, float32)
+    and frame_rgba8_sample_pixels.npy (their row-major pixel indices, float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    a = frame.astype(np.float32)
+    if a.nbytes <= DUMP_LIMIT:
+        np.save(os.path.join(dirname, "frame_rgba8.npy"), a)
+        return
+    px = a.reshape(-1, 4)
+    n = (DUMP_LIMIT - 4096) // (px.itemsize * 4 + 8)
+    idx = np.sort(np.random.default_rng(20261016).choice(px.shape[0], n, replace=False))
+    np.save(os.path.join(dirname, "frame_rgba8_sample.npy"), px[idx])
+    np.save(os.path.join(dirname, "frame_rgba8_sample_pixels.npy"), idx.astype(np.float64))
 
 
 def algorithmic_bytes(st):
@@ -185,7 +210,7 @@ def main():
     ap.add_argument("--height", type=int, default=HEADLINE[2])
     ap.add_argument("--spp", type=int, default=HEADLINE[3])
     ap.add_argument("--stripe-rows", type=int, default=4)
-    ap.add_argument("--cpu-step", type=int, default=3, help="sub-sampling step of the CPU baseline (0 = skip)")
+    ap.add_argument("--cpu-step", type=int, default=3, help="sub-sampling step of the CPU baseline with --full (0 = skip)")
     ap.add_argument("--frames-in-flight", type=int, default=0,
                     help="consecutive frames overlapped on separate streams (1..4; default 2)")
     ap.add_argument("--serial", action="store_true", help="one frame in flight (no overlap of consecutive frames)")
@@ -195,6 +220,10 @@ def main():
     ap.add_argument("--png", default=None, help="write the last frame here (rank 0)")
     ap.add_argument("--headline-only", action="store_true", help="skip the extra configurations (profiling runs)")
     ap.add_argument("--config5-spp", type=int, default=256, help="samples per pixel of the synthetic 2 M-primitive configuration (BASELINE: 256)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the other BASELINE configurations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame the last timed step computed to DIR/*.npy (float32; rank 0)")
     args = ap.parse_args()
 
     # (the pool's host driver only supports dmabuf IPC: without this RCCL fails with `hipIpcGetMemHandle: invalid argument`)
@@ -332,7 +361,7 @@ def main():
     t0 = time.perf_counter()
     raw.stats()                                            # reset the library's running mean of trace-kernel times
     for _ in range(args.steps):
-        step(timed=True)
+        last = step(timed=True)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -351,6 +380,10 @@ def main():
     if world > 1:
         all_ms = [torch.zeros_like(mine_ms) for _ in range(world)]
         dist.all_gather(all_ms, mine_ms)
+
+    if args.dump_outputs and rank == 0:       # the last timed frame, before anything else renders into its buffers
+        rows = H if world > 1 else partition.num_pixels(prank) // W
+        dump_outputs(args.dump_outputs, last[: rows * W * 4].cpu().numpy().reshape(rows, W, 4))
 
     if args.png:                      # one more frame (a collective on several GPUs: every rank takes part)
         fr = step()
@@ -420,7 +453,7 @@ def main():
             out["rehearsal"] = (f"MIRT_BENCH_REHEARSE=1: {world} ranks share GPU 0 and gather over gloo -- exercises the N > 1 code path "
                                 "end to end; value / ms_per_step say nothing about scaling")
             out["config"]["parallelism"] = f"REHEARSAL: image stripes x{world} ranks on one GPU (gloo)"
-        if world == 1 and pworld == 1 and not args.headline_only and (args.scene, W, H, SPP) == HEADLINE:
+        if args.full and world == 1 and pworld == 1 and not args.headline_only and (args.scene, W, H, SPP) == HEADLINE:
             # the other BASELINE configurations on this GPU (a few frames each, serial)
             extra = []
             raw.close()
@@ -449,7 +482,7 @@ def main():
             extra.append(c5b)
             r5.close()
             out["configs"] = extra
-        if world == 1 and args.cpu_step > 0:
+        if args.full and world == 1 and args.cpu_step > 0:
             out["cpu_baseline"] = cpu_baseline(scene_file, W, H, SPP, args.cpu_step)
         else:
             out["cpu_baseline"] = None

@@ -37,11 +37,13 @@ def _kernel_instructions(src, kernel):
     import subprocess
     import tempfile
     from cuda_ray_tracer_amd import build as B
-    out = os.path.join(tempfile.gettempdir(), "mirt_codegen_" + src + ".s")
-    cmd = [B._hipcc()] + [c for c in B.COMMON if c != "-fPIC"] + ["-x", "hip", "-S", "--cuda-device-only", os.path.join(B.CSRC, src), "-o", out]
-    subprocess.run(cmd, check=True, capture_output=True)
+    with tempfile.TemporaryDirectory(prefix="mirt_codegen_") as tmp:       # private: /tmp is shared between users
+        out = os.path.join(tmp, src + ".s")
+        cmd = [B._hipcc()] + [c for c in B.COMMON if c != "-fPIC"] + ["-x", "hip", "-S", "--cuda-device-only", os.path.join(B.CSRC, src), "-o", out]
+        subprocess.run(cmd, check=True, capture_output=True)
+        asm = open(out).read()
     body, inside = [], False
-    for l in open(out).read().splitlines():
+    for l in asm.splitlines():
         if re.match(r"^_ZN4mirt.*" + kernel + r".*:", l):
             inside = True
             continue

@@ -25,13 +25,14 @@ _COMPILED = {}
 def _compile(defines):
     """render.hip -> (resource-usage remarks, gfx950 assembly); one compilation per set of defines and process."""
     if defines not in _COMPILED:
-        out = os.path.join(tempfile.gettempdir(), "mirt_hotloop.s")
-        cmd = [B._hipcc()] + [c for c in B.COMMON if c != "-fPIC"] + list(defines) + ["-x", "hip", "-S", "--cuda-device-only", os.path.join(B.CSRC, "render.hip"),
-                                                                                   "-o", out, "-Rpass-analysis=kernel-resource-usage"]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(r.stderr[-2000:])
-        _COMPILED[defines] = (r.stderr, open(out).read())
+        with tempfile.TemporaryDirectory(prefix="mirt_hotloop_") as tmp:       # private: /tmp is shared between users
+            out = os.path.join(tmp, "render.s")
+            cmd = [B._hipcc()] + [c for c in B.COMMON if c != "-fPIC"] + list(defines) + ["-x", "hip", "-S", "--cuda-device-only", os.path.join(B.CSRC, "render.hip"),
+                                                                                       "-o", out, "-Rpass-analysis=kernel-resource-usage"]
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError(r.stderr[-2000:])
+            _COMPILED[defines] = (r.stderr, open(out).read())
     return _COMPILED[defines]
 
 

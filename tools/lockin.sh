@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 T=${1:-lock}
 O=$R/gpurun_out/$T; mkdir -p $O
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err; cat $O/bench.json
+python bench.py --full > $O/bench.json 2> $O/bench.err; cat $O/bench.json
 python bench.py --serial --cpu-step 0 > $O/bench_serial.json 2>/dev/null; cat $O/bench_serial.json
 cd /tmp
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --steps 6 --warmup 2 --cpu-step 0 > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err

@@ -17,7 +17,7 @@ if [ "$3" != "nopmc" ]; then
   rm -rf $R/gpurun_out/pmc_$T
   for f in $O/pmc_trace_kernel*.json; do cp $f profiles/${T}_$(basename $f); done
 fi
-timeout -k 10 600 python bench.py > $O/bench_tenthousand_1080p16.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench_tenthousand_1080p16.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 cut -c1-1200 $O/bench_tenthousand_1080p16.json
 timeout -k 10 200 python bench.py --serial --cpu-step 0 --headline-only > $O/bench_tenthousand_1080p16_serial.json 2>/dev/null || exit 1
 cd /tmp

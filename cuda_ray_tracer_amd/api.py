@@ -22,6 +22,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MIRT_LIB") or os.path.join(HERE, "_build", "libmirt.so")
 
 MIRT_RENDER_COUNTERS = 1
+MIRT_HIT_NONE, MIRT_HIT_SPHERE, MIRT_HIT_TRIANGLE, MIRT_HIT_PLANE = 0, 1, 2, 3
+MIRT_QUERY_ANY_HIT = 1
 
 
 class MirtError(RuntimeError):
@@ -36,6 +38,16 @@ class Vec3(C.Structure):
 
     def tolist(self):
         return [self.x, self.y, self.z]
+
+
+class Ray(C.Structure):
+    """MirtRay: one row of a float32 [n, 8] ray tensor (pack_rays)."""
+    _fields_ = [("o", Vec3), ("tmax", C.c_float), ("d", Vec3), ("pad", C.c_float)]
+
+
+class Hit(C.Structure):
+    """MirtHit: one row of a 4-byte [n, 6] hit tensor (unpack_hits)."""
+    _fields_ = [("t", C.c_float), ("kind", C.c_uint32), ("id", C.c_uint32), ("n", Vec3)]
 
 
 class SceneDesc(C.Structure):
@@ -89,6 +101,7 @@ EXPORTS = [
     "mirt_get_stats", "mirt_get_tree", "mirt_probe_math", "mirt_probe_xorwow", "mirt_write_png",
     "mirt_multi_create", "mirt_multi_destroy", "mirt_multi_num_parts", "mirt_multi_set_option", "mirt_render_frame_multi",
     "mirt_multi_submit", "mirt_multi_wait", "mirt_render_frames_multi", "mirt_multi_get_stats", "mirt_part_pixel_xy",
+    "mirt_trace_rays", "mirt_camera_rays",
 ]
 
 _lib = None
@@ -144,6 +157,9 @@ def lib():
     L.mirt_render_frames_multi.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(MultiStats), C.POINTER(C.c_float)]
     L.mirt_multi_get_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(Stats)]
     L.mirt_part_pixel_xy.argtypes = [C.POINTER(RenderParams), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    if hasattr(L, "mirt_trace_rays"):      # (ray queries: a build that predates them -- MIRT_LIB A/B runs -- still loads)
+        L.mirt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.mirt_camera_rays.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -422,6 +438,85 @@ def finalize(d_image, d_accum, img_width, img_height, total_samples, params=None
 
 def scatter_part(params, d_part, d_frame, stream=None):
     _check(lib().mirt_scatter_part(C.byref(params), C.c_void_p(d_part.data_ptr()), C.c_void_p(d_frame.data_ptr()), _stream_ptr(stream)))
+
+
+# ------------------------------------------------------------------------------------------------------
+# Ray queries (mirt_trace_rays / mirt_camera_rays): rays are float32 [n, 8] tensors (MirtRay), hits 4-byte [n, 6] tensors (MirtHit)
+# ------------------------------------------------------------------------------------------------------
+def _query_layout(x, name, dtypes, cols, rows):
+    """ValueError unless x is a contiguous [rows, cols] tensor of one of the dtypes."""
+    import torch
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor")
+    if x.dtype not in dtypes:
+        raise ValueError(f"{name} has dtype {x.dtype}; expected one of {[str(d) for d in dtypes]}")
+    if x.dim() != 2 or x.shape[1] != cols or (rows is not None and x.shape[0] != rows):
+        raise ValueError(f"{name} has shape {list(x.shape)}; expected [{rows if rows is not None else 'n'}, {cols}]")
+    if not x.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def _query_device(x, name, raw):
+    """ValueError unless x is on the scene's device."""
+    import torch
+    if x.device.type != "cuda" or (x.device.index if x.device.index is not None else torch.cuda.current_device()) != raw.device:
+        raise ValueError(f"{name} is on {x.device}; the scene is on cuda:{raw.device}")
+
+
+def _hit_dtypes():
+    import torch
+    return tuple(d for d in (torch.float32, torch.int32, getattr(torch, "uint32", None)) if d is not None)
+
+
+def trace_rays(raw, d_rays, d_hits, any_hit=False, stream=None):
+    """mirt_trace_rays: closest hit (hitNearest, draw.cu:292-318) or, with any_hit, occlusion of every ray of d_rays (float32
+    [n, 8], MirtRay rows: pack_rays) into d_hits (a 4-byte dtype, [n, 6], MirtHit rows: unpack_hits).  Both contiguous and on
+    the scene's device.  Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    _query_layout(d_rays, "d_rays", (torch.float32,), 8, None)
+    _query_layout(d_hits, "d_hits", _hit_dtypes(), 6, d_rays.shape[0])
+    _query_device(d_rays, "d_rays", raw)
+    _query_device(d_hits, "d_hits", raw)
+    n = d_rays.shape[0]
+    _check(lib().mirt_trace_rays(raw._h, C.c_void_p(d_rays.data_ptr()) if n else None, n, C.c_void_p(d_hits.data_ptr()) if n else None,
+                                 MIRT_QUERY_ANY_HIT if any_hit else 0, _stream_ptr(stream)))
+
+
+def camera_rays(raw, d_rays, img_width, img_height, aa, params=None, stream=None):
+    """mirt_camera_rays: the primary ray of sample 0 of every pixel of the frame (or of the part `params` selects), in the order
+    render writes pixels, into d_rays (float32 [num_pixels, 8], contiguous, on the scene's device).  trace_rays of these rays
+    gives the render's primary hits."""
+    import torch
+    p = params if params is not None else render_params(img_width, img_height, aa)
+    _query_layout(d_rays, "d_rays", (torch.float32,), 8, num_pixels(p))
+    _query_device(d_rays, "d_rays", raw)
+    _check(lib().mirt_camera_rays(raw._h, C.byref(p), C.c_void_p(d_rays.data_ptr()), _stream_ptr(stream)))
+
+
+def pack_rays(origins, dirs, tmax=float("inf")):
+    """float32 [n, 8] MirtRay rows from origins [n, 3] (or [3]), directions [n, 3] (any non-zero length) and tmax (a number or
+    [n]), on the directions' device."""
+    import torch
+    dirs = torch.as_tensor(dirs, dtype=torch.float32)
+    if dirs.dim() != 2 or dirs.shape[1] != 3:
+        raise ValueError(f"dirs has shape {list(dirs.shape)}; expected [n, 3]")
+    n = dirs.shape[0]
+    out = torch.zeros((n, 8), dtype=torch.float32, device=dirs.device)
+    out[:, 0:3] = torch.as_tensor(origins, dtype=torch.float32, device=dirs.device)
+    out[:, 3] = torch.as_tensor(tmax, dtype=torch.float32, device=dirs.device)
+    out[:, 4:7] = dirs
+    return out
+
+
+def unpack_hits(hits):
+    """(t, kind, id, normal) views of a [n, 6] hit tensor: t float32 [n] (-1 for a miss), kind / id int32 [n] (MIRT_HIT_*; the
+    index into the scene's sphere, triangle or plane array), normal float32 [n, 3]."""
+    import torch
+    if hits.dim() != 2 or hits.shape[1] != 6 or hits.element_size() != 4:
+        raise ValueError(f"hits must be a 4-byte [n, 6] tensor, got {hits.dtype} {list(hits.shape)}")
+    f = hits.view(torch.float32)
+    i = hits.view(torch.int32)
+    return f[:, 0], i[:, 1], i[:, 2], f[:, 3:6]
 
 
 def write_png(path, rgba_u8_host, width, height):

@@ -334,6 +334,20 @@ int mirt_scatter_part(const MirtRenderParams* p, const void* d_part_rgba8, void*
   return scatter_part(p, d_part_rgba8, d_frame_rgba8, (hipStream_t)stream);
 }
 
+int mirt_trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits, uint32_t flags, void* stream)
+{
+  if (!sc) { set_error("mirt_trace_rays: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return trace_rays(sc, d_rays, num_rays, d_hits, flags, (hipStream_t)stream);
+}
+
+int mirt_camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, void* stream)
+{
+  if (!sc || !p) { set_error("mirt_camera_rays: null argument"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return camera_rays(sc, p, d_rays, (hipStream_t)stream);
+}
+
 int mirt_get_stats(MirtScene* sc, MirtStats* out)
 {
   if (!sc || !out) { set_error("mirt_get_stats: null argument"); return MIRT_ERR_ARG; }

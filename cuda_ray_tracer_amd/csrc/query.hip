@@ -1,0 +1,258 @@
+// Ray queries on a built scene (include/mirt.h: mirt_trace_rays, mirt_camera_rays): the reference's hitNearest (draw.cu:292-318)
+// for rays a caller supplies, its occlusion test (diffuseLight's shadow rays, draw.cu:347-352, 365-370), and the primary rays of
+// a frame.  Not a path of the render: it reads the scene only and touches no render context, counter or hand-out order.
+//
+// trace_rays_kernel   one lane = one ray (grid-stride over the batch): the planes (checkPlane, draw.cu:581-615), then the walk
+//                     of traverse_lbvh (bvh_traversal.cu:92-183) over the exact 64-byte node records, left child first -- the
+//                     reference's own walk, so no vetting and no second walk is ever needed.  A lane carries the ray, 1/d, the
+//                     best distance and record and a stack pointer; the stack lives in LDS ([entry][lane]), entries deeper
+//                     than QSTACK_LDS in a per-lane private array (scratch) that the bundled scenes rarely reach.
+// camera_rays_kernel  one lane = one pixel: the ray sample 0 of the pixel starts with in the render (init_sample_core +
+//                     primary_ray), before the Ray constructor normalises its direction.
+#include "scene_dev.h"
+#include "host_scene.h"
+#include "shade_common.h"
+
+#include <cmath>
+#include <cstring>
+#include <string>
+
+namespace mirt {
+namespace {
+
+constexpr int QBLOCK = 256;
+// 64 VGPRs: 8 waves per SIMD, 32 per CU.  LDS: QSTACK_LDS x 4 B x 64 lanes = 5 KiB per wave, 160 KiB per CU at full occupancy.
+constexpr int QWAVES_PER_SIMD = 8;
+constexpr int QSTACK_LDS = 20;
+
+struct QueryArgs {
+  const float4* rays;             // MirtRay: (o, tmax), (d, pad)
+  uint32_t* hits;                 // MirtHit: 6 words
+  long long num_rays;
+  const float4* nodes;            // record heap (scene_dev.h)
+  const uint32_t* unit_prim;
+  const PlaneDev* planes; int num_planes;
+  uint32_t root_ref;              // the exact records' root (REF_NONE: no primitive)
+  uint32_t prim_base16;
+  int lds_depth;                  // stack entries kept in LDS (<= QSTACK_LDS)
+};
+
+template <bool ANY>
+__global__ void __launch_bounds__(QBLOCK, QWAVES_PER_SIMD) trace_rays_kernel(const QueryArgs q)
+{
+  __shared__ uint32_t lds_stack[QSTACK_LDS * QBLOCK];
+  uint32_t spill[STACK_TOTAL];                     // (entries lds_depth.. of the lane's stack: the rarely taken spill path)
+  const int tid = threadIdx.x;
+  const long long stride = (long long)gridDim.x * QBLOCK;
+  const unsigned char* const heap = reinterpret_cast<const unsigned char*>(q.nodes);
+  const float tmin = 0.0001f;
+  for (long long i = (long long)blockIdx.x * QBLOCK + tid; i < q.num_rays; i += stride) {
+    const float4 r0 = q.rays[2 * i], r1 = q.rays[2 * i + 1];
+    const f3 o = mk3(r0.x, r0.y, r0.z);
+    const float tmax = r0.w;
+    const f3 d = normalize(mk3(r1.x, r1.y, r1.z));      // Ray(eye, dir, bounce), object.cuh:69
+    // a ray with nothing to look for (tmax <= 0 or NaN) or no direction (shorter than normalize's 1e-6, or NaN) is a miss
+    const bool live = tmax > 0.0f && (fabsf(d.x) + fabsf(d.y) + fabsf(d.z)) > 0.0f;
+    float tplane = INFINITY, tbest = INFINITY;
+    int plane_id = -1;
+    uint32_t refbest = REF_NONE;
+    if (live) nearest_plane(q.planes, q.num_planes, o, d, tplane, plane_id);
+    // an occlusion query that a plane already answers needs no walk
+    if (live && q.root_ref != REF_NONE && !(ANY && plane_id >= 0 && tplane < tmax)) {
+      const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+      uint32_t cur = q.root_ref;
+      int sp = 0;
+      for (;;) {
+        const float4* rec = reinterpret_cast<const float4*>(heap + (cur << 4));
+        bool pop;
+        if (cur & REF_LEAF) {
+          // intersect_leaf_primitives, bvh_traversal.cu:47-89
+          float t = 0.0f;
+          bool hit;
+          if (cur & REF_TRI) {
+            hit = triangle_hit(rec[0], rec[1], rec[2], o, d, t);
+          } else {
+            float tc, t_far;
+            hit = sphere_hit(rec[0], o, d, t, tc, t_far);
+          }
+          const bool closer = closer_hit(hit, t, tbest, cur & REF_OFFMASK, refbest);
+          tbest = closer ? t : tbest;
+          refbest = closer ? cur : refbest;
+          if (ANY && closer && t < tmax) break;           // the first occluder ends an occlusion query
+          pop = true;
+        } else {
+          // hit_aabb_adapted on both children, left first (bvh_traversal.cu:11-44, 149-157)
+          const float4 b0 = rec[0], b1 = rec[1], b2 = rec[2];
+          const uint2 ch = *reinterpret_cast<const uint2*>(rec + 3);
+          bool hl, hr;
+          float tel, ter;
+          box_pair(b0, b1, b2, o.x, o.y, o.z, inv.x, inv.y, inv.z, tbest, tmin, hl, hr, tel, ter);
+          if (hl && hr) {
+            // (the tree is at most 58 levels deep, DESIGN.md section 1: sp stays below STACK_TOTAL; the mask only bounds the index)
+            if (sp < q.lds_depth) lds_stack[sp * QBLOCK + tid] = ch.y;
+            else spill[(sp - q.lds_depth) & (STACK_TOTAL - 1)] = ch.y;
+            ++sp;
+          }
+          cur = hl ? ch.x : ch.y;
+          pop = !(hl || hr);
+        }
+        if (pop) {
+          if (sp == 0) break;
+          --sp;
+          cur = sp < q.lds_depth ? lds_stack[sp * QBLOCK + tid] : spill[(sp - q.lds_depth) & (STACK_TOTAL - 1)];
+        }
+      }
+    }
+    // hitNearest: the nearer of BVH hit and plane hit, the plane winning a tie (draw.cu:292-318); an occlusion query reports the
+    // occluder it found.  Then the caller's bound (draw.cu:365-370).
+    const bool bvh_hit = refbest != REF_NONE;
+    const bool use_bvh = bvh_hit && (ANY ? tbest < tmax : (plane_id < 0 || tbest < tplane));
+    const float t = use_bvh ? tbest : tplane;
+    const bool report = (use_bvh || plane_id >= 0) && t < tmax;
+    uint32_t kind = 0u, id = 0u;
+    f3 n = mk3(0.0f, 0.0f, 0.0f);
+    if (report) {
+      // ObjectInfo.normal of the winner, from p = t d + o (struct.cu:64-163, draw.cu:581-615)
+      if (use_bvh) {
+        const uint32_t off16 = refbest & REF_OFFMASK;
+        const float4* rec = q.nodes + off16;
+        id = q.unit_prim[off16 - q.prim_base16] & 0x7fffffffu;
+        if (refbest & REF_TRI) {
+          const float4 q0 = rec[0], q1 = rec[1];
+          const f3 nor = mk3(q0.w, q1.x, q1.y);
+          n = (dot(d, nor) < 0.0f) ? nor : -nor;
+          kind = MIRT_HIT_TRIANGLE;
+        } else {
+          const float4 s = rec[0];
+          const f3 c = mk3(s.x, s.y, s.z);
+          const f3 p = t * d + o;
+          const f3 cr0 = c - o;
+          const bool inside = (dot(cr0, cr0) < s.w * s.w);
+          n = normalize(inside ? (c - p) : (p - c));
+          kind = MIRT_HIT_SPHERE;
+        }
+      } else {
+        typedef const PlaneDev __attribute__((address_space(4))) * ConstPlanes;
+        const ConstPlanes planes = (ConstPlanes)(unsigned long long)q.planes;
+        const f3 pnor = mk3(planes[plane_id].nx, planes[plane_id].ny, planes[plane_id].nz);
+        n = (dot(pnor, d) < 0.0f) ? pnor : -pnor;
+        id = (uint32_t)plane_id;
+        kind = MIRT_HIT_PLANE;
+      }
+    }
+    uint32_t* const h = q.hits + 6 * i;
+    h[0] = __float_as_uint(report ? t : -1.0f);
+    h[1] = kind;
+    h[2] = id;
+    h[3] = __float_as_uint(n.x);
+    h[4] = __float_as_uint(n.y);
+    h[5] = __float_as_uint(n.z);
+  }
+}
+
+// init_sample_core (sample 0 of local pixel i of the part) + primary_dir
+__global__ void __launch_bounds__(QBLOCK) camera_rays_kernel(const RenderArgs a, float4* __restrict__ rays, long long num_pixels)
+{
+  const long long i = (long long)blockIdx.x * QBLOCK + threadIdx.x;
+  if (i >= num_pixels) return;
+  // local pixel of the part -> frame pixel, as init_sample_core does it (a part has < 2^31 pixels: checked by camera_rays)
+  const uint32_t stripe_pixels = (uint32_t)a.stripe_rows * (uint32_t)a.width;
+  const uint32_t lp = (uint32_t)i;
+  const uint32_t ls = lp / stripe_pixels;
+  const uint32_t within = lp - ls * stripe_pixels;
+  const uint32_t gs = ls * (uint32_t)a.num_parts + (uint32_t)a.part;
+  const uint32_t wy = within / (uint32_t)a.width;
+  const int py = (int)(gs * (uint32_t)a.stripe_rows + wy);
+  const int px = (int)(within - wy * (uint32_t)a.width);
+  const uint32_t pixel = (uint32_t)py * (uint32_t)a.width + (uint32_t)px;
+  Xorwow rng;
+  rng.v0 = rng.v1 = rng.v2 = rng.v3 = rng.v4 = rng.d = 0; rng.bm_flag = 0; rng.bm_extra = 0.0f;
+  // curand_init(1234 + pixel, 0, 0) for spp > 1 (draw.cu:162), curand_init(1234, pixel, 0) otherwise (draw.cu:105): the tables
+  // camera_rays loaded say which
+  if (a.needs_rng) xw_init(rng, a.rng, pixel, 0u);
+  float fx = (float)px, fy = (float)py;
+  if (a.spp >= 1) {
+    const float jx = randD(-0.5f, 0.5f, rng);
+    const float jy = randD(-0.5f, 0.5f, rng);
+    fx = (float)px + jx; fy = (float)py + jy;
+  }
+  const RayS r = primary_dir(a, fx, fy, rng);
+  // hitNearest answers a bounce-0 ray with nothing (draw.cu:294)
+  rays[2 * i] = make_float4(r.o.x, r.o.y, r.o.z, r.bounce == 0 ? 0.0f : INFINITY);
+  rays[2 * i + 1] = make_float4(r.d.x, r.d.y, r.d.z, 0.0f);
+}
+
+int query_grid_blocks(int device)
+{
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess) return 1024;
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_rays_kernel<false>, QBLOCK, 0) != hipSuccess || per_cu < 1)
+    per_cu = QWAVES_PER_SIMD * 4 * 64 / QBLOCK;
+  return prop.multiProcessorCount * per_cu;
+}
+
+} // namespace
+
+int trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits, uint32_t flags, hipStream_t stream)
+{
+  if ((flags & ~(uint32_t)MIRT_QUERY_ANY_HIT) != 0u) { set_error("mirt_trace_rays: unknown flag bits"); return MIRT_ERR_ARG; }
+  if (num_rays < 0) { set_error("mirt_trace_rays: negative num_rays"); return MIRT_ERR_ARG; }
+  if (num_rays > 0 && (!d_rays || !d_hits)) { set_error("mirt_trace_rays: null buffer"); return MIRT_ERR_ARG; }
+  if (((uintptr_t)d_rays & 15u) != 0u || ((uintptr_t)d_hits & 3u) != 0u) {
+    set_error("mirt_trace_rays: d_rays must be 16-byte aligned, d_hits 4-byte aligned"); return MIRT_ERR_ARG;
+  }
+  if (!sc->built) { set_error("mirt_trace_rays: call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
+  if (num_rays == 0) return MIRT_OK;
+  if (!sc->query_blocks) sc->query_blocks = query_grid_blocks(sc->device);      // per scene, i.e. per device
+  QueryArgs q;
+  q.rays = reinterpret_cast<const float4*>(d_rays);
+  q.hits = reinterpret_cast<uint32_t*>(d_hits);
+  q.num_rays = num_rays;
+  q.nodes = sc->nodes; q.unit_prim = sc->unit_prim;
+  q.planes = sc->planes; q.num_planes = sc->d.num_planes;
+  q.root_ref = sc->root_ref; q.prim_base16 = sc->prim_base / 16u;
+  const int opt = sc->opt.stack_lds_depth;
+  q.lds_depth = (opt >= 0 && opt < QSTACK_LDS) ? opt : QSTACK_LDS;      // tests force the spill path
+  const long long want = (num_rays + QBLOCK - 1) / QBLOCK;
+  const int blocks = (int)(want < sc->query_blocks ? want : sc->query_blocks);
+  if (flags & MIRT_QUERY_ANY_HIT) hipLaunchKernelGGL(trace_rays_kernel<true>, dim3(blocks), dim3(QBLOCK), 0, stream, q);
+  else hipLaunchKernelGGL(trace_rays_kernel<false>, dim3(blocks), dim3(QBLOCK), 0, stream, q);
+  MIRT_HIP(hipGetLastError());
+  return MIRT_OK;
+}
+
+int camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, hipStream_t stream)
+{
+  const int64_t npix = render_num_pixels(p);
+  if (npix < 0 || p->spp < 0) { set_error("mirt_camera_rays: bad parameters"); return MIRT_ERR_ARG; }
+  if (npix > 0 && !d_rays) { set_error("mirt_camera_rays: null buffer"); return MIRT_ERR_ARG; }
+  if (((uintptr_t)d_rays & 15u) != 0u) { set_error("mirt_camera_rays: d_rays must be 16-byte aligned"); return MIRT_ERR_ARG; }
+  if ((int64_t)p->width * p->height > 0x7fffffffll - 1234) { set_error("mirt_camera_rays: frame too large for the 32-bit pixel seed"); return MIRT_ERR_ARG; }
+  if (npix == 0) return MIRT_OK;
+  if (npix >= 0x7fffffffll || (long long)p->stripe_rows * p->width >= 0x7fffffffll) { set_error("mirt_camera_rays: part too large"); return MIRT_ERR_ARG; }
+  RenderArgs a;
+  memset(&a, 0, sizeof(a));
+  a.width = p->width; a.height = p->height; a.bounces = sc->d.bounces; a.spp = p->spp;
+  a.fisheye = sc->d.fisheye; a.panorama = sc->d.panorama;
+  a.dof_focus = sc->d.dof_focus; a.dof_lens = sc->d.dof_lens;
+  a.forward.x = sc->d.forward.x; a.forward.y = sc->d.forward.y; a.forward.z = sc->d.forward.z;
+  a.right.x = sc->d.right.x; a.right.y = sc->d.right.y; a.right.z = sc->d.right.z;
+  a.up.x = sc->d.up.x; a.up.y = sc->d.up.y; a.up.z = sc->d.up.z;
+  a.eye.x = sc->d.eye.x; a.eye.y = sc->d.eye.y; a.eye.z = sc->d.eye.z;
+  a.stripe_rows = p->stripe_rows; a.num_parts = p->num_parts; a.part = p->part;
+  // the primary ray consumes random numbers for the jitter (spp >= 1) and the lens (depth of field), nothing else
+  a.needs_rng = (p->spp >= 1) || (sc->d.dof_focus != 0.0f && !sc->d.fisheye && !sc->d.panorama);
+  if (a.needs_rng) {
+    // spp > 1: sample 0's tables -- any cached sample table covers it (a render's larger one is not evicted); else the per-pixel
+    // tables of the frame
+    int rc = ensure_rng_tables(&sc->rng, p->spp > 1 ? 1 : 0, (long long)p->width * p->height, stream, &a.rng, true);
+    if (rc != MIRT_OK) return rc;
+  }
+  const int blocks = (int)((npix + QBLOCK - 1) / QBLOCK);
+  hipLaunchKernelGGL(camera_rays_kernel, dim3(blocks), dim3(QBLOCK), 0, stream, a, reinterpret_cast<float4*>(d_rays), (long long)npix);
+  MIRT_HIP(hipGetLastError());
+  return MIRT_OK;
+}
+
+} // namespace mirt

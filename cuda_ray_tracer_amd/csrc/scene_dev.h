@@ -273,6 +273,7 @@ struct MirtScene {
   bool colors_finite = true;               // every material colour and light colour is finite (0 * colour == 0)
   bool any_trans = false;                  // some material has transparency != 0
   bool any_rough = false;
+  int query_blocks = 0;                    // grid size of the ray-query kernel on this scene's device (query.hip; filled on first use)
 };
 
 namespace mirt {
@@ -294,6 +295,9 @@ int ensure_rng_tables(RngCache* rc, int sample_tables, long long frame_pixels, h
 int render_accumulate(MirtScene* sc, const MirtRenderParams* p, void* d_accum, int sample_first, int sample_count, hipStream_t stream);
 int finalize(const MirtRenderParams* p, const void* d_accum, int total_samples, void* d_rgba8, hipStream_t stream);
 void rng_cache_free(RngCache* rc);
+// query.hip
+int trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits, uint32_t flags, hipStream_t stream);
+int camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, hipStream_t stream);
 // wavefront.hip
 int wavefront_trace(MirtScene* sc, RenderCtx& cx, RenderArgs& a, bool count, hipStream_t stream, float* trace_ms);
 }

@@ -1,7 +1,8 @@
 // Device code shared by the render kernels: the shading state machine (the reference's recursive
 // shootPrimaryRay / diffuseLight / reflectionLight / refractionLight / globalIllumination, draw.cu:260-568, as an explicit
 // ray-tree walk), the camera (struct.cu:16-62), plane test (draw.cu:581-615) and per-lane state.  Included by
-// render.hip (single-kernel path) and wavefront.hip (trace / shade kernel pair).
+// render.hip (single-kernel path) and wavefront.hip (trace / shade kernel pair); query.hip (ray queries) uses the camera,
+// the primitive and box tests.
 #ifndef MIRT_SHADE_COMMON_H
 #define MIRT_SHADE_COMMON_H
 
@@ -50,8 +51,9 @@ MIRT_DEV float set_expose(float c, float expose)
 struct RayS { f3 o, d; int bounce; };
 MIRT_DEV RayS mkray(const f3& o, const f3& d, int bounce) { RayS r; r.o = o; r.d = normalize(d); r.bounce = bounce; return r; }
 
-// Ray::Ray(x, y, state, config), struct.cu:16-62
-MIRT_DEV RayS primary_ray(const RenderArgs& a, float x, float y, Xorwow& rng)
+// Ray::Ray(x, y, state, config), struct.cu:16-62, up to the constructor's normalisation: r.d is the direction as the camera
+// computes it (mirt_camera_rays writes it; mirt_trace_rays normalises it the way primary_ray does)
+MIRT_DEV RayS primary_dir(const RenderArgs& a, float x, float y, Xorwow& rng)
 {
   const float PI = 3.14159265358979323846f;
   const float max_dim = fmaxf((float)a.width, (float)a.height);
@@ -81,7 +83,14 @@ MIRT_DEV RayS primary_ray(const RenderArgs& a, float x, float y, Xorwow& rng)
     dir = a.forward + sx * a.right + sy * a.up;
   }
   r.bounce = a.bounces;
-  r.d = normalize(dir);
+  r.d = dir;
+  return r;
+}
+
+MIRT_DEV RayS primary_ray(const RenderArgs& a, float x, float y, Xorwow& rng)
+{
+  RayS r = primary_dir(a, x, y, rng);
+  r.d = normalize(r.d);
   return r;
 }
 
@@ -321,6 +330,25 @@ struct Lane {
   float tbest;
   uint32_t refbest;
 };
+
+// checkPlane, draw.cu:581-615: the nearest plane hit (plane_id -1: none).  The loop of start_ray below, for the query kernel
+// (query.hip); start_ray keeps its own copy: calling this from there moved the trace kernels' register allocation.
+MIRT_DEV void nearest_plane(const PlaneDev* planes_in, int num_planes, const f3& o, const f3& d, float& tplane, int& plane_id)
+{
+  tplane = INFINITY;
+  plane_id = -1;
+  // (the planes are the same for every lane and never written by a kernel: read them through the constant address space,
+  // i.e. with scalar loads, not through the per-lane address unit)
+  typedef const PlaneDev __attribute__((address_space(4))) * ConstPlanes;
+  const ConstPlanes planes = (ConstPlanes)(unsigned long long)planes_in;
+  for (int i = 0; i < num_planes; ++i) {
+    const f3 pnor = mk3(planes[i].nx, planes[i].ny, planes[i].nz);
+    const float t = dot(mk3(planes[i].px, planes[i].py, planes[i].pz) - o, pnor) / dot(d, pnor);
+    if (t <= 1e-6f) continue;
+    if (t < tplane && t > EPSILON) { tplane = t; plane_id = i; }
+  }
+  if (tplane >= (float)(INT_MAX - 10)) { tplane = INFINITY; plane_id = -1; }
+}
 
 // hitNearest's plane half (checkPlane, draw.cu:581-615) and the decision whether the BVH must be walked at all.
 template <bool COUNT, bool HAVE_INV = false, bool QN = false, typename Args = RenderArgs>

@@ -180,6 +180,50 @@ int mirt_part_pixel_xy(const MirtRenderParams* p, int64_t local, int32_t* x, int
 /* Scatter a compact part buffer back into a full row-major frame (device to device). */
 int mirt_scatter_part(const MirtRenderParams* p, const void* d_part_rgba8, void* d_frame_rgba8, void* stream);
 
+/* ---- ray queries on a built scene --------------------------------------------------------------- */
+/* What a ray hits, for rays the caller makes: the reference's hitNearest (draw.cu:292-318) and the occlusion test of diffuseLight
+ * (draw.cu:347-352, 365-370) as entry points, plus the primary rays of a frame.  Not in the reference (its rays never leave the
+ * render kernel).  Callers detect the feature by these symbols (MIRT_VERSION stays 3).
+ *
+ * MirtRay: origin, tmax, direction (any non-zero length), pad; 32 B, read as two 16-byte loads (d_rays 16-byte aligned).
+ * MirtHit: the primary-hit record: t (distance along the unit direction; -1 for a miss), kind (MIRT_HIT_*), id (index into the
+ * scene's sphere, triangle or plane array as passed in MirtSceneDesc, i.e. file order) and the normal n; 24 B (d_hits 4-byte
+ * aligned).  A miss is t = -1, kind 0, id 0, n = 0. */
+typedef struct MirtRay { MirtVec3 o; float tmax; MirtVec3 d; float pad; } MirtRay;        /* 32 B */
+typedef struct MirtHit { float t; uint32_t kind, id; MirtVec3 n; } MirtHit;              /* 24 B */
+#define MIRT_HIT_NONE 0
+#define MIRT_HIT_SPHERE 1
+#define MIRT_HIT_TRIANGLE 2
+#define MIRT_HIT_PLANE 3
+#define MIRT_QUERY_ANY_HIT 1u
+/* num_rays rays from d_rays -> num_rays records to d_hits (device pointers).
+ * flags 0, closest hit: the ray is Ray(eye, dir, bounce) (object.cuh:69): d normalised by vec3::normalize (vec3.cuh:72-82).  The
+ *   answer is hitNearest of that ray, bit for bit: traverse_lbvh (bvh_traversal.cu:92-183) -- from node 0, left child first, box
+ *   test with tmin 1e-4 and te < best, a leaf accepted when 1e-6 < t < best, ties to the earlier sorted leaf -- then checkPlane
+ *   (draw.cu:581-615), the BVH hit winning only when strictly nearer.  It is reported only if t < tmax (the test diffuseLight
+ *   applies to a bulb, draw.cu:365-370), otherwise the record is a miss.  The normal is ObjectInfo.normal with p = t d + o:
+ *   sphere normalize(inside ? c - p : p - c) (struct.cu:64-109), triangle denom < 0 ? nor : -nor (struct.cu:111-163), plane
+ *   dot(n, d) < 0 ? n : -n (draw.cu:581-615).
+ * MIRT_QUERY_ANY_HIT, occlusion: kind != 0 exactly when something is hit at t < tmax -- the same boolean as the closest-hit
+ *   query with the same tmax (the render's shadow_anyhit relies on it).  The planes are asked first; the walk ends at the first
+ *   leaf hit with t < tmax.  The record is the occluder found, not necessarily the nearest.
+ * Both walk the exact 64-byte node records in the reference's order (never the quantised or wide ones): the reference's result
+ * by construction.  A ray with tmax <= 0 or NaN, or with a direction that normalises to 0 or NaN, is a miss and is not walked.
+ * Asynchronous on `stream`; reads the scene only (no render workspace, MirtStats counter or random-number table), so it may run
+ * on another stream while a frame is in flight.  No allocation and no synchronisation: one launch.  num_rays 0: MIRT_OK, nothing
+ * launched.  MIRT_ERR_ARG: null scene, num_rays < 0, a null or misaligned buffer with num_rays > 0, unknown flag bits;
+ * MIRT_ERR_STATE before mirt_build_lbvh. */
+int mirt_trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits, uint32_t flags, void* stream);
+/* The primary rays of a frame (or part, p as for mirt_render; p->flags ignored): mirt_render_num_pixels(p) rays in the part's
+ * compact order.  Ray i is the one sample 0 of its pixel starts with in the render: curand_init(1234, pixel, 0) for spp <= 1
+ * (draw.cu:105), curand_init(1234 + pixel, 0, 0) for spp > 1 (draw.cu:162), the pixel jittered for spp >= 1 (draw.cu:110-118,
+ * 165-171), fisheye / panorama / depth of field as the scene sets them (Ray::Ray, struct.cu:16-62).  o is the ray's origin (the
+ * lens point with depth of field), d its direction BEFORE the Ray constructor normalises it -- mirt_trace_rays normalises it
+ * once, so camera rays followed by a closest-hit query give the render's primary hit bit for bit.  tmax = +inf, or 0 when the
+ * scene's bounces is 0 (hitNearest answers a bounce-0 ray with nothing, draw.cu:294).  Uses the scene's random-number table
+ * cache: with spp > 1 any cached sample table serves. */
+int mirt_camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, void* stream);
+
 /* ---- several GPUs in one process --------------------------------------------------------------- */
 /* Not in the reference (single GPU, main.cu:25-94).  The scene is uploaded to every listed device and every device builds
  * the identical LBVH; a frame is cut into interleaved stripes of `stripe_rows` rows, device r renders part r (a

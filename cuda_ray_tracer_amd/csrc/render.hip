@@ -741,7 +741,9 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
   const bool qn = sc->grid_ok && (notri ? (qwant && opt.traversal >= 1 && sc->root_ref_q != REF_NONE)
                                         : (qwant && opt.traversal == 1 && sc->root_ref_w != REF_NONE && (opt.qnodes >= 2 || sc->N >= 65536)));
   // kernels specialised for what the scene does not have (SPEC_*, shade_common.h)
-  const bool nobulb = opt.specialise != 0 && sc->d.num_bulbs == 0, nopend = opt.specialise != 0 && !need_pending;
+  // (a scene with a non-finite colour gets the general kernels: only they carry the colour * 0 terms, gi_zero_term)
+  const bool specialise = opt.specialise != 0 && sc->colors_finite;
+  const bool nobulb = specialise && sc->d.num_bulbs == 0, nopend = specialise && !need_pending;
   a.root_ref = qn ? (notri ? sc->root_ref_q : sc->root_ref_w) : sc->root_ref; a.num_spheres = sc->Ns; a.num_prims = sc->N;
   a.qparams = qn ? sc->qparams : nullptr;
   a.tri_boxes = sc->tri_boxes;
@@ -754,6 +756,7 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
   a.swap_mask = opt.traversal == 1 ? ((qn && notri) ? NODE_SWAP_PURE : 0u) : (opt.traversal == 2 ? NODE_SWAP_ANY : 0u);
   a.skip_unlit = (opt.skip_unlit != 0 && sc->colors_finite && sc->d.num_suns + sc->d.num_bulbs <= 32) ? 1 : 0;
   a.shadow_anyhit = opt.shadow_anyhit != 0 ? 1 : 0;
+  a.nonfinite_colours = sc->colors_finite ? 0 : 1;
   a.planes = sc->planes; a.num_planes = sc->d.num_planes;
   a.suns = sc->suns; a.num_suns = sc->d.num_suns;
   a.bulbs = sc->bulbs; a.num_bulbs = sc->d.num_bulbs;

@@ -84,6 +84,7 @@ struct RenderArgs {
   int num_spheres;
   int num_prims;
   const PlaneDev* planes; int num_planes;
+  int nonfinite_colours;          // 1: some colour of the scene (or its exposure) is inf or NaN: terms that are colour * 0 are not dropped (advance_core, gi_zero_term; general kernels only)
   const LightDev* suns; int num_suns;
   const LightDev* bulbs; int num_bulbs;
   // rng

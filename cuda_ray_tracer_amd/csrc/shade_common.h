@@ -601,6 +601,7 @@ template <bool COUNT, int SPEC = 0>
 MIRT_DEV int advance_core(const RenderArgs& a, Lane& S, Counters& cn, const long long gid, const long long gthreads)
 {
   constexpr bool NOTRI = (SPEC & SPEC_NOTRI) != 0, NOBULB = (SPEC & SPEC_NOBULB) != 0, NOPEND = (SPEC & SPEC_NOPEND) != 0;
+  constexpr bool GENERAL = !NOBULB && !NOPEND;
   (void)gthreads;
   const int nlights = NOBULB ? a.num_suns : a.num_suns + a.num_bulbs;
   int micro = M_TRACE;
@@ -680,6 +681,7 @@ MIRT_DEV int advance_core(const RenderArgs& a, Lane& S, Counters& cn, const long
       micro = (S.bounce == 0) ? M_POP : M_TRACE;
     } else if (!hit) {
       // primary miss: RGBA(0,0,0,0) (draw.cu:267,284).  A secondary miss contributes nothing to rgb.
+      if (GENERAL && S.state == ST_GI && a.nonfinite_colours) S.L = S.L + S.wt * 0.0f;      // (gi_zero_term: the gi ray missed)
       micro = (S.state == ST_PRIMARY) ? M_DONE : M_POP;
     } else {
       // refraction arguments X of the node being entered: the parent's H after a reflection (draw.cu:424), else H itself
@@ -700,6 +702,12 @@ MIRT_DEV int advance_core(const RenderArgs& a, Lane& S, Counters& cn, const long
       const f3 K = (one - Sh) * (one - T);
       // (a full pending list would drop the child: counted, and mirt_get_stats reports it as an error -- the list is sized for
       // the deepest chain the scene's bounces / gi allow, so this does not happen)
+      // gi_zero_term: the reference adds mat.color * globalIllumination(...) to the diffuse term of a primary or gi hit even when
+      // gi is off or used up and the result is RGBA() (draw.cu:274, 541, 558): 0 for a finite colour, NaN for inf or NaN.  Only a
+      // scene with such a colour executes it, and only the general kernels hold the code (the host gives such a scene no
+      // specialised one: the trace kernels sit at their register ceiling); the same goes for a gi ray that has bounce 0 or
+      // misses (draw.cu:549-553).
+      if (GENERAL && a.nonfinite_colours && has_gi && (a.gi == 0 || S.gi_n == 0)) S.L = S.L + (S.wt * K) * (nm.color * 0.0f);
       if (NOPEND) { has_gi = false; XtransNZ = false; }      // (gi 0 and no transparent material: nothing is ever pending)
       if (has_gi && a.gi != 0 && S.gi_n != 0 && S.pc >= a.pending_slots) atomicAdd(a.overflow, 1ull);
       if (XtransNZ && Xbounce > 0 && S.pc + ((has_gi && a.gi != 0 && S.gi_n != 0) ? 1 : 0) >= a.pending_slots) atomicAdd(a.overflow, 1ull);
@@ -764,6 +772,7 @@ MIRT_DEV int advance_core(const RenderArgs& a, Lane& S, Counters& cn, const long
           set_ray(S, mkray(p + n * EPSILON, gi_dir, ib - 1));
           S.gi_n = ib - 1;
           S.state = ST_GI;
+          if (GENERAL && S.bounce == 0 && a.nonfinite_colours) S.L = S.L + S.wt * 0.0f;      // (gi_zero_term: a bounce-0 ray never hits)
           micro = (S.bounce == 0) ? M_POP : M_TRACE;
         } else {
           // refractionLight, draw.cu:456-480

@@ -567,16 +567,40 @@ struct Obj {
   uint32_t kind, id; /* bookkeeping only: 1 sphere, 2 triangle, 3 plane */
   uint32_t leaf;     /* bookkeeping: sorted position of the primitive (its leaf is node N - 1 + leaf) */
   bool literal;      /* bookkeeping: the result of a second, literal walk (ORC_FLAG_QNODES / ORC_FLAG_REACH) */
+  float tc, t_far;   /* bookkeeping, sphere hits: the parameter of the point nearest the centre and of the far intersection */
 };
-static inline Obj obj_none() { Obj o; o.isHit = false; o.distance = -1.0f; o.i_point = mk(0, 0, 0); o.normal = mk(0, 0, 0); o.mat = mat_default(); o.kind = 0; o.id = 0; o.leaf = 0; o.literal = false; return o; }
+static inline Obj obj_none() { Obj o; o.isHit = false; o.distance = -1.0f; o.i_point = mk(0, 0, 0); o.normal = mk(0, 0, 0); o.mat = mat_default(); o.kind = 0; o.id = 0; o.leaf = 0; o.literal = false; o.tc = 0.0f; o.t_far = 0.0f; return o; }
 static inline Obj obj_hit(float t, const V3& p, const V3& n, const Mat& m, uint32_t kind, uint32_t id)
-{ Obj o; o.isHit = true; o.distance = t; o.i_point = p; o.normal = n; o.mat = m; o.kind = kind; o.id = id; o.leaf = 0; o.literal = false; return o; }
+{ Obj o; o.isHit = true; o.distance = t; o.i_point = p; o.normal = n; o.mat = m; o.kind = kind; o.id = id; o.leaf = 0; o.literal = false; o.tc = 0.0f; o.t_far = 0.0f; return o; }
+
+/* Branch counters of the shading recursion (orc_render_branches; tests/oracle_lib.py BRANCH_FIELDS names them in this order).
+ * They say which paths of draw.cu:292-568 a scene takes -- tests/test_shade_matrix.py requires the scenes of tests/shade_scenes.py to
+ * reach the ones they were built for.  Not part of OStats: the product has no counterpart to compare them with. */
+enum {
+  BR_REFR_ENTERED,        /* refractionLight past its early return (draw.cu:456-470) */
+  BR_REFR_TIR_FIRST,      /* ... the first interface totally reflects: k < 0 (needs ior < 1) */
+  BR_REFR_INSIDE_MISS,    /* ... the inside ray hits nothing: the default ObjectInfo is used (no miss check, draw.cu:482-487) */
+  BR_REFR_SECOND_K_NEG,   /* ... k < 0 at the second interface: sqrtf(k) is NaN, and so is the final ray */
+  BR_REFR_INSIDE_PLANE,   /* ... the inside ray ends on a plane */
+  BR_REFR_FINAL_BOUNCE0,  /* ... the final ray has bounce 0 (it never hits, draw.cu:294) */
+  BR_REFR_ON_PLANE,       /* ... the transparent object is a plane */
+  BR_REFR_ON_TRIANGLE,    /* ... a triangle */
+  BR_GI_BOUNCE0,          /* the gi ray has bounce 0 */
+  BR_REFL_BOUNCE0,        /* reflectionLight past its early return whose ray would have bounce - 1 == 0: not traced by the product */
+  BR_UNLIT_SKIPPED,       /* a light the shading normal faces away from, answered without a shadow ray (ORC_FLAG_SKIP_UNLIT) */
+  BR_SHADOW_BY_PLANE,     /* a shadow ray answered by a plane before any walk (ORC_FLAG_ANYHIT_SHADOW) */
+  BR_DIFFUSE_OVER_32,     /* diffuseLight evaluated in a scene with more than 32 lights */
+  BR_DIFFUSE_NO_LIGHTS,   /* ... in a scene without lights */
+  BR_PLANE_WINS_TIE,      /* hitNearest: BVH hit and plane hit at exactly the same distance (the plane is taken, draw.cu:311) */
+  BR_COUNT
+};
 
 struct Ctx {
   const Scene* sc;
   int width, height;      /* frame size used by the camera (struct.cu:17-20) */
   uint32_t flags;
   OStats st;
+  uint64_t br[BR_COUNT] = {};
 };
 
 /* struct.cu:64-109 */
@@ -597,7 +621,9 @@ static Obj check_sphere(const Ctx& cx, const Ray& ray, uint32_t idx)
   V3 p = t * ray.dir + ray.eye;
   V3 nor = inside ? (c - p) : (p - c);
   nor = normalize(nor);
-  return obj_hit(t, p, nor, mat_from(s.mat), 1, idx);
+  Obj h = obj_hit(t, p, nor, mat_from(s.mat), 1, idx);
+  h.tc = tc; h.t_far = tc + t_offset;
+  return h;
 }
 
 /* struct.cu:111-163 */
@@ -742,6 +768,23 @@ static inline bool hit_qbox(const ONode& b, const float* smin, const float* step
   return t_enter < t_exit && t_enter < tmax && t_exit > tmin;
 }
 
+/* A sphere hit found through quantised boxes: the order-independent clauses of its exact leaf box test, `t_enter < t_exit &&
+ * t_exit > t_min` (bvh_traversal.cu:43), as the product restores them (shade_common.h sphere_leaf_box_admits): the far
+ * intersection bounds the box's exit from below, so with t_far comfortably above t_min the hit is admitted without the test --
+ * also in the one case where the test would fail all the same: a ray with a zero direction component that runs exactly in a face
+ * plane of the box, (plane - o) * inf = NaN, and touches the sphere there.  The reference never tests that sphere; ORC_FLAG_REACH
+ * (the product: hit_needs_literal_walk) finds it out and walks the ray again. */
+static inline bool sphere_leaf_box_admits(const ONode& node, const Ray& ray, const V3& inv, float tmin, const Obj& h, float r)
+{
+  if (h.t_far > 0.0001f + 1e-5f * (fabsf(h.tc) + fabsf(r))) return true;
+  float tx1 = (node.xmin - ray.eye.x) * inv.x, tx2 = (node.xmax - ray.eye.x) * inv.x;
+  float ty1 = (node.ymin - ray.eye.y) * inv.y, ty2 = (node.ymax - ray.eye.y) * inv.y;
+  float tz1 = (node.zmin - ray.eye.z) * inv.z, tz2 = (node.zmax - ray.eye.z) * inv.z;
+  float t_enter = fmaxf(fmaxf(fminf(tx1, tx2), fminf(ty1, ty2)), fminf(tz1, tz2));
+  float t_exit = fminf(fminf(fmaxf(tx1, tx2), fmaxf(ty1, ty2)), fmaxf(tz1, tz2));
+  return t_enter < t_exit && t_exit > tmin;
+}
+
 /* traverse() with the product's near-child-first descent (see ORC_FLAG_ORDERED above): same closest hit as traverse(),
  * fewer node visits. */
 static Obj traverse_ordered(Ctx& cx, const Ray& ray, float initial_t_max, bool early, float stop_below, bool allow_qn = true)
@@ -774,15 +817,7 @@ static Obj traverse_ordered(Ctx& cx, const Ray& ray, float initial_t_max, bool e
       Obj h;
       if (ref.type == 0) {
         h = check_sphere(cx, ray, ref.id); cx.st.sphere_tests++;
-        if (qn && h.isHit) {      /* the two order-independent clauses of the exact leaf box test */
-          float te;
-          hit_aabb_t(node, ray.eye, inv, tmin, INFINITY, &te);
-          float tx1 = (node.xmin - ray.eye.x) * inv.x, tx2 = (node.xmax - ray.eye.x) * inv.x;
-          float ty1 = (node.ymin - ray.eye.y) * inv.y, ty2 = (node.ymax - ray.eye.y) * inv.y;
-          float tz1 = (node.zmin - ray.eye.z) * inv.z, tz2 = (node.zmax - ray.eye.z) * inv.z;
-          float t_exit = fminf(fminf(fmaxf(tx1, tx2), fmaxf(ty1, ty2)), fmaxf(tz1, tz2));
-          if (!(te < t_exit && t_exit > tmin)) h.isHit = false;
-        }
+        if (qn && h.isHit && !sphere_leaf_box_admits(node, ray, inv, tmin, h, sc.spheres[ref.id].r)) h.isHit = false;
       }
       else { h = check_triangle(cx, ray, ref.id); cx.st.tri_tests++; }
       if (h.isHit && h.distance > 1e-6f && (h.distance < tmax || (have && h.distance == tmax && k < best_leaf))) {
@@ -849,10 +884,7 @@ static Obj traverse_wide(Ctx& cx, const Ray& ray, float initial_t_max, bool earl
       Obj h;
       if (ref.type == 0) {
         h = check_sphere(cx, ray, ref.id); cx.st.sphere_tests++;
-        if (h.isHit) {      /* the two order-independent clauses of the exact leaf box test */
-          float te;
-          if (!hit_aabb_t(node, ray.eye, inv, tmin, INFINITY, &te)) h.isHit = false;
-        }
+        if (h.isHit && !sphere_leaf_box_admits(node, ray, inv, tmin, h, sc.spheres[ref.id].r)) h.isHit = false;
       }
       else { h = check_triangle(cx, ray, ref.id); cx.st.tri_tests++; }
       if (h.isHit && h.distance > 1e-6f && (h.distance < tmax || (have && h.distance == tmax && k < best_leaf))) {
@@ -947,6 +979,7 @@ static Obj hit_nearest(Ctx& cx, const Ray& ray, bool count_mat = true, int vet =
     if (!(box_ok && te < b.distance)) { cx.st.qn_retraces++; b = traverse(cx, ray, INFINITY, false, -1.0f); }
   }
   Obj r;
+  if (b.isHit && p.isHit && b.distance == p.distance) cx.br[BR_PLANE_WINS_TIE]++;
   if (b.isHit && p.isHit) r = (b.distance < p.distance) ? b : p;
   else if (b.isHit) r = b;
   else if (p.isHit) r = p;
@@ -971,7 +1004,7 @@ static bool occluded(Ctx& cx, const Ray& ray, float limit, bool bulb = false)
   /* early-exit form: same boolean, fewer node visits; the plane is asked first */
   cx.st.rays++;
   Obj p = check_plane(cx, ray);
-  if (p.isHit && p.distance < limit) return true;
+  if (p.isHit && p.distance < limit) { cx.br[BR_SHADOW_BY_PLANE]++; return true; }
   Obj b = traverse_any(cx, ray, INFINITY, true, limit);
   return b.isHit && b.distance < limit;
 }
@@ -1012,11 +1045,13 @@ static C4 diffuse_light(Ctx& cx, const Obj& obj, Rng* rng)
   V3 normal = obj.normal;
   if (obj.mat.roughness > 0.0f) normal = rough_normal(cx, normal, obj.mat.roughness, rng);
   normal = normalize(normal);
+  if (sc.suns.size() + sc.bulbs.size() > 32) cx.br[BR_DIFFUSE_OVER_32]++;
+  if (sc.suns.size() + sc.bulbs.size() == 0) cx.br[BR_DIFFUSE_NO_LIGHTS]++;
   for (size_t i = 0; i < sc.suns.size(); ++i) {
     V3 ld = mk(sc.suns[i].dir);
     Ray sr = mkray(obj.i_point + obj.normal * 0.001f, ld, 1);
     const bool unlit = (cx.flags & ORC_FLAG_SKIP_UNLIT) && !(dot(normal, normalize(ld)) > 0.0f);
-    if (unlit) { cx.st.rays++; cx.st.shadow_rays++; }
+    if (unlit) { cx.st.rays++; cx.st.shadow_rays++; cx.br[BR_UNLIT_SKIPPED]++; }
     else if (occluded(cx, sr, INFINITY)) continue;
     float lambert = fmaxf(dot(normal, normalize(ld)), 0.0f);
     color = color + color_sun(lambert, obj.mat.color, c3(sc.suns[i].color), sc.d.expose);
@@ -1025,7 +1060,7 @@ static C4 diffuse_light(Ctx& cx, const Obj& obj, Rng* rng)
     V3 bd = mk(sc.bulbs[i].point) - obj.i_point;
     Ray sr = mkray(obj.i_point + obj.normal * 0.001f, bd, 1);
     const bool unlit = (cx.flags & ORC_FLAG_SKIP_UNLIT) && !(dot(normal, normalize(bd)) > 0.0f);
-    if (unlit) { cx.st.rays++; cx.st.shadow_rays++; }
+    if (unlit) { cx.st.rays++; cx.st.shadow_rays++; cx.br[BR_UNLIT_SKIPPED]++; }
     else if (occluded(cx, sr, length(bd), true)) continue;
     float lambert = fmaxf(dot(normal, normalize(bd)), 0.0f);
     color = color + color_bulb(lambert, obj.mat.color, c3(sc.bulbs[i].color), length(bd), sc.d.expose);
@@ -1043,6 +1078,7 @@ static C4 reflection_light(Ctx& cx, const Ray& ray, const Obj& obj, Rng* rng)
   if (obj.mat.roughness > 0.0f) normal = rough_normal(cx, normal, obj.mat.roughness, rng);
   normal = normalize(normal);
   V3 rd = ray.dir - 2.0f * (dot(normal, ray.dir)) * normal;
+  if (ray.bounce - 1 == 0) cx.br[BR_REFL_BOUNCE0]++;
   Ray second = mkray(obj.i_point + obj.normal * 0.001f, rd, ray.bounce - 1);
   Obj so = hit_nearest(cx, second);
   C3 shine, trans;
@@ -1072,22 +1108,30 @@ static C4 refraction_light(Ctx& cx, const Ray& ray, const Obj& obj, Rng* rng)
   int bounce = ray.bounce;
   float dn = dot(normal, dir);
   float k = 1.0f - (ior * ior) * (1.0f - (dn * dn));
+  cx.br[BR_REFR_ENTERED]++;
+  if (obj.kind == 3) cx.br[BR_REFR_ON_PLANE]++;
+  if (obj.kind == 2) cx.br[BR_REFR_ON_TRIANGLE]++;
   if (k < 0) {
+    cx.br[BR_REFR_TIR_FIRST]++;
     refract_dir = dir - 2.0f * (dot(normal, dir)) * normal;
     final_ray = mkray(i_point + normal * 0.001f, refract_dir, --bounce);
   } else {
     refract_dir = ior * dir - (ior * (dot(normal, dir)) + sqrtf(k)) * normal;
     inside_ray = mkray(i_point - normal * 0.0001f, refract_dir, bounce);
     Obj other = hit_nearest(cx, inside_ray);   /* no miss check in the reference (draw.cu:482-487) */
+    if (!other.isHit) cx.br[BR_REFR_INSIDE_MISS]++;
+    if (other.isHit && other.kind == 3) cx.br[BR_REFR_INSIDE_PLANE]++;
     normal = normalize(other.normal);
     ior = other.mat.ior;
     dir = inside_ray.dir;
     i_point = other.i_point;
     float dn2 = dot(normal, dir);
     k = 1.0f - ior * ior * (1.0f - (dn2 * dn2));
+    if (k < 0) cx.br[BR_REFR_SECOND_K_NEG]++;
     refract_dir = ior * dir - (ior * (dot(normal, dir)) + sqrtf(k)) * normal;
     final_ray = mkray(i_point - normal * 0.0001f, refract_dir, --bounce);
   }
+  if (bounce == 0) cx.br[BR_REFR_FINAL_BOUNCE0]++;
   Obj fo = hit_nearest(cx, final_ray);
   C3 shine, trans;
   if (bounce == 0) { shine = c3(0, 0, 0); trans = c3(0, 0, 0); }
@@ -1121,6 +1165,7 @@ static C4 global_illumination(Ctx& cx, const Obj& obj, int gi_bounce, Rng* rng)
   V3 normal = obj.normal;
   V3 i_point = obj.i_point;
   V3 gi_dir = normalize(normal + sphere_point(rng));
+  if (gi_bounce - 1 == 0) cx.br[BR_GI_BOUNCE0]++;
   Ray gi_ray = mkray(i_point + normal * 0.001f, gi_dir, gi_bounce - 1);
   Obj go = hit_nearest(cx, gi_ray);
   C4 color = c4zero();
@@ -1318,12 +1363,13 @@ void orc_get_bounds(void* h, float* mn, float* mx) { Scene* s = (Scene*)h; memcp
 /* Render the tile [x0,x0+tw) x [y0,y0+th) of a width x height frame at spp samples per pixel.
  * out_f: tw*th*4 floats (linear RGBA mean before sRGB), out_u8: tw*th*4 bytes, aov: tw*th primary hit records
  * (any may be NULL).  nthreads > 1 uses OpenMP over rows (results do not depend on it). */
-int orc_render(void* h, int width, int height, int spp, int x0, int y0, int tw, int th,
-               float* out_f, uint8_t* out_u8, OHit* aov, OStats* stats, uint32_t flags, int nthreads)
+static int render_tile(void* h, int width, int height, int spp, int x0, int y0, int tw, int th,
+                       float* out_f, uint8_t* out_u8, OHit* aov, OStats* stats, uint32_t flags, int nthreads, uint64_t* branches)
 {
   Scene* sc = (Scene*)h;
   if (!sc->built) return 1;
   OStats total; memset(&total, 0, sizeof(total));
+  uint64_t br[BR_COUNT] = {};
 #ifdef _OPENMP
   if (nthreads < 1) nthreads = 1;
   #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
@@ -1337,11 +1383,24 @@ int orc_render(void* h, int width, int height, int spp, int x0, int y0, int tw, 
 #ifdef _OPENMP
     #pragma omp critical
 #endif
-    stats_add(&total, cx.st);
+    { stats_add(&total, cx.st); for (int i = 0; i < BR_COUNT; ++i) br[i] += cx.br[i]; }
   }
   (void)nthreads;
   if (stats) *stats = total;
+  if (branches) memcpy(branches, br, sizeof(br));
   return 0;
+}
+int orc_render(void* h, int width, int height, int spp, int x0, int y0, int tw, int th,
+               float* out_f, uint8_t* out_u8, OHit* aov, OStats* stats, uint32_t flags, int nthreads)
+{
+  return render_tile(h, width, height, spp, x0, y0, tw, th, out_f, out_u8, aov, stats, flags, nthreads, NULL);
+}
+/* orc_render, returning also the BR_COUNT branch counters of the shading recursion (summed over the tile) */
+int orc_num_branch_counters(void) { return BR_COUNT; }
+int orc_render_branches(void* h, int width, int height, int spp, int x0, int y0, int tw, int th,
+                        float* out_f, uint8_t* out_u8, OStats* stats, uint32_t flags, int nthreads, uint64_t* branches)
+{
+  return render_tile(h, width, height, spp, x0, y0, tw, th, out_f, out_u8, NULL, stats, flags, nthreads, branches);
 }
 
 /* render_kernel_atomic_aa, draw.cu:49-92, as the product's mirt_render_accumulate defines it: for every pixel of the tile the

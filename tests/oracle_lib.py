@@ -72,6 +72,12 @@ STAT_FIELDS = ["samples", "rays", "shadow_rays", "node_iters", "internal_visits"
                "mat_fetches", "max_stack", "prim_hits", "overflow", "qn_retraces", "traversals"]
 
 
+# orc_render_branches: which paths of the shading recursion a render took (oracle.cpp, enum BR_*, in this order)
+BRANCH_FIELDS = ["refr_entered", "refr_tir_first", "refr_inside_miss", "refr_second_k_neg", "refr_inside_plane", "refr_final_bounce0",
+                 "refr_on_plane", "refr_on_triangle", "gi_bounce0", "refl_bounce0", "unlit_skipped", "shadow_by_plane",
+                 "diffuse_over_32", "diffuse_no_lights", "plane_wins_tie"]
+
+
 class Stats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in STAT_FIELDS]
 
@@ -106,6 +112,9 @@ def lib():
         L.orc_get_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_render.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_uint32, C.c_int]
+        L.orc_render_branches.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_uint32, C.c_int, C.c_void_p]
+        assert L.orc_num_branch_counters() == len(BRANCH_FIELDS)
         L.orc_render_subsample.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Stats), C.c_uint32,
                                            C.c_int, C.POINTER(C.c_float)]
         L.orc_render_accumulate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -206,6 +215,18 @@ class OracleScene:
                               aov.ctypes.data if want_aov else None, C.byref(st), flags, nthreads)
         assert rc == 0
         return dict(f32=f, u8=u, aov=aov, stats=st.as_dict())
+
+    def render_branches(self, width, height, spp, tile=None, flags=0, nthreads=1):
+        """render() that also returns the branch counters of the shading recursion (BRANCH_FIELDS) as `branches`."""
+        x0, y0, tw, th = tile if tile else (0, 0, width, height)
+        f = np.zeros((th, tw, 4), np.float32)
+        u = np.zeros((th, tw, 4), np.uint8)
+        st = Stats()
+        br = np.zeros(len(BRANCH_FIELDS), np.uint64)
+        rc = lib().orc_render_branches(self.h, width, height, spp, x0, y0, tw, th, f.ctypes.data, u.ctypes.data, C.byref(st), flags, nthreads,
+                                       br.ctypes.data)
+        assert rc == 0
+        return dict(f32=f, u8=u, aov=None, stats=st.as_dict(), branches={n: int(v) for n, v in zip(BRANCH_FIELDS, br)})
 
     def render_accumulate(self, accum, width, height, first, count, tile=None, flags=0, nthreads=1):
         """Adds samples [first, first + count) of every pixel of the tile to accum ([th, tw, 4] float32, in place)."""

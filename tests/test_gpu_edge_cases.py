@@ -9,41 +9,9 @@ from cuda_ray_tracer_amd import api
 import oracle_lib as ol
 import pyscene
 import edge_scenes
+from gpu_case import run_case
 
 pytestmark = pytest.mark.gpu
-
-
-def run_case(text, w, h, spp, **options):
-    stl = m.parseText(text)
-    raw = m.initRawConfigFromStl(stl, 0)
-    for k, v in options.items():
-        raw.set_option(k, v)
-    m.build_lbvh_karas(raw)
-    p = api.render_params(w, h, spp, counters=True)
-    img = torch.empty(w * h * 4, dtype=torch.uint8, device="cuda")
-    flt = torch.empty(w * h * 4, dtype=torch.float32, device="cuda")
-    m.render(img, w, h, spp, raw, d_float=flt, params=p)
-    torch.cuda.synchronize()
-    st = raw.stats()
-    tree = raw.tree() if stl.num_prims > 0 else None
-    raw.close()
-    o = ol.OracleScene(pyscene.parse_lines(text.split("\n")), bounds_mode=0)
-    ref = o.render(w, h, spp, flags=ol.product_flags(stl.num_triangles > 0, traversal=options.get("traversal", 1), qnodes=options.get("qnodes", 1),
-                                                      nprims=stl.num_prims, grid_ok=o.grid_ok()), nthreads=8)
-    if tree is not None:
-        on = o.nodes()
-        for f in ("left", "right"):
-            assert np.array_equal(tree[0][f], on[f]), f
-    o.close()
-    gf, gu = flt.cpu().numpy().reshape(h, w, 4), img.cpu().numpy().reshape(h, w, 4)
-    both_nan = np.isnan(gf) & np.isnan(ref["f32"])
-    d = np.where(both_nan, 0.0, np.abs(gf.astype(np.float64) - ref["f32"].astype(np.float64)))
-    assert np.array_equal(np.isnan(gf), np.isnan(ref["f32"]))
-    assert np.nanmax(d) <= 1e-4, float(np.nanmax(d))
-    assert np.abs(gu.astype(np.int32) - ref["u8"].astype(np.int32)).max() <= 1
-    for k in ("samples", "rays", "shadow_rays", "internal_visits", "sphere_tests", "tri_tests", "mat_fetches", "max_stack"):
-        assert st[k] == ref["stats"][k], (k, st[k], ref["stats"][k])
-    return st, gu
 
 
 @pytest.mark.parametrize("name", [n for n in edge_scenes.ALL if n != "deep_stack"])

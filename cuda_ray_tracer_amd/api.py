@@ -50,6 +50,25 @@ class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("kind", C.c_uint32), ("id", C.c_uint32), ("n", Vec3)]
 
 
+class Camera(C.Structure):
+    """MirtCamera: the camera fields of a scene (RawConfig.camera / set_camera)."""
+    _fields_ = [("eye", Vec3), ("forward", Vec3), ("right", Vec3), ("up", Vec3),
+                ("dof_focus", C.c_float), ("dof_lens", C.c_float), ("fisheye", C.c_int32), ("panorama", C.c_int32)]
+
+
+def _camera_with(cam, fields):
+    """A copy of `cam` with the keyword fields replaced (a Vec3 field takes a Vec3 or three numbers)."""
+    out = Camera.from_buffer_copy(bytes(cam))
+    names = dict(Camera._fields_)
+    for k, v in fields.items():
+        if k not in names:
+            raise ValueError(f"{k} is not a camera field; expected one of {sorted(names)}")
+        if names[k] is Vec3 and not isinstance(v, Vec3):
+            v = Vec3(*(float(c) for c in v))
+        setattr(out, k, v)
+    return out
+
+
 class SceneDesc(C.Structure):
     _fields_ = [
         ("width", C.c_int32), ("height", C.c_int32), ("bounces", C.c_int32), ("aa", C.c_int32),
@@ -102,6 +121,7 @@ EXPORTS = [
     "mirt_multi_create", "mirt_multi_destroy", "mirt_multi_num_parts", "mirt_multi_set_option", "mirt_render_frame_multi",
     "mirt_multi_submit", "mirt_multi_wait", "mirt_render_frames_multi", "mirt_multi_get_stats", "mirt_part_pixel_xy",
     "mirt_trace_rays", "mirt_camera_rays",
+    "mirt_scene_get_camera", "mirt_scene_set_camera", "mirt_multi_set_camera", "mirt_scene_update_spheres", "mirt_scene_update_triangles",
 ]
 
 _lib = None
@@ -160,6 +180,12 @@ def lib():
     if hasattr(L, "mirt_trace_rays"):      # (ray queries: a build that predates them -- MIRT_LIB A/B runs -- still loads)
         L.mirt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p]
         L.mirt_camera_rays.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_void_p]
+    if hasattr(L, "mirt_scene_set_camera"):      # (updates in place: likewise)
+        L.mirt_scene_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
+        L.mirt_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
+        L.mirt_multi_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
+        L.mirt_scene_update_spheres.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.mirt_scene_update_triangles.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -273,6 +299,20 @@ class RawConfig:
         _check(lib().mirt_scene_get_option(self._h, name.encode(), C.byref(v)))
         return v.value
 
+    def camera(self):
+        """mirt_scene_get_camera: the scene's camera as a Camera."""
+        cam = Camera()
+        _check(lib().mirt_scene_get_camera(self._h, C.byref(cam)))
+        return cam
+
+    def set_camera(self, cam=None, **fields):
+        """mirt_scene_set_camera: `cam` (default: the current camera) with the keyword fields replaced, e.g.
+        set_camera(eye=(0, 1, 5), fisheye=1).  The fields are taken as given.  Applies to the calls issued afterwards; a frame
+        in flight keeps its camera.  Returns the camera that was set."""
+        new = _camera_with(cam if cam is not None else self.camera(), fields)
+        _check(lib().mirt_scene_set_camera(self._h, C.byref(new)))
+        return new
+
     def tree(self):
         """(nodes, codes, refs, bounds) in the reference's numbering -- for parity tests."""
         import numpy as np
@@ -319,6 +359,13 @@ class MultiGpu:
     def set_option(self, name, value):
         """mirt_multi_set_option: the option on every device's scene."""
         _check(lib().mirt_multi_set_option(self._h, name.encode(), int(value)))
+
+    def set_camera(self, cam, **fields):
+        """mirt_multi_set_camera: `cam` (with the keyword fields replaced) on every device's scene, for the frames submitted
+        afterwards."""
+        new = _camera_with(cam, fields)
+        _check(lib().mirt_multi_set_camera(self._h, C.byref(new)))
+        return new
 
     def render_frame(self, width, height, spp, stripe_rows=4):
         import numpy as np
@@ -491,6 +538,31 @@ def camera_rays(raw, d_rays, img_width, img_height, aa, params=None, stream=None
     _query_layout(d_rays, "d_rays", (torch.float32,), 8, num_pixels(p))
     _query_device(d_rays, "d_rays", raw)
     _check(lib().mirt_camera_rays(raw._h, C.byref(p), C.c_void_p(d_rays.data_ptr()), _stream_ptr(stream)))
+
+
+# ------------------------------------------------------------------------------------------------------
+# Updates in place (mirt_scene_update_spheres / mirt_scene_update_triangles): new geometry from device tensors
+# ------------------------------------------------------------------------------------------------------
+def update_spheres(raw, d_xyzr, first=0, stream=None):
+    """mirt_scene_update_spheres: spheres first .. first+n-1 (file order) take cx, cy, cz, r from d_xyzr (float32 [n, 4],
+    contiguous, on the scene's device).  Asynchronous on `stream` (default: torch's current stream); the scene is not built
+    until the next build_lbvh_karas (n = 0 changes nothing)."""
+    import torch
+    _query_layout(d_xyzr, "d_xyzr", (torch.float32,), 4, None)
+    _query_device(d_xyzr, "d_xyzr", raw)
+    n = d_xyzr.shape[0]
+    _check(lib().mirt_scene_update_spheres(raw._h, C.c_void_p(d_xyzr.data_ptr()) if n else None, int(first), n, _stream_ptr(stream)))
+
+
+def update_triangles(raw, d_verts, first=0, stream=None):
+    """mirt_scene_update_triangles: triangles first .. first+n-1 (file order) take p0, p1, p2 from d_verts (float32 [n, 9],
+    contiguous, on the scene's device); nor, e1 and e2 are computed on the device as the parser computes them
+    (object.cuh:177-191).  Asynchronous on `stream`; the scene is not built until the next build_lbvh_karas."""
+    import torch
+    _query_layout(d_verts, "d_verts", (torch.float32,), 9, None)
+    _query_device(d_verts, "d_verts", raw)
+    n = d_verts.shape[0]
+    _check(lib().mirt_scene_update_triangles(raw._h, C.c_void_p(d_verts.data_ptr()) if n else None, int(first), n, _stream_ptr(stream)))
 
 
 def pack_rays(origins, dirs, tmax=float("inf")):

@@ -296,6 +296,7 @@ int mirt_build_lbvh(MirtScene* sc, void* stream, float* build_ms)
   if (!sc) { set_error("mirt_build_lbvh: null scene"); return MIRT_ERR_ARG; }
   MIRT_HIP(hipSetDevice(sc->device));
   int rc = build_lbvh(sc, (hipStream_t)stream);
+  if (rc == MIRT_OK) sc->updated = false;
   if (rc == MIRT_OK && build_ms) *build_ms = sc->build_ms;
   return rc;
 }
@@ -344,8 +345,45 @@ int mirt_trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d
 int mirt_camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, void* stream)
 {
   if (!sc || !p) { set_error("mirt_camera_rays: null argument"); return MIRT_ERR_ARG; }
+  // (the rays themselves need no tree -- a scene that was never built gives them, as before -- but between an update and its
+  // build the scene answers nothing)
+  if (sc->updated) { set_error("mirt_camera_rays: the scene was updated: call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
   MIRT_HIP(hipSetDevice(sc->device));
   return camera_rays(sc, p, d_rays, (hipStream_t)stream);
+}
+
+int mirt_scene_get_camera(const MirtScene* sc, MirtCamera* out)
+{
+  if (!sc || !out) { set_error("mirt_scene_get_camera: null argument"); return MIRT_ERR_ARG; }
+  const MirtSceneDesc& d = sc->d;
+  out->eye = d.eye; out->forward = d.forward; out->right = d.right; out->up = d.up;
+  out->dof_focus = d.dof_focus; out->dof_lens = d.dof_lens; out->fisheye = d.fisheye; out->panorama = d.panorama;
+  return MIRT_OK;
+}
+
+// Host state only: render.hip and query.hip copy these fields into the RenderArgs of every call they issue, so a frame in
+// flight -- each of its slabs -- keeps the camera it was issued with.
+int mirt_scene_set_camera(MirtScene* sc, const MirtCamera* cam)
+{
+  if (!sc || !cam) { set_error("mirt_scene_set_camera: null argument"); return MIRT_ERR_ARG; }
+  MirtSceneDesc& d = sc->d;
+  d.eye = cam->eye; d.forward = cam->forward; d.right = cam->right; d.up = cam->up;
+  d.dof_focus = cam->dof_focus; d.dof_lens = cam->dof_lens; d.fisheye = cam->fisheye; d.panorama = cam->panorama;
+  return MIRT_OK;
+}
+
+int mirt_scene_update_spheres(MirtScene* sc, const void* d_spheres, int first, int count, void* stream)
+{
+  if (!sc) { set_error("mirt_scene_update_spheres: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return update_spheres(sc, d_spheres, first, count, (hipStream_t)stream);
+}
+
+int mirt_scene_update_triangles(MirtScene* sc, const void* d_verts, int first, int count, void* stream)
+{
+  if (!sc) { set_error("mirt_scene_update_triangles: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return update_triangles(sc, d_verts, first, count, (hipStream_t)stream);
 }
 
 int mirt_get_stats(MirtScene* sc, MirtStats* out)

@@ -235,6 +235,13 @@ int mirt_multi_set_option(MirtMulti* mm, const char* name, int value)
   return MIRT_OK;
 }
 
+int mirt_multi_set_camera(MirtMulti* mm, const MirtCamera* cam)
+{
+  if (!mm || !cam) { mirt::set_error("mirt_multi_set_camera: null argument"); return MIRT_ERR_ARG; }
+  for (MirtScene* sc : mm->scene) { int rc = mirt_scene_set_camera(sc, cam); if (rc != MIRT_OK) return rc; }
+  return MIRT_OK;
+}
+
 int mirt_multi_get_stats(MirtMulti* mm, int part, MirtStats* out)
 {
   if (!mm || part < 0 || part >= mm->n || !out) { mirt::set_error("mirt_multi_get_stats: bad argument"); return MIRT_ERR_ARG; }

@@ -275,6 +275,7 @@ struct MirtScene {
   bool any_trans = false;                  // some material has transparency != 0
   bool any_rough = false;
   int query_blocks = 0;                    // grid size of the ray-query kernel on this scene's device (query.hip; filled on first use)
+  bool updated = false;                    // geometry updated in place since the last build (update.hip): mirt_camera_rays waits for the build like every other call
 };
 
 namespace mirt {
@@ -299,6 +300,9 @@ void rng_cache_free(RngCache* rc);
 // query.hip
 int trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits, uint32_t flags, hipStream_t stream);
 int camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, hipStream_t stream);
+// update.hip
+int update_spheres(MirtScene* sc, const void* d_spheres, int first, int count, hipStream_t stream);
+int update_triangles(MirtScene* sc, const void* d_verts, int first, int count, hipStream_t stream);
 // wavefront.hip
 int wavefront_trace(MirtScene* sc, RenderCtx& cx, RenderArgs& a, bool count, hipStream_t stream, float* trace_ms);
 }

@@ -224,6 +224,41 @@ int mirt_trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d
  * cache: with spp > 1 any cached sample table serves. */
 int mirt_camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, void* stream);
 
+/* ---- updates of a built scene in place ---------------------------------------------------------- */
+/* Move the camera, the spheres and the triangles of a scene without creating it again: the render workspaces, the
+ * random-number tables and the measured hand-out order of the samples ("sched") stay.  Not in the reference (its RawConfig is
+ * filled once, config_utils.cu:18-199).  Callers detect the feature by these symbols (MIRT_VERSION stays 3).
+ *
+ * MirtCamera: the camera fields of MirtSceneDesc, taken as given (the forward / up keyword rule of parse.cpp:60-72 is the
+ * parser's business and is not applied); 64 B.  expose, bounces, gi, lights and planes are not part of it and stay fixed. */
+typedef struct MirtCamera { MirtVec3 eye, forward, right, up; float dof_focus, dof_lens; int32_t fisheye, panorama; } MirtCamera;
+int mirt_scene_get_camera(const MirtScene* sc, MirtCamera* out);
+/* The new camera applies to every mirt_render, mirt_render_accumulate, mirt_camera_rays (and mirt_multi_submit) issued after
+ * the call.  A frame already issued keeps the camera it was issued with, in every slab of a call of several slabs: each slab's
+ * kernel arguments were copied when the call was issued.  Host state only: no device work, no synchronisation, the scene stays
+ * built.  MIRT_ERR_ARG: null scene or camera. */
+int mirt_scene_set_camera(MirtScene* sc, const MirtCamera* cam);
+/* New geometry from device memory (hipMalloc, or a torch data_ptr(), on the scene's device), values taken as they are, as
+ * mirt_scene_create takes them.  One kernel, one lane per primitive, asynchronous on `stream`.
+ *   d_spheres: float [count][4] = cx, cy, cz, r of spheres first .. first+count-1 (file order); 16-byte aligned
+ *   d_verts:   float [count][9] = p0, p1, p2 of triangles first .. first+count-1 (file order); 4-byte aligned.  nor, e1 and e2
+ *              are computed as Triangle(Vertex, Vertex, Vertex, RGB) computes them (object.cuh:177-191): normalize(cross(p1 - p0,
+ *              p2 - p0)), the two crosses with nor, 1 / dot, three multiplies -- one rounding per operation, the bits the parser
+ *              produces on the host for the same vertices (a zero-area triangle gives NaN in both places)
+ * Materials, primitive counts, the order of the primitives, planes and lights do not change.
+ * State: an update marks the scene NOT BUILT: until the next mirt_build_lbvh (issued on the same stream, or after the caller
+ * has ordered it behind the update), mirt_render*, mirt_trace_rays, mirt_camera_rays and mirt_get_tree return MIRT_ERR_STATE.
+ * Several updates may precede one build.  The build is the full one: the result is exactly the scene that mirt_scene_create +
+ * mirt_build_lbvh give for the same values (the reference builds its tree from scratch; a refitted tree would be another tree).
+ * count 0: MIRT_OK, nothing launched, the scene stays built.
+ * Frames in flight: before it enqueues anything the call waits on the host for the last frame of every render context -- the
+ * build that follows rewrites the records those frames read -- so a frame issued before the update finishes with the old
+ * geometry.  Ray queries in flight on other streams use no render context: ordering them before an update is the caller's duty.
+ * MIRT_ERR_ARG: null scene, negative first or count, a range beyond num_spheres / num_triangles, a null or misaligned pointer
+ * with count > 0. */
+int mirt_scene_update_spheres(MirtScene* sc, const void* d_spheres, int first, int count, void* stream);
+int mirt_scene_update_triangles(MirtScene* sc, const void* d_verts, int first, int count, void* stream);
+
 /* ---- several GPUs in one process --------------------------------------------------------------- */
 /* Not in the reference (single GPU, main.cu:25-94).  The scene is uploaded to every listed device and every device builds
  * the identical LBVH; a frame is cut into interleaved stripes of `stripe_rows` rows, device r renders part r (a
@@ -247,6 +282,7 @@ int mirt_multi_create(const MirtSceneDesc* desc, int ngpu, const int* devices, M
 void mirt_multi_destroy(MirtMulti* mm);
 int mirt_multi_num_parts(const MirtMulti* mm);
 int mirt_multi_set_option(MirtMulti* mm, const char* name, int value);      /* mirt_scene_set_option on every device's scene */
+int mirt_multi_set_camera(MirtMulti* mm, const MirtCamera* cam);            /* mirt_scene_set_camera on every device's scene: frames submitted afterwards */
 /* Frames in flight: mirt_multi_submit issues one width x height frame at spp samples per pixel on every device and returns at
  * once with a ticket; mirt_multi_wait blocks until that frame is gathered (and copied to host_rgba, nullable, which must stay
  * valid until then).  Up to MIRT_MULTI_MAX_IN_FLIGHT frames may be in flight: consecutive frames overlap on every device (the

@@ -5,9 +5,11 @@ Host side: api.py (ctypes over include/mirt.h).  Device side: csrc/*.hip, built 
 from .api import (MirtError, StlConfig, RawConfig, parseInput, parseText, syntheticScene, initRawConfigFromStl,
                   copyConfigDataToDevice, freeRawConfigDeviceMemory, build_lbvh_karas, render, render_params,
                   num_pixels, scatter_part, write_png, lib, render_accumulate, finalize, Ray, Hit, trace_rays,
-                  camera_rays, pack_rays, unpack_hits, Camera, update_spheres, update_triangles)
+                  camera_rays, pack_rays, unpack_hits, Camera, update_spheres, update_triangles, render_accumulate_pixels,
+                  select_pixels, finalize_counts, render_adaptive)
 
 __all__ = ["MirtError", "StlConfig", "RawConfig", "parseInput", "parseText", "syntheticScene", "initRawConfigFromStl",
            "copyConfigDataToDevice", "freeRawConfigDeviceMemory", "build_lbvh_karas", "render", "render_params",
            "num_pixels", "scatter_part", "write_png", "lib", "render_accumulate", "finalize", "Ray", "Hit", "trace_rays",
-           "camera_rays", "pack_rays", "unpack_hits", "Camera", "update_spheres", "update_triangles"]
+           "camera_rays", "pack_rays", "unpack_hits", "Camera", "update_spheres", "update_triangles", "render_accumulate_pixels",
+           "select_pixels", "finalize_counts", "render_adaptive"]

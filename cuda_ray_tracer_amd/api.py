@@ -122,6 +122,7 @@ EXPORTS = [
     "mirt_multi_submit", "mirt_multi_wait", "mirt_render_frames_multi", "mirt_multi_get_stats", "mirt_part_pixel_xy",
     "mirt_trace_rays", "mirt_camera_rays",
     "mirt_scene_get_camera", "mirt_scene_set_camera", "mirt_multi_set_camera", "mirt_scene_update_spheres", "mirt_scene_update_triangles",
+    "mirt_render_accumulate_pixels", "mirt_select_pixels", "mirt_finalize_counts",
 ]
 
 _lib = None
@@ -186,6 +187,12 @@ def lib():
         L.mirt_multi_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
         L.mirt_scene_update_spheres.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.mirt_scene_update_triangles.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(L, "mirt_render_accumulate_pixels"):      # (adaptive sampling: likewise)
+        L.mirt_render_accumulate_pixels.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_int, C.c_int, C.c_void_p]
+        L.mirt_select_pixels.argtypes = [C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
+        L.mirt_finalize_counts.argtypes = [C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -563,6 +570,142 @@ def update_triangles(raw, d_verts, first=0, stream=None):
     _query_device(d_verts, "d_verts", raw)
     n = d_verts.shape[0]
     _check(lib().mirt_scene_update_triangles(raw._h, C.c_void_p(d_verts.data_ptr()) if n else None, int(first), n, _stream_ptr(stream)))
+
+
+# ------------------------------------------------------------------------------------------------------
+# Adaptive sampling (mirt_render_accumulate_pixels / mirt_select_pixels / mirt_finalize_counts): accum and accum_sq are float32
+# tensors of num_pixels * 4 elements, counts 4-byte integer tensors of num_pixels, pixel lists int32 / uint32 [n]
+# ------------------------------------------------------------------------------------------------------
+def _int_dtypes():
+    import torch
+    return tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
+
+
+def _flat_layout(x, name, dtypes, numel):
+    """ValueError unless x is a contiguous tensor of one of the dtypes with `numel` elements (None: one-dimensional, any length)."""
+    import torch
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor")
+    if x.dtype not in dtypes:
+        raise ValueError(f"{name} has dtype {x.dtype}; expected one of {[str(d) for d in dtypes]}")
+    if numel is None:
+        if x.dim() != 1:
+            raise ValueError(f"{name} has shape {list(x.shape)}; expected [n]")
+    elif x.numel() != numel:
+        raise ValueError(f"{name} has shape {list(x.shape)}; expected {numel} elements")
+    if not x.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def _same_device(x, name, device):
+    import torch
+    index = x.device.index if x.device.index is not None else (torch.cuda.current_device() if x.device.type == "cuda" else None)
+    if x.device.type != "cuda" or index != device:
+        raise ValueError(f"{name} is on {x.device}; expected cuda:{device}")
+
+
+def render_accumulate_pixels(raw, d_accum, img_width, img_height, sample_first, sample_count, pixels=None, d_accum_sq=None, d_counts=None,
+                             params=None, stream=None):
+    """mirt_render_accumulate_pixels: render_accumulate for the pixels of `pixels` (int32 / uint32 [n], distinct local pixel
+    indices, any order; None: every pixel), adding as well the squared samples to d_accum_sq and sample_count to d_counts (both
+    optional).  Unlisted pixels are neither traced nor written.  Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    p = params if params is not None else render_params(img_width, img_height, max(sample_first + sample_count, 2))
+    n = num_pixels(p)
+    _flat_layout(d_accum, "d_accum", (torch.float32,), 4 * n)
+    _query_device(d_accum, "d_accum", raw)
+    if d_accum_sq is not None:
+        _flat_layout(d_accum_sq, "d_accum_sq", (torch.float32,), 4 * n)
+        _query_device(d_accum_sq, "d_accum_sq", raw)
+    if d_counts is not None:
+        _flat_layout(d_counts, "d_counts", _int_dtypes(), n)
+        _query_device(d_counts, "d_counts", raw)
+    listed = 0
+    if pixels is not None:
+        _flat_layout(pixels, "pixels", _int_dtypes(), None)
+        _query_device(pixels, "pixels", raw)
+        listed = pixels.shape[0]
+        if listed == 0:      # (an empty tensor has no address to pass: an empty list renders nothing)
+            return
+    _check(lib().mirt_render_accumulate_pixels(raw._h, C.byref(p), C.c_void_p(pixels.data_ptr()) if pixels is not None else None, listed,
+                                               C.c_void_p(d_accum.data_ptr()), C.c_void_p(d_accum_sq.data_ptr()) if d_accum_sq is not None else None,
+                                               C.c_void_p(d_counts.data_ptr()) if d_counts is not None else None, int(sample_first), int(sample_count),
+                                               _stream_ptr(stream)))
+
+
+def select_pixels(d_accum, d_accum_sq, d_counts, img_width, img_height, min_samples, max_samples, max_variance, d_pixels_out, d_num_out,
+                  params=None, stream=None):
+    """mirt_select_pixels: the pixels with fewer than max_samples samples that have fewer than min_samples or whose estimated
+    variance of the mean exceeds max_variance, in increasing order, into d_pixels_out (int32 / uint32 [num_pixels]); their number
+    into d_num_out (one 4-byte integer).  All tensors on the device of d_accum.  Asynchronous on `stream`."""
+    import torch
+    p = params if params is not None else render_params(img_width, img_height, 2)
+    n = num_pixels(p)
+    _flat_layout(d_accum, "d_accum", (torch.float32,), 4 * n)
+    _flat_layout(d_accum_sq, "d_accum_sq", (torch.float32,), 4 * n)
+    _flat_layout(d_counts, "d_counts", _int_dtypes(), n)
+    _flat_layout(d_pixels_out, "d_pixels_out", _int_dtypes(), n)
+    _flat_layout(d_num_out, "d_num_out", _int_dtypes(), 1)
+    if d_accum.device.type != "cuda":
+        raise ValueError(f"d_accum is on {d_accum.device}; expected a cuda device")
+    device = d_accum.device.index if d_accum.device.index is not None else torch.cuda.current_device()
+    for x, name in ((d_accum_sq, "d_accum_sq"), (d_counts, "d_counts"), (d_pixels_out, "d_pixels_out"), (d_num_out, "d_num_out")):
+        _same_device(x, name, device)
+    with torch.cuda.device(device):
+        _check(lib().mirt_select_pixels(C.byref(p), C.c_void_p(d_accum.data_ptr()), C.c_void_p(d_accum_sq.data_ptr()), C.c_void_p(d_counts.data_ptr()),
+                                        int(min_samples), int(max_samples), float(max_variance), C.c_void_p(d_pixels_out.data_ptr()),
+                                        C.c_void_p(d_num_out.data_ptr()), _stream_ptr(stream)))
+
+
+def finalize_counts(d_image, d_accum, d_counts, img_width, img_height, params=None, stream=None):
+    """mirt_finalize_counts: finalize with d_counts[pixel] as each pixel's number of samples (0: a zero pixel)."""
+    import torch
+    p = params if params is not None else render_params(img_width, img_height, 2)
+    n = num_pixels(p)
+    _flat_layout(d_image, "d_image", (torch.uint8,), 4 * n)
+    _flat_layout(d_accum, "d_accum", (torch.float32,), 4 * n)
+    _flat_layout(d_counts, "d_counts", _int_dtypes(), n)
+    if d_accum.device.type != "cuda":
+        raise ValueError(f"d_accum is on {d_accum.device}; expected a cuda device")
+    device = d_accum.device.index if d_accum.device.index is not None else torch.cuda.current_device()
+    _same_device(d_image, "d_image", device)
+    _same_device(d_counts, "d_counts", device)
+    with torch.cuda.device(device):
+        _check(lib().mirt_finalize_counts(C.byref(p), C.c_void_p(d_accum.data_ptr()), C.c_void_p(d_counts.data_ptr()), C.c_void_p(d_image.data_ptr()),
+                                          _stream_ptr(stream)))
+
+
+def render_adaptive(raw, width, height, min_spp, max_spp, step, max_variance, params=None, stream=None):
+    """Adaptive sampling of one frame (or of the part `params` selects): samples [0, min_spp) for every pixel, then rounds of
+    select_pixels -> render_accumulate_pixels adding samples [min_spp + r step, min_spp + (r + 1) step) to the pixels still
+    noisier than max_variance, while the round stays within max_spp; finalize_counts at the end.  Every round uses one sample
+    range for all its pixels, so no pixel sees a sample index twice.  Reads 4 bytes back per round (the number selected).
+    Returns (rgba8 uint8 [num_pixels * 4], counts int32 [num_pixels], rounds)."""
+    import torch
+    if min_spp < 2 or max_spp < min_spp or step < 1:
+        raise ValueError("render_adaptive needs 2 <= min_spp <= max_spp and step >= 1")
+    p = params if params is not None else render_params(width, height, max(max_spp, 2))
+    n = num_pixels(p)
+    dev = torch.device("cuda", raw.device)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        accum = torch.zeros(4 * n, dtype=torch.float32, device=dev)
+        accum_sq = torch.zeros(4 * n, dtype=torch.float32, device=dev)
+        counts = torch.zeros(n, dtype=torch.int32, device=dev)
+        pixels = torch.empty(n, dtype=torch.int32, device=dev)
+        num = torch.zeros(1, dtype=torch.int32, device=dev)
+        image = torch.empty(4 * n, dtype=torch.uint8, device=dev)
+        render_accumulate_pixels(raw, accum, width, height, 0, min_spp, None, accum_sq, counts, params=p, stream=s)
+        rounds = 0
+        while min_spp + (rounds + 1) * step <= max_spp:
+            select_pixels(accum, accum_sq, counts, width, height, min_spp, max_spp, max_variance, pixels, num, params=p, stream=s)
+            k = int(num.item())
+            if k == 0:
+                break
+            render_accumulate_pixels(raw, accum, width, height, min_spp + rounds * step, step, pixels[:k], accum_sq, counts, params=p, stream=s)
+            rounds += 1
+        finalize_counts(image, accum, counts, width, height, params=p, stream=s)
+    return image, counts, rounds
 
 
 def pack_rays(origins, dirs, tmax=float("inf")):

@@ -273,6 +273,7 @@ void mirt_scene_destroy(MirtScene* sc)
     mirt::RenderCtx& c = sc->ctx[i];
     hipFree(c.samples); hipFree(c.stack_spill); hipFree(c.pending); hipFree(c.counters); hipFree(c.args_dev);
     hipFree(c.chunk_cost); for (uint32_t* o : c.order_out) hipFree(o);
+    hipFree(c.sp_list); hipFree(c.sp_table); hipFree(c.sp_blocks);
     if (c.ev0) hipEventDestroy(c.ev0);
     if (c.ev1) hipEventDestroy(c.ev1);
     if (c.ev2) hipEventDestroy(c.ev2);
@@ -327,6 +328,30 @@ int mirt_finalize(const MirtRenderParams* p, const void* d_accum_f32, int total_
 {
   if (!p) { set_error("mirt_finalize: null argument"); return MIRT_ERR_ARG; }
   return finalize(p, d_accum_f32, total_samples, d_rgba8, (hipStream_t)stream);
+}
+
+int mirt_render_accumulate_pixels(MirtScene* sc, const MirtRenderParams* p, const uint32_t* d_pixels, int64_t num_listed, void* d_accum_f32,
+                                  void* d_accum_sq_f32, uint32_t* d_counts, int sample_first, int sample_count, void* stream)
+{
+  if (!sc || !p) { set_error("mirt_render_accumulate_pixels: null argument"); return MIRT_ERR_ARG; }
+  if (!d_pixels && num_listed > 0) { set_error("mirt_render_accumulate_pixels: null pixel list (every pixel of the part: d_pixels = NULL with num_listed = 0)"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  mirt::AdaptiveArgs ax;
+  ax.list = d_pixels; ax.num_listed = num_listed; ax.accum_sq = (float4*)d_accum_sq_f32; ax.counts = d_counts;
+  return render_accumulate_pixels(sc, p, ax, d_accum_f32, sample_first, sample_count, (hipStream_t)stream);
+}
+
+int mirt_select_pixels(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, int min_samples,
+                       int max_samples, float max_variance, uint32_t* d_pixels_out, uint32_t* d_num_out, void* stream)
+{
+  if (!p) { set_error("mirt_select_pixels: null argument"); return MIRT_ERR_ARG; }
+  return select_pixels(p, d_accum_f32, d_accum_sq_f32, d_counts, min_samples, max_samples, max_variance, d_pixels_out, d_num_out, (hipStream_t)stream);
+}
+
+int mirt_finalize_counts(const MirtRenderParams* p, const void* d_accum_f32, const uint32_t* d_counts, void* d_rgba8, void* stream)
+{
+  if (!p) { set_error("mirt_finalize_counts: null argument"); return MIRT_ERR_ARG; }
+  return finalize_counts(p, d_accum_f32, d_counts, d_rgba8, (hipStream_t)stream);
 }
 
 int mirt_scatter_part(const MirtRenderParams* p, const void* d_part_rgba8, void* d_frame_rgba8, void* stream)

@@ -259,6 +259,14 @@ MIRT_DEV float rgb_to_srgb(float l)
   sol = fminf(1.0f, fmaxf(0.0f, sol));
   return sol;
 }
+// draw.cu:9-11
+MIRT_DEV unsigned char to_uchar_round(float f) { return (unsigned char)(fminf(fmaxf(f, 0.0f), 1.0f) * 255.0f + 0.5f); }
+// the sample mean of finalize_kernel and of render (draw.cu:22-25, 191-200): one reciprocal, four multiplies
+MIRT_DEV float4 mean_of(const float4 sum, int spp)
+{
+  const float inv = 1.0f / (float)spp;
+  return make_float4(sum.x * inv, sum.y * inv, sum.z * inv, sum.w * inv);
+}
 
 // ---- XORWOW (curand_kernel.h semantics) -----------------------------------------
 struct Xorwow {

@@ -1,7 +1,7 @@
 // raytracer -- the reference's command line (main.cu:25-94) over libmirt's C ABI:
 //
 //     raytracer scene.txt [--width W] [--height H] [--spp N] [--out file.png] [--device D] [--gpus N] [--frames K]
-//                         [--traversal 0|1|2] [--bounds-as-shipped]
+//                         [--traversal 0|1|2] [--bounds-as-shipped] [--adaptive V [--min-spp N] [--step N]]
 //
 // Same contract: one positional scene file, the PNG is named by the scene's `png W H name` line and written to the
 // current directory, the same lines go to stdout -- the phase timings (main.cu:39,61,71,80,93, with the reference's labels:
@@ -11,6 +11,9 @@
 // EXIT_FAILURE).  The optional flags override resolution / samples per pixel of the scene file (BASELINE.json's configs do).
 // --gpus N renders the frame on N GPUs of this node (image stripes, replicated BVH, RCCL framebuffer gather: mirt_multi_*);
 // --frames K renders K frames back to back (consecutive frames overlap on every device) and reports ms per frame.
+// --adaptive V: adaptive sampling (mirt_render_accumulate_pixels / mirt_select_pixels / mirt_finalize_counts): --min-spp samples
+// (default 4) for every pixel, then rounds of --step more (default: --min-spp) for the pixels whose estimated variance of the mean
+// exceeds V, up to --spp samples per pixel; one line reports the samples used.  One GPU only.
 // --bounds-as-shipped builds the tree of the shipped reference (scene bounds never stored, parse.cpp:28: every Morton code 0).
 #include <hip/hip_runtime.h>
 
@@ -61,6 +64,9 @@ int main(int argc, char* argv[])
 {
   if (argc < 2) { std::cout << "Error opening file..." << std::endl; return 1; }
   int ow = 0, oh = 0, ospp = -1, device = 0, gpus = 1, traversal = -1, frames = 1, shipped = 0;
+  int min_spp = 4, step = 0;
+  bool adaptive = false;
+  float max_variance = 0.0f;
   std::string out_override;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
@@ -74,8 +80,15 @@ int main(int argc, char* argv[])
     else if (a == "--traversal") { need(1); traversal = atoi(argv[++i]); }
     else if (a == "--frames") { need(1); frames = atoi(argv[++i]); if (frames < 1) frames = 1; }
     else if (a == "--bounds-as-shipped") shipped = 1;
+    else if (a == "--adaptive") { need(1); adaptive = true; max_variance = (float)atof(argv[++i]); }
+    else if (a == "--min-spp") { need(1); min_spp = atoi(argv[++i]); }
+    else if (a == "--step") { need(1); step = atoi(argv[++i]); }
     else { std::cerr << "unknown option " << a << std::endl; return 2; }
   }
+
+  if (adaptive && gpus > 1) { std::cerr << "--adaptive renders on one GPU: it cannot be combined with --gpus " << gpus << std::endl; return 2; }
+  if (step <= 0) step = min_spp;
+  if (adaptive && (min_spp < 2 || (ospp >= 0 && ospp < min_spp))) { std::cerr << "--adaptive needs 2 <= --min-spp <= --spp" << std::endl; return 2; }
 
   MirtHostScene* hs = nullptr;
   die_on(mirt_parse_scene_file(argv[1], &hs), "parseInput");
@@ -148,8 +161,36 @@ int main(int argc, char* argv[])
   std::cout << "Malloc and transfer to device time: " << elapsed.count() << " seconds" << std::endl;
 
   start = std::chrono::high_resolution_clock::now();
-  print_debug_render(width, height, spp);
-  for (int f = 0; f < frames; ++f) die_on(mirt_render(sc, &p, d_image, nullptr, nullptr), "render");
+  if (!adaptive) print_debug_render(width, height, spp);
+  if (adaptive) {
+    // the loop of DESIGN.md section 6e: every pixel gets samples [0, min_spp), then the pixels mirt_select_pixels still finds noisy
+    // get the samples of one more round, the same range for all of them
+    if (spp < min_spp) { std::cerr << "--adaptive needs 2 <= --min-spp <= --spp" << std::endl; return 2; }
+    const size_t n = (size_t)width * height;
+    void *accum = nullptr, *accum_sq = nullptr;
+    uint32_t *counts = nullptr, *pixels = nullptr, *num = nullptr;
+    HIP_CHECK(hipMalloc(&accum, 16 * n)); HIP_CHECK(hipMalloc(&accum_sq, 16 * n));
+    HIP_CHECK(hipMalloc(&counts, 4 * n)); HIP_CHECK(hipMalloc(&pixels, 4 * n)); HIP_CHECK(hipMalloc(&num, 4));
+    HIP_CHECK(hipMemset(accum, 0, 16 * n)); HIP_CHECK(hipMemset(accum_sq, 0, 16 * n)); HIP_CHECK(hipMemset(counts, 0, 4 * n));
+    p.spp = spp > 2 ? spp : 2;
+    die_on(mirt_render_accumulate_pixels(sc, &p, nullptr, 0, accum, accum_sq, counts, 0, min_spp, nullptr), "render");
+    for (int r = 0; min_spp + (r + 1) * step <= spp; ++r) {
+      die_on(mirt_select_pixels(&p, accum, accum_sq, counts, min_spp, spp, max_variance, pixels, num, nullptr), "render");
+      uint32_t k = 0;
+      HIP_CHECK(hipMemcpy(&k, num, 4, hipMemcpyDeviceToHost));
+      if (k == 0) break;
+      die_on(mirt_render_accumulate_pixels(sc, &p, pixels, k, accum, accum_sq, counts, min_spp + r * step, step, nullptr), "render");
+    }
+    die_on(mirt_finalize_counts(&p, accum, counts, d_image, nullptr), "render");
+    std::vector<uint32_t> host_counts(n);
+    HIP_CHECK(hipMemcpy(host_counts.data(), counts, 4 * n, hipMemcpyDeviceToHost));
+    unsigned long long used = 0;
+    for (uint32_t c : host_counts) used += c;
+    printf("Adaptive sampling: %llu samples used (min-spp x pixels: %llu, spp x pixels: %llu)\n", used, (unsigned long long)min_spp * n, (unsigned long long)spp * n);
+    HIP_CHECK(hipFree(accum)); HIP_CHECK(hipFree(accum_sq)); HIP_CHECK(hipFree(counts)); HIP_CHECK(hipFree(pixels)); HIP_CHECK(hipFree(num));
+  } else {
+    for (int f = 0; f < frames; ++f) die_on(mirt_render(sc, &p, d_image, nullptr, nullptr), "render");
+  }
   HIP_CHECK(hipDeviceSynchronize());
   {
     MirtStats st;      // (a capacity overflow during the render is an error, not a warning on stdout as bvh_traversal.cu:154-164)

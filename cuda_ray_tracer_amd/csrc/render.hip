@@ -378,8 +378,7 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
 }
 #undef MIRT_HELD
 
-// draw.cu:9-11
-MIRT_DEV unsigned char to_uchar_round(float f) { return (unsigned char)(fminf(fmaxf(f, 0.0f), 1.0f) * 255.0f + 0.5f); }
+// (to_uchar_round, draw.cu:9-11, and mean_of: device_common.h)
 // draw.cu:129-132: plain float -> unsigned char conversion
 MIRT_DEV unsigned char to_uchar_trunc(float f)
 {
@@ -388,11 +387,6 @@ MIRT_DEV unsigned char to_uchar_trunc(float f)
   return (unsigned char)f;
 }
 
-MIRT_DEV float4 mean_of(const float4 sum, int spp)
-{
-  const float inv = 1.0f / (float)spp;
-  return make_float4(sum.x * inv, sum.y * inv, sum.z * inv, sum.w * inv);
-}
 // pixel_color_accum / uchar conversion, draw.cu:191-205 (spp > 1) and draw.cu:120-135 (spp <= 1)
 MIRT_DEV void write_pixel(const ResolveArgs& a, long long lq, const float4 sum)
 {
@@ -640,10 +634,15 @@ static int grid_blocks(int device)
 // costs one drain of the persistent grid (~1-2 ms per 64 M samples).
 //   d_accum == null: pixels are written (mean, sRGB, quantise);  sample_first must be 0 and sample_count max(spp, 1)
 //   d_accum != null: the sum of each pixel's samples [sample_first, sample_first + sample_count) is ADDED to d_accum
+//   ax != null (with d_accum): mirt_render_accumulate_pixels -- the second moment and the counts are added as well, and with
+//                    ax->list only the listed pixels are rendered: every launch hands out, through RenderArgs::sample_order, the
+//                    samples of the listed pixels of its slab (adaptive.hip) instead of the scene's measured order, to the same
+//                    trace kernels.  The workspace stays indexed by the slab's dense sample number.
 static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, void* d_rgba_f32, void* d_accum, int sample_first,
-                       int sample_count, hipStream_t stream)
+                       int sample_count, hipStream_t stream, const AdaptiveArgs* ax = nullptr)
 {
-  const char* who = d_accum ? "mirt_render_accumulate" : "mirt_render";
+  const char* who = ax ? "mirt_render_accumulate_pixels" : (d_accum ? "mirt_render_accumulate" : "mirt_render");
+  const bool sparse = ax && ax->list;
   if (!sc->built) { set_error(std::string(who) + ": call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
   const int64_t npix = local_pixels(p);
   if (npix < 0 || p->spp < 0 || (!d_rgba8 && !d_accum)) { set_error(std::string(who) + ": bad parameters"); return MIRT_ERR_ARG; }
@@ -653,6 +652,7 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
   if ((int64_t)p->width * p->height > 0x7fffffffll - 1234) { set_error(std::string(who) + ": frame too large for the 32-bit pixel seed"); return MIRT_ERR_ARG; }
   if (npix == 0) return MIRT_OK;
   if (npix >= 0x7fffffffll || (long long)p->stripe_rows * p->width >= 0x7fffffffll) { set_error(std::string(who) + ": part too large"); return MIRT_ERR_ARG; }
+  if (sparse && sc->opt.wavefront != 0) { set_error(std::string(who) + ": a pixel list is not supported with wavefront = 1 (the trace / shade kernel pair does not hand samples out through a table)"); return MIRT_ERR_ARG; }
   const bool per_pixel_seed = d_accum != nullptr || p->spp > 1;      // draw.cu:74,162 vs draw.cu:105
   const int sppe = sample_count;
   const Options& opt = sc->opt;
@@ -662,17 +662,20 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
   if (slab_pixels > npix) slab_pixels = npix;
   const int nslabs = (int)((npix + slab_pixels - 1) / slab_pixels);
   const long long slab_samples_max = slab_pixels * sppe;
+  // (a sparse launch hands out at most this many samples: the listed pixels of one slab)
+  const long long listed_max = sparse ? (ax->num_listed < slab_pixels ? ax->num_listed : slab_pixels) : 0;
+  const long long launch_samples_max = sparse ? listed_max * sppe : slab_samples_max;
   const bool count = (p->flags & MIRT_RENDER_COUNTERS) != 0;
 
   if (!sc->grid_blocks) sc->grid_blocks = grid_blocks(sc->device);      // per scene, i.e. per device
   const int blocks_cached = sc->grid_blocks;
-  long long want_blocks = (slab_samples_max + TRACE_BLOCK - 1) / TRACE_BLOCK;
+  long long want_blocks = (launch_samples_max + TRACE_BLOCK - 1) / TRACE_BLOCK;
   int blocks = (int)(want_blocks < blocks_cached ? want_blocks : blocks_cached);
   // A small frame (one GPU's stripe set of an 8-GPU job) rendered while another frame is in flight gets half the grid:
   // every wave ends with a drain -- its last samples, few live lanes, 0.5-2.5 ms -- during which it holds its slot, and
   // with two half-grid frames resident at a time there are half as many drains per frame (1/8 of 1080p x 16: 5.8 -> 5.4
   // ms per frame; no gain from 1/4 of a frame up, a loss for a frame rendered alone).
-  if (!count && blocks == blocks_cached && slab_samples_max < 20ll * blocks_cached * TRACE_BLOCK) {
+  if (!count && blocks == blocks_cached && launch_samples_max < 20ll * blocks_cached * TRACE_BLOCK) {
     for (int i = 0; i < MIRT_MAX_FRAMES; ++i) {
       const RenderCtx& c = sc->ctx[i];
       if (c.used && c.stream != stream && hipEventQuery(c.ev3) == hipErrorNotReady) { blocks = blocks_cached > 1 ? blocks_cached / 2 : 1; break; }   // (a frame on this same stream does not overlap)
@@ -706,6 +709,27 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
     hipFree(cx.stack_spill); cx.stack_spill = nullptr; cx.spill_cap = 0;
     MIRT_HIP(hipMalloc(&cx.stack_spill, sizeof(uint32_t) * spill_need));
     cx.spill_cap = spill_need;
+  }
+  if (sparse) {
+    const size_t blocks_need = sparse_blocks_words(ax->num_listed);
+    if (cx.sp_list_cap < (size_t)ax->num_listed || cx.sp_table_cap < (size_t)launch_samples_max || cx.sp_blocks_cap < blocks_need) {
+      MIRT_HIP(hipStreamSynchronize(stream));
+      if (cx.sp_list_cap < (size_t)ax->num_listed) {
+        hipFree(cx.sp_list); cx.sp_list = nullptr; cx.sp_list_cap = 0;
+        MIRT_HIP(hipMalloc(&cx.sp_list, 4 * (size_t)ax->num_listed));
+        cx.sp_list_cap = (size_t)ax->num_listed;
+      }
+      if (cx.sp_table_cap < (size_t)launch_samples_max) {
+        hipFree(cx.sp_table); cx.sp_table = nullptr; cx.sp_table_cap = 0;
+        MIRT_HIP(hipMalloc(&cx.sp_table, 4 * (size_t)launch_samples_max));
+        cx.sp_table_cap = (size_t)launch_samples_max;
+      }
+      if (cx.sp_blocks_cap < blocks_need) {
+        hipFree(cx.sp_blocks); cx.sp_blocks = nullptr; cx.sp_blocks_cap = 0;
+        MIRT_HIP(hipMalloc(&cx.sp_blocks, 4 * blocks_need));
+        cx.sp_blocks_cap = blocks_need;
+      }
+    }
   }
   const bool need_pending = sc->any_trans || sc->d.gi != 0;
   const int pending_slots = need_pending ? 2 * (sc->d.bounces + (sc->d.gi > 0 ? sc->d.gi : 0) + 2) : 0;
@@ -789,13 +813,15 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
   // chunk size: 256 samples, smaller for a small (part of a) frame so that every wave still gets a dozen chunks or more --
   // with four chunks per wave (1/8 of a 1080p frame) the waves finished up to a chunk apart
   int chunk_shift = MAX_CHUNK_SHIFT;
-  while (chunk_shift > MIN_CHUNK_SHIFT && (slab_samples_max >> chunk_shift) < 16ll * blocks * (TRACE_BLOCK / 64)) --chunk_shift;
+  while (chunk_shift > MIN_CHUNK_SHIFT && (launch_samples_max >> chunk_shift) < 16ll * blocks * (TRACE_BLOCK / 64)) --chunk_shift;
   if (opt.chunk_shift >= 4) chunk_shift = opt.chunk_shift;
   a.chunk_shift = chunk_shift;
   const size_t nchunks = (size_t)((slab_samples_max + (1ll << chunk_shift) - 1) >> chunk_shift);
   // sched = 1 (by chunk): one-slab calls only; sched = 2 (by sample): any call
   const bool wavefront = opt.wavefront != 0;
-  const bool sched = opt.sched == 1 && nslabs == 1 && !wavefront;
+  // (a sparse call is handed out in list order: it neither measures an order nor uses one, and leaves the chunk orders and the
+  // scene's by-sample table -- which belong to the dense shape rendered last -- as they are)
+  const bool sched = opt.sched == 1 && nslabs == 1 && !wavefront && !sparse;
   if (sched && cx.chunk_cap < nchunks) {
     MIRT_HIP(hipDeviceSynchronize());   // a frame on another stream may still be reading one of these orders
     hipFree(cx.chunk_cost); cx.chunk_cost = nullptr; cx.chunk_cap = 0; cx.order_key = -1;
@@ -827,7 +853,7 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
   // chunk order: a 1/8 stripe share of the headline frame 4.16 -> 3.22 ms alone (its last expensive samples no longer start
   // late), redchair.txt 1080p16 23.8 -> 20.5 ms, tenthousand.txt 22.5 -> 21.7.
   const long long total_samples = (long long)npix * sppe;
-  const bool by_sample = opt.sched == 2 && !wavefront && slab_samples_max < 0x7fffffffll && total_samples <= (3ll << 30);
+  const bool by_sample = opt.sched == 2 && !wavefront && !sparse && slab_samples_max < 0x7fffffffll && total_samples <= (3ll << 30);
   bool measure_samples = false, ordered_samples = false;
   a.sample_order = nullptr; a.sample_key = nullptr;
   if (by_sample) {
@@ -894,6 +920,10 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
     a.pixel_base = p0; a.num_local_pixels = pn; a.num_samples = pn * sppe;
     a.sample_order = ordered_samples ? sc->so_order + (size_t)p0 * sppe : nullptr;      // (this launch's part of the table)
     a.sample_key = measure_samples ? sc->so_keys : nullptr;
+    if (sparse) {
+      a.sample_order = cx.sp_table;
+      a.num_samples = (pn < listed_max ? pn : listed_max) * sppe;      // (an upper bound: sparse_expand writes the launch's own number over it)
+    }
     // (the work counter, counters[8], and the count of waves that ran past its end, counters[12], are left at zero by the launch
     // itself; counters[9], the overflow events, is only reset by mirt_get_stats)
     if (wavefront) {
@@ -912,6 +942,12 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
       if (!cx.args_valid[slot] || memcmp(&cx.args_host[slot], &a, sizeof(RenderArgs)) != 0) {
         MIRT_HIP(hipMemcpyAsync(adev, &a, sizeof(RenderArgs), hipMemcpyHostToDevice, stream));
         cx.args_host[slot] = a; cx.args_valid[slot] = true;
+      }
+      if (sparse) {
+        // this slab's listed pixels -> the hand-out table and, in the device copy of the arguments, the number of samples
+        cx.args_valid[slot] = false;      // (the device copy no longer equals the host's)
+        int rc = sparse_expand(cx, ax->list, ax->num_listed, p0, pn, sppe, &adev->num_samples, stream);
+        if (rc != MIRT_OK) return rc;
       }
       MIRT_HIP(hipEventRecord(cx.slab_ev[2 * slab], stream));
       // one instantiation per form of the random-number tables (device_common.h, xw_init) and per node format
@@ -938,7 +974,10 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
     ResolveArgs ra;
     ra.samples = cx.samples; ra.rgba8 = (unsigned char*)d_rgba8; ra.rgba_f32 = (float4*)d_rgba_f32; ra.accum = (float4*)d_accum;
     ra.num_local_pixels = pn; ra.pixel_base = p0; ra.spp = p->spp; ra.count = sample_count;
-    if (sample_count > 1 && P <= 64) {
+    if (ax) {
+      int rc = resolve_moments(cx, cx.samples, *ax, (float4*)d_accum, p0, pn, ax->num_listed, sample_count, stream);
+      if (rc != MIRT_OK) return rc;
+    } else if (sample_count > 1 && P <= 64) {
       const long long ppb = TBLOCK >> lg;
       hipLaunchKernelGGL(resolve_tree_kernel, dim3((unsigned)((pn + ppb - 1) / ppb)), dim3(TBLOCK), 0, stream, ra, P, lg);
     } else {
@@ -999,6 +1038,16 @@ int render_accumulate(MirtScene* sc, const MirtRenderParams* p, void* d_accum, i
 {
   if (!d_accum) { set_error("mirt_render_accumulate: bad parameters"); return MIRT_ERR_ARG; }
   return render_impl(sc, p, nullptr, nullptr, d_accum, sample_first, sample_count, stream);
+}
+
+// mirt_render_accumulate_pixels: the list is device memory, so its entries are bounded on the device (adaptive.hip, RangePred)
+int render_accumulate_pixels(MirtScene* sc, const MirtRenderParams* p, const AdaptiveArgs& ax, void* d_accum, int sample_first, int sample_count, hipStream_t stream)
+{
+  if (!d_accum || ax.num_listed < 0 || sample_count < 0) { set_error("mirt_render_accumulate_pixels: bad parameters"); return MIRT_ERR_ARG; }
+  if (ax.list && ax.num_listed > 0 && ((uintptr_t)ax.list & 3u) != 0) { set_error("mirt_render_accumulate_pixels: the pixel list must be 4-byte aligned"); return MIRT_ERR_ARG; }
+  if (!sc->built) { set_error("mirt_render_accumulate_pixels: call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
+  if (ax.list && ax.num_listed == 0) return MIRT_OK;
+  return render_impl(sc, p, nullptr, nullptr, d_accum, sample_first, sample_count, stream, &ax);
 }
 
 __global__ void __launch_bounds__(RBLOCK) finalize_kernel_dev(const float4* __restrict__ accum, uchar4* __restrict__ rgba8, long long n, int aa)

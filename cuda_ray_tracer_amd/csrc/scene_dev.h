@@ -204,6 +204,21 @@ struct RenderCtx {
   unsigned long long order_frame = 0;      // frame_id of the frame that measured it
   hipEvent_t order_ev = nullptr;           // ... and the end of its sort
   float wf_trace_ms = -1.0f;               // >= 0: the wavefront path ran; summed trace-kernel time
+  // mirt_render_accumulate_pixels with a pixel list (adaptive.hip): the listed pixels of the current slab in list order, the
+  // position -> launch-sample table made from them (RenderArgs::sample_order of that launch), and the per-block counts of the
+  // compaction, whose last word is the number of pixels kept
+  uint32_t* sp_list = nullptr; size_t sp_list_cap = 0;
+  uint32_t* sp_table = nullptr; size_t sp_table_cap = 0;
+  uint32_t* sp_blocks = nullptr; size_t sp_blocks_cap = 0;
+};
+
+// What mirt_render_accumulate_pixels adds to mirt_render_accumulate: the pixels to render (null: every pixel of the part) and
+// the two optional outputs.
+struct AdaptiveArgs {
+  const uint32_t* list = nullptr;          // device: num_listed distinct local pixels of the part, any order
+  long long num_listed = 0;
+  float4* accum_sq = nullptr;              // nullable: per-pixel sums of the squared samples
+  uint32_t* counts = nullptr;              // nullable: per-pixel sample counts
 };
 
 } // namespace mirt
@@ -297,6 +312,15 @@ int ensure_rng_tables(RngCache* rc, int sample_tables, long long frame_pixels, h
 int render_accumulate(MirtScene* sc, const MirtRenderParams* p, void* d_accum, int sample_first, int sample_count, hipStream_t stream);
 int finalize(const MirtRenderParams* p, const void* d_accum, int total_samples, void* d_rgba8, hipStream_t stream);
 void rng_cache_free(RngCache* rc);
+int render_accumulate_pixels(MirtScene* sc, const MirtRenderParams* p, const AdaptiveArgs& ax, void* d_accum, int sample_first, int sample_count, hipStream_t stream);
+// adaptive.hip
+size_t sparse_blocks_words(long long num_listed);
+int sparse_expand(RenderCtx& cx, const uint32_t* list, long long num_listed, long long p0, long long pn, int count, long long* num_samples_dev, hipStream_t stream);
+int resolve_moments(RenderCtx& cx, const float4* samples, const AdaptiveArgs& ax, float4* accum, long long p0, long long pn, long long num_listed,
+                    int count, hipStream_t stream);
+int select_pixels(const MirtRenderParams* p, const void* d_accum, const void* d_accum_sq, const uint32_t* d_counts, int min_samples, int max_samples,
+                  float max_variance, uint32_t* d_pixels_out, uint32_t* d_num_out, hipStream_t stream);
+int finalize_counts(const MirtRenderParams* p, const void* d_accum, const uint32_t* d_counts, void* d_rgba8, hipStream_t stream);
 // query.hip
 int trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits, uint32_t flags, hipStream_t stream);
 int camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, hipStream_t stream);

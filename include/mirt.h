@@ -174,6 +174,49 @@ int mirt_render(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, void* d
 int mirt_render_accumulate(MirtScene* sc, const MirtRenderParams* p, void* d_accum_f32, int sample_first, int sample_count, void* stream);
 int mirt_finalize(const MirtRenderParams* p, const void* d_accum_f32, int total_samples, void* d_rgba8, void* stream);
 
+/* ---- adaptive sampling: more samples only where the image is noisy -------------------------------- */
+/* Not in the reference (render_kernel_atomic_aa adds the same samples to every pixel).  Callers detect the feature by these
+ * symbols (MIRT_VERSION stays 3).  The three calls are the pieces of one loop: a dense call with moments and counts, then rounds
+ * of mirt_select_pixels -> mirt_render_accumulate_pixels on the selected pixels, then mirt_finalize_counts.
+ *
+ * mirt_render_accumulate_pixels: mirt_render_accumulate for the pixels of a list.  d_pixels: num_listed DISTINCT local pixel
+ * indices into the part's compact buffer (the indexing of mirt_part_pixel_xy), uint32, device memory, 4-byte aligned, any order.
+ * For every listed pixel lp:
+ *   d_accum_f32[lp]    += the sum of its samples [sample_first, sample_first + sample_count): the float4, bit for bit, that
+ *                         mirt_render_accumulate with the same p, sample_first and sample_count adds to that pixel
+ *   d_accum_sq_f32[lp] += (nullable) the per-channel sum of the squares of the same samples (float4): each square one float32
+ *                         multiply, summed in the same xor-butterfly order as the samples (absent samples 0, P the next power of two)
+ *   d_counts[lp]       += (nullable, uint32) sample_count
+ * One read-modify-write per pixel and buffer, no atomics.  A pixel that is not listed is neither traced nor written, in any of
+ * the three buffers; neither is an entry >= mirt_render_num_pixels(p) (the list is bounded on the device).
+ * d_pixels == NULL with num_listed == 0: every pixel of the part -- the dense call, its measured hand-out order included, plus the
+ * two extra outputs.  d_pixels != NULL with num_listed == 0: MIRT_OK, nothing launched.
+ * As mirt_render_accumulate: asynchronous on `stream`; sample_first + sample_count <= 4096; rendered in slabs of at most
+ * 2^slab_log2 samples of workspace (a slab is a range of the part's pixels, and holds the listed pixels that fall into it);
+ * MIRT_RENDER_COUNTERS counts (samples = num_listed x sample_count); render contexts, frames in flight and overflow reporting
+ * as for every render call.  A call with a list is handed out in list order: it neither uses nor changes the measured hand-out
+ * order ("sched") of the dense shape rendered last, so a full frame rendered afterwards is not measured again.
+ * MIRT_ERR_STATE before mirt_build_lbvh.  MIRT_ERR_ARG: null scene, p or d_accum_f32; a negative count; a null list with
+ * num_listed > 0, or a misaligned one; a list (d_pixels != NULL) on a scene with wavefront = 1 -- the trace / shade kernel pair
+ * takes its samples in frame order only. */
+int mirt_render_accumulate_pixels(MirtScene* sc, const MirtRenderParams* p, const uint32_t* d_pixels, int64_t num_listed, void* d_accum_f32,
+                                  void* d_accum_sq_f32, uint32_t* d_counts, int sample_first, int sample_count, void* stream);
+/* The pixels of the part that need more samples, in increasing order, to d_pixels_out (capacity mirt_render_num_pixels(p)
+ * entries) and their number to d_num_out (one uint32); all device memory.  Pixel lp with n = d_counts[lp] is selected when
+ *     n < max_samples && (n < min_samples || e > max_variance)
+ * where e is the largest, over the channels r, g, b, of the estimated variance of the pixel mean, in float32 with one rounding
+ * per operation and IEEE division; S = d_accum_f32[lp], Q = d_accum_sq_f32[lp]:
+ *     nf = (float)n;  m = S_c / nf;  q = Q_c / nf;  v = q - m * m;  v = v > 0 ? v : 0;  e_c = v / (nf - 1);  e = fmaxf(e_r, fmaxf(e_g, e_b))
+ * (v > 0 ? v : 0 also turns a NaN into 0: a non-finite pixel is not chased to max_samples).  The result is deterministic: wave
+ * ballots, a block scan and a scan over the blocks in a second pass; no kernel waits for another block.
+ * Asynchronous on `stream`, on the current device; no allocation beyond a workspace kept per device and stream (4 B per 1024
+ * pixels).  MIRT_ERR_ARG: a null pointer, min_samples < 2, max_samples < min_samples. */
+int mirt_select_pixels(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, int min_samples,
+                       int max_samples, float max_variance, uint32_t* d_pixels_out, uint32_t* d_num_out, void* stream);
+/* mirt_finalize with a sample count per pixel: pixel lp gets exactly the bytes mirt_finalize(total_samples = d_counts[lp])
+ * gives it (mean, sRGB, clamp * 255 + 0.5, draw.cu:22-46); a pixel with count 0 is written as 0, 0, 0, 0. */
+int mirt_finalize_counts(const MirtRenderParams* p, const void* d_accum_f32, const uint32_t* d_counts, void* d_rgba8, void* stream);
+
 /* Where local pixel `local` of a part's compact buffer lies in the frame (host arithmetic: the mapping mirt_render,
  * mirt_scatter_part and the multi-GPU gather use).  Returns MIRT_ERR_ARG when `local` is not a pixel of the part. */
 int mirt_part_pixel_xy(const MirtRenderParams* p, int64_t local, int32_t* x, int32_t* y);

@@ -123,6 +123,7 @@ EXPORTS = [
     "mirt_trace_rays", "mirt_camera_rays",
     "mirt_scene_get_camera", "mirt_scene_set_camera", "mirt_multi_set_camera", "mirt_scene_update_spheres", "mirt_scene_update_triangles",
     "mirt_render_accumulate_pixels", "mirt_select_pixels", "mirt_finalize_counts",
+    "mirt_hit_features", "mirt_denoise", "mirt_denoise_work_bytes",
 ]
 
 _lib = None
@@ -193,6 +194,12 @@ def lib():
         L.mirt_select_pixels.argtypes = [C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                          C.c_void_p]
         L.mirt_finalize_counts.argtypes = [C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "mirt_denoise"):      # (denoising: likewise)
+        L.mirt_hit_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.mirt_denoise_work_bytes.argtypes = [C.POINTER(RenderParams)]
+        L.mirt_denoise_work_bytes.restype = C.c_size_t
+        L.mirt_denoise.argtypes = [C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -706,6 +713,96 @@ def render_adaptive(raw, width, height, min_spp, max_spp, step, max_variance, pa
             rounds += 1
         finalize_counts(image, accum, counts, width, height, params=p, stream=s)
     return image, counts, rounds
+
+
+# ------------------------------------------------------------------------------------------------------
+# Denoising (mirt_hit_features / mirt_denoise): features are float32 [n, 8] tensors, (Px, Py, Pz, hit, nx, ny, nz, 0) per ray
+# ------------------------------------------------------------------------------------------------------
+# Defaults of the filter's three scales, MIRT_DENOISE_SIGMA_* of include/mirt.h (DESIGN.md section 6f has the table of mean squared
+# errors against converged frames they were chosen from)
+DENOISE_SIGMA_C = 1.0
+DENOISE_SIGMA_N = 0.03
+DENOISE_SIGMA_P = 0.1
+
+
+def hit_features(raw, d_rays, d_hits, d_features, stream=None):
+    """mirt_hit_features: rays (float32 [n, 8]) and their closest-hit records (a 4-byte dtype, [n, 6]) -> d_features (float32
+    [n, 8]): hit point and hit flag, normal and 0; a miss gives a zero row.  All contiguous and on the scene's device.
+    Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    _query_layout(d_rays, "d_rays", (torch.float32,), 8, None)
+    n = d_rays.shape[0]
+    _query_layout(d_hits, "d_hits", _hit_dtypes(), 6, n)
+    _query_layout(d_features, "d_features", (torch.float32,), 8, n)
+    for x, name in ((d_rays, "d_rays"), (d_hits, "d_hits"), (d_features, "d_features")):
+        _query_device(x, name, raw)
+    _check(lib().mirt_hit_features(raw._h, C.c_void_p(d_rays.data_ptr()) if n else None, C.c_void_p(d_hits.data_ptr()) if n else None, n,
+                                   C.c_void_p(d_features.data_ptr()) if n else None, _stream_ptr(stream)))
+
+
+def denoise_work_bytes(img_width, img_height, params=None):
+    """mirt_denoise_work_bytes: the bytes of workspace a denoise call of this frame needs (40 per pixel; host arithmetic)."""
+    p = params if params is not None else render_params(img_width, img_height, 2)
+    return int(lib().mirt_denoise_work_bytes(C.byref(p)))
+
+
+def denoise(d_out, d_accum, d_accum_sq, d_counts, d_features, img_width, img_height, d_work, iterations=5, sigma_c=DENOISE_SIGMA_C,
+            sigma_n=DENOISE_SIGMA_N, sigma_p=DENOISE_SIGMA_P, params=None, stream=None):
+    """mirt_denoise: the variance-guided a-trous filter over a whole frame.  d_accum, d_accum_sq (float32, 4 per pixel) and
+    d_counts (a 4-byte integer per pixel) as render_accumulate_pixels leaves them, d_features (float32 [num_pixels, 8]) from
+    hit_features of the frame's camera rays; d_out (float32, 4 per pixel) receives the filtered mean -- finalize(..., 1) makes the
+    8-bit image of it; d_work is a float32 tensor of denoise_work_bytes / 4 elements that no other call in flight uses.  All
+    tensors contiguous, on one device, and distinct.  Asynchronous on `stream`."""
+    import torch
+    p = params if params is not None else render_params(img_width, img_height, 2)
+    if p.num_parts != 1:
+        raise ValueError("denoise works on whole frames: params.num_parts must be 1")
+    n = num_pixels(p)
+    _flat_layout(d_out, "d_out", (torch.float32,), 4 * n)
+    _flat_layout(d_accum, "d_accum", (torch.float32,), 4 * n)
+    _flat_layout(d_accum_sq, "d_accum_sq", (torch.float32,), 4 * n)
+    _flat_layout(d_counts, "d_counts", _int_dtypes(), n)
+    _query_layout(d_features, "d_features", (torch.float32,), 8, n)
+    _flat_layout(d_work, "d_work", (torch.float32,), 10 * n)
+    if not 0 <= int(iterations) <= 8:
+        raise ValueError(f"iterations is {iterations}; expected 0..8")
+    for s, name in ((sigma_c, "sigma_c"), (sigma_n, "sigma_n"), (sigma_p, "sigma_p")):
+        if not (0.0 < float(s) < float("inf")):
+            raise ValueError(f"{name} is {s}; expected a finite positive number")
+    if d_accum.device.type != "cuda":
+        raise ValueError(f"d_accum is on {d_accum.device}; expected a cuda device")
+    device = d_accum.device.index if d_accum.device.index is not None else torch.cuda.current_device()
+    for x, name in ((d_out, "d_out"), (d_accum_sq, "d_accum_sq"), (d_counts, "d_counts"), (d_features, "d_features"), (d_work, "d_work")):
+        _same_device(x, name, device)
+    with torch.cuda.device(device):
+        _check(lib().mirt_denoise(C.byref(p), C.c_void_p(d_accum.data_ptr()), C.c_void_p(d_accum_sq.data_ptr()), C.c_void_p(d_counts.data_ptr()),
+                                  C.c_void_p(d_features.data_ptr()), int(iterations), float(sigma_c), float(sigma_n), float(sigma_p),
+                                  C.c_void_p(d_work.data_ptr()), C.c_void_p(d_out.data_ptr()), _stream_ptr(stream)))
+
+
+def denoise_frame(raw, accum, accum_sq, counts, width, height, spp, iterations=5, sigma_c=DENOISE_SIGMA_C, sigma_n=DENOISE_SIGMA_N,
+                  sigma_p=DENOISE_SIGMA_P, stream=None):
+    """Denoise the frame whose moments render_accumulate_pixels (or render_adaptive's loop) left in accum, accum_sq and counts:
+    camera_rays (sample 0 of every pixel of a width x height frame at `spp`) -> trace_rays -> hit_features -> denoise ->
+    finalize with total_samples = 1.  Returns (rgba8 uint8 [num_pixels * 4], float32 [num_pixels * 4]: the filtered mean)."""
+    import torch
+    p = render_params(width, height, max(spp, 2))      # (the seeding of render_accumulate's samples, whatever their number)
+    n = num_pixels(p)
+    dev = torch.device("cuda", raw.device)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        hits = torch.empty((n, 6), dtype=torch.int32, device=dev)
+        features = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        work = torch.empty(10 * n, dtype=torch.float32, device=dev)
+        out = torch.empty(4 * n, dtype=torch.float32, device=dev)
+        image = torch.empty(4 * n, dtype=torch.uint8, device=dev)
+        camera_rays(raw, rays, width, height, p.spp, params=p, stream=s)
+        trace_rays(raw, rays, hits, stream=s)
+        hit_features(raw, rays, hits, features, stream=s)
+        denoise(out, accum, accum_sq, counts, features, width, height, work, iterations, sigma_c, sigma_n, sigma_p, params=p, stream=s)
+        finalize(image, out, width, height, 1, params=p, stream=s)
+    return image, out
 
 
 def pack_rays(origins, dirs, tmax=float("inf")):

@@ -377,6 +377,22 @@ int mirt_camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, voi
   return camera_rays(sc, p, d_rays, (hipStream_t)stream);
 }
 
+int mirt_hit_features(MirtScene* sc, const void* d_rays, const void* d_hits, int64_t n, void* d_features, void* stream)
+{
+  if (!sc) { set_error("mirt_hit_features: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return hit_features(sc, d_rays, d_hits, n, d_features, (hipStream_t)stream);
+}
+
+size_t mirt_denoise_work_bytes(const MirtRenderParams* p) { return denoise_work_bytes(p); }
+
+int mirt_denoise(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, const void* d_features,
+                 int iterations, float sigma_c, float sigma_n, float sigma_p, void* d_work, void* d_out_f32, void* stream)
+{
+  if (!p) { set_error("mirt_denoise: null argument"); return MIRT_ERR_ARG; }
+  return denoise(p, d_accum_f32, d_accum_sq_f32, d_counts, d_features, iterations, sigma_c, sigma_n, sigma_p, d_work, d_out_f32, (hipStream_t)stream);
+}
+
 int mirt_scene_get_camera(const MirtScene* sc, MirtCamera* out)
 {
   if (!sc || !out) { set_error("mirt_scene_get_camera: null argument"); return MIRT_ERR_ARG; }

@@ -1,7 +1,7 @@
 // raytracer -- the reference's command line (main.cu:25-94) over libmirt's C ABI:
 //
 //     raytracer scene.txt [--width W] [--height H] [--spp N] [--out file.png] [--device D] [--gpus N] [--frames K]
-//                         [--traversal 0|1|2] [--bounds-as-shipped] [--adaptive V [--min-spp N] [--step N]]
+//                         [--traversal 0|1|2] [--bounds-as-shipped] [--adaptive V [--min-spp N] [--step N]] [--denoise K]
 //
 // Same contract: one positional scene file, the PNG is named by the scene's `png W H name` line and written to the
 // current directory, the same lines go to stdout -- the phase timings (main.cu:39,61,71,80,93, with the reference's labels:
@@ -14,6 +14,9 @@
 // --adaptive V: adaptive sampling (mirt_render_accumulate_pixels / mirt_select_pixels / mirt_finalize_counts): --min-spp samples
 // (default 4) for every pixel, then rounds of --step more (default: --min-spp) for the pixels whose estimated variance of the mean
 // exceeds V, up to --spp samples per pixel; one line reports the samples used.  One GPU only.
+// --denoise K: the frame's sample moments (all --spp samples of every pixel, or what --adaptive leaves) are filtered by K iterations
+// of mirt_denoise with the default scales, guided by the closest hits of the frame's camera rays (mirt_camera_rays ->
+// mirt_trace_rays -> mirt_hit_features); the image is the filtered mean.  One GPU only.
 // --bounds-as-shipped builds the tree of the shipped reference (scene bounds never stored, parse.cpp:28: every Morton code 0).
 #include <hip/hip_runtime.h>
 
@@ -64,7 +67,7 @@ int main(int argc, char* argv[])
 {
   if (argc < 2) { std::cout << "Error opening file..." << std::endl; return 1; }
   int ow = 0, oh = 0, ospp = -1, device = 0, gpus = 1, traversal = -1, frames = 1, shipped = 0;
-  int min_spp = 4, step = 0;
+  int min_spp = 4, step = 0, denoise = -1;
   bool adaptive = false;
   float max_variance = 0.0f;
   std::string out_override;
@@ -83,10 +86,12 @@ int main(int argc, char* argv[])
     else if (a == "--adaptive") { need(1); adaptive = true; max_variance = (float)atof(argv[++i]); }
     else if (a == "--min-spp") { need(1); min_spp = atoi(argv[++i]); }
     else if (a == "--step") { need(1); step = atoi(argv[++i]); }
+    else if (a == "--denoise") { need(1); denoise = atoi(argv[++i]); if (denoise < 0 || denoise > 8) { std::cerr << "--denoise takes 0 to 8 iterations" << std::endl; return 2; } }
     else { std::cerr << "unknown option " << a << std::endl; return 2; }
   }
 
   if (adaptive && gpus > 1) { std::cerr << "--adaptive renders on one GPU: it cannot be combined with --gpus " << gpus << std::endl; return 2; }
+  if (denoise >= 0 && gpus > 1) { std::cerr << "--denoise filters a whole frame on one GPU: it cannot be combined with --gpus " << gpus << std::endl; return 2; }
   if (step <= 0) step = min_spp;
   if (adaptive && (min_spp < 2 || (ospp >= 0 && ospp < min_spp))) { std::cerr << "--adaptive needs 2 <= --min-spp <= --spp" << std::endl; return 2; }
 
@@ -162,10 +167,11 @@ int main(int argc, char* argv[])
 
   start = std::chrono::high_resolution_clock::now();
   if (!adaptive) print_debug_render(width, height, spp);
-  if (adaptive) {
+  if (adaptive || denoise >= 0) {
     // the loop of DESIGN.md section 6e: every pixel gets samples [0, min_spp), then the pixels mirt_select_pixels still finds noisy
-    // get the samples of one more round, the same range for all of them
-    if (spp < min_spp) { std::cerr << "--adaptive needs 2 <= --min-spp <= --spp" << std::endl; return 2; }
+    // get the samples of one more round, the same range for all of them.  --denoise alone: every pixel gets samples [0, spp).
+    if (adaptive && spp < min_spp) { std::cerr << "--adaptive needs 2 <= --min-spp <= --spp" << std::endl; return 2; }
+    const int first_count = adaptive ? min_spp : (spp > 1 ? spp : 1);
     const size_t n = (size_t)width * height;
     void *accum = nullptr, *accum_sq = nullptr;
     uint32_t *counts = nullptr, *pixels = nullptr, *num = nullptr;
@@ -173,20 +179,38 @@ int main(int argc, char* argv[])
     HIP_CHECK(hipMalloc(&counts, 4 * n)); HIP_CHECK(hipMalloc(&pixels, 4 * n)); HIP_CHECK(hipMalloc(&num, 4));
     HIP_CHECK(hipMemset(accum, 0, 16 * n)); HIP_CHECK(hipMemset(accum_sq, 0, 16 * n)); HIP_CHECK(hipMemset(counts, 0, 4 * n));
     p.spp = spp > 2 ? spp : 2;
-    die_on(mirt_render_accumulate_pixels(sc, &p, nullptr, 0, accum, accum_sq, counts, 0, min_spp, nullptr), "render");
-    for (int r = 0; min_spp + (r + 1) * step <= spp; ++r) {
+    die_on(mirt_render_accumulate_pixels(sc, &p, nullptr, 0, accum, accum_sq, counts, 0, first_count, nullptr), "render");
+    for (int r = 0; adaptive && min_spp + (r + 1) * step <= spp; ++r) {
       die_on(mirt_select_pixels(&p, accum, accum_sq, counts, min_spp, spp, max_variance, pixels, num, nullptr), "render");
       uint32_t k = 0;
       HIP_CHECK(hipMemcpy(&k, num, 4, hipMemcpyDeviceToHost));
       if (k == 0) break;
       die_on(mirt_render_accumulate_pixels(sc, &p, pixels, k, accum, accum_sq, counts, min_spp + r * step, step, nullptr), "render");
     }
-    die_on(mirt_finalize_counts(&p, accum, counts, d_image, nullptr), "render");
-    std::vector<uint32_t> host_counts(n);
-    HIP_CHECK(hipMemcpy(host_counts.data(), counts, 4 * n, hipMemcpyDeviceToHost));
-    unsigned long long used = 0;
-    for (uint32_t c : host_counts) used += c;
-    printf("Adaptive sampling: %llu samples used (min-spp x pixels: %llu, spp x pixels: %llu)\n", used, (unsigned long long)min_spp * n, (unsigned long long)spp * n);
+    if (denoise >= 0) {
+      // sample 0's primary hits steer the filter (p.spp > 1: the rays mirt_render_accumulate_pixels started with)
+      void *rays = nullptr, *hits = nullptr, *features = nullptr, *work = nullptr, *mean = nullptr;
+      HIP_CHECK(hipMalloc(&rays, 32 * n)); HIP_CHECK(hipMalloc(&hits, 24 * n)); HIP_CHECK(hipMalloc(&features, 32 * n));
+      HIP_CHECK(hipMalloc(&work, mirt_denoise_work_bytes(&p))); HIP_CHECK(hipMalloc(&mean, 16 * n));
+      die_on(mirt_camera_rays(sc, &p, rays, nullptr), "render");
+      die_on(mirt_trace_rays(sc, rays, (int64_t)n, hits, 0, nullptr), "render");
+      die_on(mirt_hit_features(sc, rays, hits, (int64_t)n, features, nullptr), "render");
+      die_on(mirt_denoise(&p, accum, accum_sq, counts, features, denoise, MIRT_DENOISE_SIGMA_C, MIRT_DENOISE_SIGMA_N, MIRT_DENOISE_SIGMA_P, work, mean, nullptr),
+             "render");
+      die_on(mirt_finalize(&p, mean, 1, d_image, nullptr), "render");
+      HIP_CHECK(hipDeviceSynchronize());
+      HIP_CHECK(hipFree(rays)); HIP_CHECK(hipFree(hits)); HIP_CHECK(hipFree(features)); HIP_CHECK(hipFree(work)); HIP_CHECK(hipFree(mean));
+      printf("Denoise: %d iterations\n", denoise);
+    } else {
+      die_on(mirt_finalize_counts(&p, accum, counts, d_image, nullptr), "render");
+    }
+    if (adaptive) {
+      std::vector<uint32_t> host_counts(n);
+      HIP_CHECK(hipMemcpy(host_counts.data(), counts, 4 * n, hipMemcpyDeviceToHost));
+      unsigned long long used = 0;
+      for (uint32_t c : host_counts) used += c;
+      printf("Adaptive sampling: %llu samples used (min-spp x pixels: %llu, spp x pixels: %llu)\n", used, (unsigned long long)min_spp * n, (unsigned long long)spp * n);
+    }
     HIP_CHECK(hipFree(accum)); HIP_CHECK(hipFree(accum_sq)); HIP_CHECK(hipFree(counts)); HIP_CHECK(hipFree(pixels)); HIP_CHECK(hipFree(num));
   } else {
     for (int f = 0; f < frames; ++f) die_on(mirt_render(sc, &p, d_image, nullptr, nullptr), "render");

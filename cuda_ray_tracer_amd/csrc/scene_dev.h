@@ -324,6 +324,11 @@ int finalize_counts(const MirtRenderParams* p, const void* d_accum, const uint32
 // query.hip
 int trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits, uint32_t flags, hipStream_t stream);
 int camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, hipStream_t stream);
+// denoise.hip
+int hit_features(MirtScene* sc, const void* d_rays, const void* d_hits, int64_t n, void* d_features, hipStream_t stream);
+size_t denoise_work_bytes(const MirtRenderParams* p);
+int denoise(const MirtRenderParams* p, const void* d_accum, const void* d_accum_sq, const uint32_t* d_counts, const void* d_features, int iterations,
+            float sigma_c, float sigma_n, float sigma_p, void* d_work, void* d_out, hipStream_t stream);
 // update.hip
 int update_spheres(MirtScene* sc, const void* d_spheres, int first, int count, hipStream_t stream);
 int update_triangles(MirtScene* sc, const void* d_verts, int first, int count, hipStream_t stream);

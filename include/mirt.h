@@ -267,6 +267,65 @@ int mirt_trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d
  * cache: with spp > 1 any cached sample table serves. */
 int mirt_camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, void* stream);
 
+/* ---- denoising a frame: hit features and a variance-guided a-trous filter ------------------------- */
+/* Not in the reference (it writes the sample mean as it is).  Callers detect the feature by these symbols (MIRT_VERSION stays
+ * 3).  The inputs are what the calls above leave in device memory: the closest hits of a frame's camera rays, and the sums, the
+ * sums of squares and the counts of mirt_render_accumulate_pixels.  Both calls are asynchronous on `stream`, take device pointers
+ * only, allocate nothing, never synchronise, and touch no render context, MirtStats counter or hand-out table.  All arithmetic is
+ * float32 with one IEEE rounding per operation (no fused multiply-add), IEEE division and square root; a + b + c means (a + b) + c;
+ * dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z; length(u) = sqrtf(dot(u, u)); fmaxf / fminf return the operand that is not a NaN.
+ *
+ * mirt_hit_features: n MirtRay rows and the n MirtHit rows a closest-hit mirt_trace_rays answered for them -> n feature rows of
+ * 32 B (d_features 16-byte aligned), each written with two 16-byte stores:
+ *     (Px, Py, Pz, hit)  (nx, ny, nz, 0)
+ * hit = 1.0f and P_c = o_c + t * normalize(d)_c (normalize as mirt_trace_rays normalises: vec3.cuh:72-82; the product rounded,
+ * then the sum), n the record's normal as reported; a miss (kind == MIRT_HIT_NONE) writes eight zeros.  One lane per row.  The
+ * scene is needed only for its device and the "built" check.  n == 0: MIRT_OK, nothing launched.  MIRT_ERR_ARG: null scene,
+ * n < 0, a null or misaligned buffer with n > 0; MIRT_ERR_STATE before mirt_build_lbvh. */
+int mirt_hit_features(MirtScene* sc, const void* d_rays, const void* d_hits, int64_t n, void* d_features, void* stream);
+/* mirt_denoise: the frame p describes (width x height, row-major, N = width * height pixels; p->spp, stripe_rows and flags are
+ * not used) from S = d_accum_f32, Q = d_accum_sq_f32 (float4 per pixel), k = d_counts (uint32 per pixel) and F = d_features
+ * (mirt_hit_features rows of the pixels' rays) -> d_out_f32: N float4, the filtered MEAN (mirt_finalize with total_samples = 1
+ * turns it into the 8-bit image).  d_work: mirt_denoise_work_bytes(p) = 40 N bytes of caller memory (two colour and two variance
+ * buffers; host arithmetic; 0 for parameters mirt_denoise refuses), 16-byte aligned like the float buffers; calls that may overlap
+ * in time need a d_work each.  On the current device.
+ *
+ * Prepare (one kernel), pixel p with k = k_p:
+ *     k == 0: c = (0, 0, 0, 0), else nf = (float)k; c_ch = S_ch / nf for r, g, b, a
+ *     k < 2:  v = 0, else v = mirt_select_pixels' e: m = S_ch / nf; q = Q_ch / nf; t = q - m * m; t = t > 0 ? t : 0 (a NaN gives
+ *             0); e_ch = t / (nf - 1); v = fmaxf(e_r, fmaxf(e_g, e_b))
+ * Iteration i = 0 .. iterations - 1 with step s = 2^i (one kernel each; colour and variance ping-pong between the buffers of
+ * d_work, the last colour goes to d_out_f32; iterations == 0: d_out_f32 = c), pixel p = (x, y):
+ *     c_p.rgb has a non-finite channel: c'_p = c_p, v'_p = v_p.  Otherwise
+ *     g = k00 v(x-1, y-1) + k01 v(x, y-1) + k02 v(x+1, y-1) + k10 v(x-1, y) + ... + k22 v(x+1, y+1), summed left to right in this
+ *         (row-major) order, coordinates clamped to the frame, k = (1/16 1/8 1/16; 1/8 1/4 1/8; 1/16 1/8 1/16)
+ *     den = sigma_c * sqrtf(g) + 1e-10f
+ *     sw = sv = 0, sc = (0, 0, 0, 0); for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), q = (x + s dx, y + s dy):
+ *         skip the tap when q is outside the frame, or c_q.rgb has a non-finite channel
+ *         h = K[|dx|] * K[|dy|], K = (3/8, 1/4, 1/16)
+ *         dx == 0 and dy == 0: a = 0.  Otherwise, with hit_p = (F_p[3] != 0):
+ *             skip the tap when hit_p != hit_q
+ *             both hit:  a_n = fmaxf(0, 1 - dot(n_p, n_q)) / sigma_n;  D = P_q - P_p;  l = length(D);
+ *                        a_p = l == 0 ? 0 : fabsf(dot(n_p, D)) / (sigma_p * l)      -- |cosine| between the centre's normal and
+ *                        the displacement: no scene unit, about 0 inside a flat surface, large across a depth step
+ *             both miss: a_n = a_p = 0
+ *             a_c = fmaxf(fmaxf(|c_p.r - c_q.r|, |c_p.g - c_q.g|), |c_p.b - c_q.b|) / den
+ *             t = a_n + a_p + a_c; skip the tap when t is a NaN; a = fminf(t, 87)
+ *         w = h * expf(-a)      -- the library's own expf (mirt_probe_math which = 1), the same bits on every device
+ *         sw = sw + w;  sc_ch = sc_ch + w * c_q.ch (r, g, b, a);  sv = sv + (w * w) * v_q
+ *     c'_p.ch = sc_ch / sw;  v'_p = sv / (sw * sw)      -- the centre tap is never skipped, so sw >= 9/64
+ * Every pixel depends on its inputs only (no atomics, no communication between lanes): the result does not depend on timing.
+ * MIRT_ERR_ARG (all checked on the host, before any device work): a null pointer; p->num_parts != 1 (whole frames only: a
+ * striped part has no neighbours across stripes); iterations outside [0, 8]; a sigma that is not finite and positive; a
+ * misaligned buffer; d_out_f32 or d_work overlapping an input range (16 N, 16 N, 4 N, 32 N bytes) or each other. */
+/* The scales the drivers (api.denoise_frame, `raytracer --denoise`) use; DESIGN.md section 6f has the table they were chosen from. */
+#define MIRT_DENOISE_SIGMA_C 1.0f
+#define MIRT_DENOISE_SIGMA_N 0.03f
+#define MIRT_DENOISE_SIGMA_P 0.1f
+size_t mirt_denoise_work_bytes(const MirtRenderParams* p);
+int mirt_denoise(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, const void* d_features,
+                 int iterations, float sigma_c, float sigma_n, float sigma_p, void* d_work, void* d_out_f32, void* stream);
+
 /* ---- updates of a built scene in place ---------------------------------------------------------- */
 /* Move the camera, the spheres and the triangles of a scene without creating it again: the render workspaces, the
  * random-number tables and the measured hand-out order of the samples ("sched") stay.  Not in the reference (its RawConfig is

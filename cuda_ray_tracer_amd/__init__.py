@@ -7,10 +7,12 @@ from .api import (MirtError, StlConfig, RawConfig, parseInput, parseText, synthe
                   num_pixels, scatter_part, write_png, lib, render_accumulate, finalize, Ray, Hit, trace_rays,
                   camera_rays, pack_rays, unpack_hits, Camera, update_spheres, update_triangles, render_accumulate_pixels,
                   select_pixels, finalize_counts, render_adaptive, hit_features, denoise,
-                  denoise_work_bytes, denoise_frame)
+                  denoise_work_bytes, denoise_frame, get_spheres, get_triangles, prev_features, temporal_accumulate,
+                  TemporalAccumulator)
 
 __all__ = ["MirtError", "StlConfig", "RawConfig", "parseInput", "parseText", "syntheticScene", "initRawConfigFromStl",
            "copyConfigDataToDevice", "freeRawConfigDeviceMemory", "build_lbvh_karas", "render", "render_params",
            "num_pixels", "scatter_part", "write_png", "lib", "render_accumulate", "finalize", "Ray", "Hit", "trace_rays",
            "camera_rays", "pack_rays", "unpack_hits", "Camera", "update_spheres", "update_triangles", "render_accumulate_pixels",
-           "select_pixels", "finalize_counts", "render_adaptive", "hit_features", "denoise", "denoise_work_bytes", "denoise_frame"]
+           "select_pixels", "finalize_counts", "render_adaptive", "hit_features", "denoise", "denoise_work_bytes", "denoise_frame",
+           "get_spheres", "get_triangles", "prev_features", "temporal_accumulate", "TemporalAccumulator"]

@@ -124,6 +124,7 @@ EXPORTS = [
     "mirt_scene_get_camera", "mirt_scene_set_camera", "mirt_multi_set_camera", "mirt_scene_update_spheres", "mirt_scene_update_triangles",
     "mirt_render_accumulate_pixels", "mirt_select_pixels", "mirt_finalize_counts",
     "mirt_hit_features", "mirt_denoise", "mirt_denoise_work_bytes",
+    "mirt_scene_get_spheres", "mirt_scene_get_triangles", "mirt_prev_features", "mirt_temporal_accumulate",
 ]
 
 _lib = None
@@ -200,6 +201,12 @@ def lib():
         L.mirt_denoise_work_bytes.restype = C.c_size_t
         L.mirt_denoise.argtypes = [C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float,
                                    C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "mirt_temporal_accumulate"):      # (temporal accumulation: likewise)
+        L.mirt_scene_get_spheres.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.mirt_scene_get_triangles.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.mirt_prev_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mirt_temporal_accumulate.argtypes = [C.POINTER(RenderParams), C.POINTER(Camera)] + [C.c_void_p] * 8 + [C.c_int, C.c_float, C.c_float] + \
+                                              [C.c_void_p] * 4
     _lib = L
     return L
 
@@ -803,6 +810,189 @@ def denoise_frame(raw, accum, accum_sq, counts, width, height, spp, iterations=5
         denoise(out, accum, accum_sq, counts, features, width, height, work, iterations, sigma_c, sigma_n, sigma_p, params=p, stream=s)
         finalize(image, out, width, height, 1, params=p, stream=s)
     return image, out
+
+# ------------------------------------------------------------------------------------------------------
+# Temporal accumulation (mirt_scene_get_spheres / mirt_scene_get_triangles / mirt_prev_features / mirt_temporal_accumulate)
+# ------------------------------------------------------------------------------------------------------
+def get_spheres(raw, d_xyzr, first=0, stream=None):
+    """mirt_scene_get_spheres: cx, cy, cz, r of spheres first .. first+n-1 (file order) into d_xyzr (float32 [n, 4], contiguous,
+    on the scene's device): what update_spheres was given, or the file's values.  Asynchronous on `stream`; the scene stays as
+    built as it was."""
+    import torch
+    _query_layout(d_xyzr, "d_xyzr", (torch.float32,), 4, None)
+    _query_device(d_xyzr, "d_xyzr", raw)
+    n = d_xyzr.shape[0]
+    _check(lib().mirt_scene_get_spheres(raw._h, int(first), n, C.c_void_p(d_xyzr.data_ptr()) if n else None, _stream_ptr(stream)))
+
+
+def get_triangles(raw, d_verts, first=0, stream=None):
+    """mirt_scene_get_triangles: p0, p1, p2 of triangles first .. first+n-1 (file order) into d_verts (float32 [n, 9], contiguous,
+    on the scene's device).  Asynchronous on `stream`; the scene stays as built as it was."""
+    import torch
+    _query_layout(d_verts, "d_verts", (torch.float32,), 9, None)
+    _query_device(d_verts, "d_verts", raw)
+    n = d_verts.shape[0]
+    _check(lib().mirt_scene_get_triangles(raw._h, int(first), n, C.c_void_p(d_verts.data_ptr()) if n else None, _stream_ptr(stream)))
+
+
+def prev_features(raw, d_rays, d_hits, d_features, d_prev_xyzr=None, d_prev_verts=None, stream=None):
+    """mirt_prev_features: hit_features' rows with the hit point and normal as they were in the previous geometry: d_prev_xyzr
+    (float32 [num_spheres, 4]) and d_prev_verts (float32 [num_triangles, 9]) are get_spheres / get_triangles of the whole scene
+    before it moved; None: that kind did not move.  All contiguous and on the scene's device.  Asynchronous on `stream`."""
+    import torch
+    _query_layout(d_rays, "d_rays", (torch.float32,), 8, None)
+    n = d_rays.shape[0]
+    _query_layout(d_hits, "d_hits", _hit_dtypes(), 6, n)
+    _query_layout(d_features, "d_features", (torch.float32,), 8, n)
+    tensors = [(d_rays, "d_rays"), (d_hits, "d_hits"), (d_features, "d_features")]
+    if d_prev_xyzr is not None:
+        _query_layout(d_prev_xyzr, "d_prev_xyzr", (torch.float32,), 4, raw.desc.num_spheres)
+        tensors.append((d_prev_xyzr, "d_prev_xyzr"))
+    if d_prev_verts is not None:
+        _query_layout(d_prev_verts, "d_prev_verts", (torch.float32,), 9, raw.desc.num_triangles)
+        tensors.append((d_prev_verts, "d_prev_verts"))
+    for x, name in tensors:
+        _query_device(x, name, raw)
+    ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None
+    _check(lib().mirt_prev_features(raw._h, ptr(d_rays), ptr(d_hits), n, ptr(d_prev_xyzr), ptr(d_prev_verts), ptr(d_features), _stream_ptr(stream)))
+
+
+def _is_pinhole(cam):
+    return cam.fisheye == 0 and cam.panorama == 0 and cam.dof_focus == 0.0
+
+
+def temporal_accumulate(d_out_accum, d_out_accum_sq, d_out_counts, d_accum, d_accum_sq, d_counts, d_prev_features, d_hist_accum, d_hist_accum_sq,
+                        d_hist_counts, d_hist_features, prev_camera, img_width, img_height, max_history=32, sigma_n=DENOISE_SIGMA_N,
+                        sigma_p=DENOISE_SIGMA_P, params=None, stream=None):
+    """mirt_temporal_accumulate: this frame's moments (d_accum, d_accum_sq: float32, 4 per pixel; d_counts: a 4-byte integer per
+    pixel) plus what survives of the previous merged frame (d_hist_*, with d_hist_features = hit_features of that frame and
+    prev_camera its Camera, a pinhole), looked up where d_prev_features (prev_features of this frame's rays) says each pixel's
+    surface point was, into d_out_*.  An output may be its own current-frame tensor (in place); no other overlap.  All tensors
+    contiguous and on one device.  Asynchronous on `stream`."""
+    import torch
+    p = params if params is not None else render_params(img_width, img_height, 2)
+    if p.num_parts != 1:
+        raise ValueError("temporal_accumulate works on whole frames: params.num_parts must be 1")
+    n = num_pixels(p)
+    moments = ((d_out_accum, "d_out_accum"), (d_out_accum_sq, "d_out_accum_sq"), (d_accum, "d_accum"), (d_accum_sq, "d_accum_sq"),
+               (d_hist_accum, "d_hist_accum"), (d_hist_accum_sq, "d_hist_accum_sq"))
+    counts = ((d_out_counts, "d_out_counts"), (d_counts, "d_counts"), (d_hist_counts, "d_hist_counts"))
+    feats = ((d_prev_features, "d_prev_features"), (d_hist_features, "d_hist_features"))
+    for x, name in moments:
+        _flat_layout(x, name, (torch.float32,), 4 * n)
+    for x, name in counts:
+        _flat_layout(x, name, _int_dtypes(), n)
+    for x, name in feats:
+        _query_layout(x, name, (torch.float32,), 8, n)
+    if not isinstance(prev_camera, Camera):
+        raise ValueError("prev_camera must be a Camera")
+    if not _is_pinhole(prev_camera):
+        raise ValueError("prev_camera must be a pinhole: fisheye, panorama and dof_focus 0")
+    if int(max_history) < 1:
+        raise ValueError(f"max_history is {max_history}; expected at least 1")
+    for s, name in ((sigma_n, "sigma_n"), (sigma_p, "sigma_p")):
+        if not (0.0 < float(s) < float("inf")):
+            raise ValueError(f"{name} is {s}; expected a finite positive number")
+    if d_accum.device.type != "cuda":
+        raise ValueError(f"d_accum is on {d_accum.device}; expected a cuda device")
+    device = d_accum.device.index if d_accum.device.index is not None else torch.cuda.current_device()
+    for x, name in moments + counts + feats:
+        _same_device(x, name, device)
+    ptr = lambda x: C.c_void_p(x.data_ptr())
+    with torch.cuda.device(device):
+        _check(lib().mirt_temporal_accumulate(C.byref(p), C.byref(prev_camera), ptr(d_accum), ptr(d_accum_sq), ptr(d_counts), ptr(d_prev_features),
+                                              ptr(d_hist_accum), ptr(d_hist_accum_sq), ptr(d_hist_counts), ptr(d_hist_features), int(max_history),
+                                              float(sigma_n), float(sigma_p), ptr(d_out_accum), ptr(d_out_accum_sq), ptr(d_out_counts),
+                                              _stream_ptr(stream)))
+
+
+class TemporalAccumulator:
+    """Frames of an animated scene that reuse the previous frame's samples.  Allocates once: this frame's moments and two history
+    sets used in turn, two feature buffers, the reprojected features, rays, hits, the snapshots of the spheres and triangles as
+    the previous frame saw them, the denoiser's workspace and the image.  The caller moves the camera (raw.set_camera), moves
+    geometry (update_spheres / update_triangles) and rebuilds (build_lbvh_karas) between frame() calls.  The scene's camera must
+    be a pinhole, at construction and at every frame."""
+
+    def __init__(self, raw, width, height, spp, max_history=32, sigma_n=DENOISE_SIGMA_N, sigma_p=DENOISE_SIGMA_P, stream=None):
+        import torch
+        if not _is_pinhole(raw.camera()):
+            raise ValueError("TemporalAccumulator needs a pinhole camera: fisheye, panorama and dof_focus 0")
+        if not 1 <= int(spp) <= 4096:
+            raise ValueError(f"spp is {spp}; expected 1..4096")
+        if int(max_history) < 1:
+            raise ValueError(f"max_history is {max_history}; expected at least 1")
+        self.raw, self.width, self.height, self.spp = raw, int(width), int(height), int(spp)
+        self.max_history, self.sigma_n, self.sigma_p = int(max_history), float(sigma_n), float(sigma_p)
+        self.params = render_params(self.width, self.height, max(self.spp, 2))
+        n = self.n = num_pixels(self.params)
+        dev = self.device = torch.device("cuda", raw.device)
+        self.stream = stream
+        f = dict(dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            self.cur = (torch.zeros(4 * n, **f), torch.zeros(4 * n, **f), torch.zeros(n, dtype=torch.int32, device=dev))
+            self.hist = [(torch.zeros(4 * n, **f), torch.zeros(4 * n, **f), torch.zeros(n, dtype=torch.int32, device=dev)) for _ in range(2)]
+            self.features = [torch.zeros((n, 8), **f) for _ in range(2)]
+            self.reprojected = torch.zeros((n, 8), **f)
+            self.rays = torch.zeros((n, 8), **f)
+            self.hits = torch.zeros((n, 6), dtype=torch.int32, device=dev)
+            self.prev_xyzr = torch.zeros((raw.desc.num_spheres, 4), **f)
+            self.prev_verts = torch.zeros((raw.desc.num_triangles, 9), **f)
+            self.work = torch.zeros(10 * n, **f)
+            self.filtered = torch.zeros(4 * n, **f)
+            self.image = torch.zeros(4 * n, dtype=torch.uint8, device=dev)
+        self.reset()
+
+    def reset(self):
+        """Forget the history: the next frame is its own samples only.  The sample indices start again at 0."""
+        self.frame_index = 0
+        self.have_history = False
+        self.slot = 0              # hist[slot], features[slot]: the previous merged frame
+        self.prev_camera = None
+
+    def frame(self, denoise_iterations=0):
+        """One frame of the scene as it is now.  Samples [first, first + spp) of every pixel with first = (frame_index * spp) mod
+        (4096 // spp * spp): consecutive frames draw different samples, and the index wraps to 0 before it would pass the
+        renderer's limit of 4096 sample indices (after 4096 // spp frames a frame repeats the samples of an earlier one, long
+        after max_history has scaled that one away).  Returns (rgba8 uint8 [num_pixels * 4], accum, accum_sq, counts): the image
+        and the merged moments, which are the history of the next frame -- they stay valid until the frame after that."""
+        import torch
+        raw, w, h, p, n = self.raw, self.width, self.height, self.params, self.n
+        cam = raw.camera()
+        if not _is_pinhole(cam):
+            raise ValueError("TemporalAccumulator needs a pinhole camera: fisheye, panorama and dof_focus 0")
+        s = self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
+        first = (self.frame_index * self.spp) % (4096 // self.spp * self.spp)
+        S, Q, k = self.cur
+        old, new = self.slot, 1 - self.slot
+        with torch.cuda.device(self.device), torch.cuda.stream(s):
+            S.zero_(); Q.zero_(); k.zero_()
+            render_accumulate_pixels(raw, S, w, h, first, self.spp, None, Q, k, params=p, stream=s)
+            camera_rays(raw, self.rays, w, h, 0, params=render_params(w, h, 0), stream=s)
+            trace_rays(raw, self.rays, self.hits, stream=s)
+            hit_features(raw, self.rays, self.hits, self.features[new], stream=s)
+            oS, oQ, ok = self.hist[new]
+            if self.have_history:
+                prev_features(raw, self.rays, self.hits, self.reprojected, self.prev_xyzr if self.prev_xyzr.shape[0] else None,
+                              self.prev_verts if self.prev_verts.shape[0] else None, stream=s)
+                hS, hQ, hk = self.hist[old]
+                temporal_accumulate(oS, oQ, ok, S, Q, k, self.reprojected, hS, hQ, hk, self.features[old], self.prev_camera, w, h,
+                                    self.max_history, self.sigma_n, self.sigma_p, params=p, stream=s)
+            else:
+                oS.copy_(S); oQ.copy_(Q); ok.copy_(k)
+            self.prev_camera = cam
+            if self.prev_xyzr.shape[0]:
+                get_spheres(raw, self.prev_xyzr, stream=s)
+            if self.prev_verts.shape[0]:
+                get_triangles(raw, self.prev_verts, stream=s)
+            self.slot, self.have_history = new, True
+            self.frame_index += 1
+            if denoise_iterations:
+                denoise(self.filtered, oS, oQ, ok, self.features[new], w, h, self.work, int(denoise_iterations), DENOISE_SIGMA_C, self.sigma_n,
+                        self.sigma_p, params=p, stream=s)
+                finalize(self.image, self.filtered, w, h, 1, params=p, stream=s)
+            else:
+                finalize_counts(self.image, oS, ok, w, h, params=p, stream=s)
+        return self.image, oS, oQ, ok
 
 
 def pack_rays(origins, dirs, tmax=float("inf")):

@@ -427,6 +427,38 @@ int mirt_scene_update_triangles(MirtScene* sc, const void* d_verts, int first, i
   return update_triangles(sc, d_verts, first, count, (hipStream_t)stream);
 }
 
+int mirt_scene_get_spheres(MirtScene* sc, int first, int count, void* d_xyzr_out, void* stream)
+{
+  if (!sc) { set_error("mirt_scene_get_spheres: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return get_spheres(sc, first, count, d_xyzr_out, (hipStream_t)stream);
+}
+
+int mirt_scene_get_triangles(MirtScene* sc, int first, int count, void* d_verts_out, void* stream)
+{
+  if (!sc) { set_error("mirt_scene_get_triangles: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return get_triangles(sc, first, count, d_verts_out, (hipStream_t)stream);
+}
+
+int mirt_prev_features(MirtScene* sc, const void* d_rays, const void* d_hits, int64_t n, const void* d_prev_xyzr, const void* d_prev_verts,
+                       void* d_features, void* stream)
+{
+  if (!sc) { set_error("mirt_prev_features: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return prev_features(sc, d_rays, d_hits, n, d_prev_xyzr, d_prev_verts, d_features, (hipStream_t)stream);
+}
+
+int mirt_temporal_accumulate(const MirtRenderParams* p, const MirtCamera* prev_camera, const void* d_accum_f32, const void* d_accum_sq_f32,
+                             const uint32_t* d_counts, const void* d_prev_features, const void* d_hist_accum_f32, const void* d_hist_accum_sq_f32,
+                             const uint32_t* d_hist_counts, const void* d_hist_features, int max_history, float sigma_n, float sigma_p,
+                             void* d_out_accum_f32, void* d_out_accum_sq_f32, uint32_t* d_out_counts, void* stream)
+{
+  if (!p || !prev_camera) { set_error("mirt_temporal_accumulate: null argument"); return MIRT_ERR_ARG; }
+  return temporal_accumulate(p, prev_camera, d_accum_f32, d_accum_sq_f32, d_counts, d_prev_features, d_hist_accum_f32, d_hist_accum_sq_f32, d_hist_counts,
+                             d_hist_features, max_history, sigma_n, sigma_p, d_out_accum_f32, d_out_accum_sq_f32, d_out_counts, (hipStream_t)stream);
+}
+
 int mirt_get_stats(MirtScene* sc, MirtStats* out)
 {
   if (!sc || !out) { set_error("mirt_get_stats: null argument"); return MIRT_ERR_ARG; }

@@ -332,6 +332,15 @@ int denoise(const MirtRenderParams* p, const void* d_accum, const void* d_accum_
 // update.hip
 int update_spheres(MirtScene* sc, const void* d_spheres, int first, int count, hipStream_t stream);
 int update_triangles(MirtScene* sc, const void* d_verts, int first, int count, hipStream_t stream);
+// temporal.hip
+int get_spheres(MirtScene* sc, int first, int count, void* d_xyzr_out, hipStream_t stream);
+int get_triangles(MirtScene* sc, int first, int count, void* d_verts_out, hipStream_t stream);
+int prev_features(MirtScene* sc, const void* d_rays, const void* d_hits, int64_t n, const void* d_prev_xyzr, const void* d_prev_verts, void* d_features,
+                  hipStream_t stream);
+int temporal_accumulate(const MirtRenderParams* p, const MirtCamera* prev_camera, const void* d_accum, const void* d_accum_sq, const uint32_t* d_counts,
+                        const void* d_prev_features, const void* d_hist_accum, const void* d_hist_accum_sq, const uint32_t* d_hist_counts,
+                        const void* d_hist_features, int max_history, float sigma_n, float sigma_p, void* d_out_accum, void* d_out_accum_sq,
+                        uint32_t* d_out_counts, hipStream_t stream);
 // wavefront.hip
 int wavefront_trace(MirtScene* sc, RenderCtx& cx, RenderArgs& a, bool count, hipStream_t stream, float* trace_ms);
 }

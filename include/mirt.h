@@ -360,6 +360,87 @@ int mirt_scene_set_camera(MirtScene* sc, const MirtCamera* cam);
  * with count > 0. */
 int mirt_scene_update_spheres(MirtScene* sc, const void* d_spheres, int first, int count, void* stream);
 int mirt_scene_update_triangles(MirtScene* sc, const void* d_verts, int first, int count, void* stream);
+/* The inverse of the two update calls, device to device: spheres / triangles first .. first+count-1 of the scene's file-order
+ * arrays into d_xyzr_out (float [count][4] = cx, cy, cz, r; 16-byte aligned) / d_verts_out (float [count][9] = p0, p1, p2; 4-byte
+ * aligned), as mirt_scene_create or the last update left them.  One kernel, one lane per primitive, asynchronous on `stream`
+ * (ordering it behind an update issued on another stream is the caller's duty).  Legal whether or not the scene is built, and
+ * that state does not change; nothing but the arrays is read.  count 0: MIRT_OK, nothing launched.  MIRT_ERR_ARG as for the
+ * updates: null scene, negative first or count, a range beyond num_spheres / num_triangles, a null or misaligned pointer with
+ * count > 0. */
+int mirt_scene_get_spheres(MirtScene* sc, int first, int count, void* d_xyzr_out, void* stream);
+int mirt_scene_get_triangles(MirtScene* sc, int first, int count, void* d_verts_out, void* stream);
+
+/* ---- temporal accumulation: the previous frame's samples, reused by reprojection --------------------- */
+/* Not in the reference (every frame starts from nothing).  Callers detect the feature by these symbols (MIRT_VERSION stays 3).
+ * Both calls are asynchronous on `stream`, take device pointers only, allocate nothing, never synchronise, use no atomics and
+ * touch no render context, MirtStats counter or hand-out table.  Arithmetic as for mirt_denoise: float32, one IEEE rounding per
+ * operation (no fused multiply-add), a + b + c = (a + b) + c, dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z, length(u) =
+ * sqrtf(dot(u, u)), normalize as mirt_trace_rays normalises (vec3.cuh:72-82), cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z,
+ * a.x b.y - a.y b.x) with each product rounded, then the difference; a vector times or divided by a scalar works per component.
+ *
+ * mirt_prev_features: where was the surface point each ray hits now, one frame ago?  n MirtRay rows, the n MirtHit rows a
+ * closest-hit mirt_trace_rays answered for them on the scene as it is now (built: MIRT_ERR_STATE otherwise), and the geometry
+ * before it moved: d_prev_xyzr (float [num_spheres][4], 16-byte aligned) and d_prev_verts (float [num_triangles][9], 4-byte
+ * aligned), whole arrays in the update calls' format -- mirt_scene_get_spheres / mirt_scene_get_triangles taken before the
+ * updates -- either may be NULL: that kind did not move.  -> n rows of mirt_hit_features' layout, (Px, Py, Pz, hit) (nx, ny, nz, 0),
+ * two 16-byte stores each.  One lane per row.  With P = o + t * normalize(d) (the product rounded, then the sum) and n the record's
+ * normal, exactly as mirt_hit_features computes them:
+ *     kind == MIRT_HIT_NONE: eight zeros
+ *     MIRT_HIT_SPHERE with d_prev_xyzr, MIRT_HIT_TRIANGLE with d_prev_verts: id >= the scene's count of that kind gives eight zeros
+ *         (the hit tensor is the caller's memory); otherwise
+ *       sphere id:   (c, r) = the scene's sphere, (c', r') = d_prev_xyzr[id]:  P' = c' + ((P - c) / r) * r';  n' = n
+ *       triangle id: p0, nor, e1, e2 = the scene's 48-byte record (object.cuh:177-191), p0', p1', p2' = d_prev_verts[id]:
+ *                    v = P - p0;  b1 = dot(e1, v);  b2 = dot(e2, v)   -- the reference's barycentrics, the coefficients of p1 - p0
+ *                    and p2 - p0;  d1 = p1' - p0';  d2 = p2' - p0';  P' = (p0' + b1 * d1) + b2 * d2;
+ *                    m = normalize(cross(d1, d2));  n' = dot(n, nor) < 0 ? -m : m   -- the query faces normals to the ray; the
+ *                    previous normal keeps that choice
+ *       row = (P', 1, n', 0)
+ *     every other record (a plane, a kind whose previous array is NULL, an unknown kind): (P, 1, n, 0)
+ * n == 0: MIRT_OK, nothing launched.  MIRT_ERR_ARG: null scene, n < 0, a null d_rays / d_hits / d_features with n > 0, a
+ * misaligned buffer. */
+int mirt_prev_features(MirtScene* sc, const void* d_rays, const void* d_hits, int64_t n, const void* d_prev_xyzr, const void* d_prev_verts,
+                       void* d_features, void* stream);
+/* mirt_temporal_accumulate: the frame p describes (width x height, row-major, N = width * height pixels; p->spp, stripe_rows and
+ * flags are not used), on the current device.  This frame's moments S, Q (float4 per pixel), k (uint32 per pixel) as
+ * mirt_render_accumulate_pixels leaves them; G = d_prev_features: mirt_prev_features of this frame's pixels' rays; the previous
+ * merged frame S^h, Q^h, k^h = d_hist_*; F^h = d_hist_features: mirt_hit_features of that frame's rays; prev_camera: that frame's
+ * camera.  -> d_out_*: moments of the same format holding this frame's samples plus the history that survives, so
+ * mirt_denoise, mirt_select_pixels and mirt_finalize_counts take them as they are.  With eye, forward, right, up of prev_camera,
+ * max_dim = fmaxf((float)width, (float)height), pixel p:
+ *   1. No history -- out = (S_p, Q_p, k_p), bit for bit -- when G_p[3] == 0 (a miss), or f below is not finite or f <= 0, or no
+ *      tap is valid.
+ *   2. P' = G_p[0..2], n' = G_p[4..6];  v = P' - eye;  f = dot(v, forward) / dot(forward, forward);
+ *      sx = dot(v, right) / dot(right, right) / f;  sy = dot(v, up) / dot(up, up) / f;
+ *      x = (sx * max_dim + (float)width) / 2;  y = ((float)height - sy * max_dim) / 2
+ *      -- the inverse of the pinhole ray forward + sx right + sy up with sx = (2 x - width) / max_dim, sy = (height - 2 y) /
+ *      max_dim, in which integer coordinates are pixel centres -- exact for a mutually orthogonal forward / right / up;
+ *      otherwise the position is approximate and step 4 rejects what lands wrong.
+ *   3. Snap: |x - rintf(x)| <= 1/1024 gives x = rintf(x); y likewise.  x0 = floorf(x), tx = x - x0, y0, ty likewise.  Taps
+ *      q = (x0 + i, y0 + j), j = 0, 1 (outer), i = 0, 1 (inner), weight w = wx_i * wy_j, wx = (1 - tx, tx), wy = (1 - ty, ty).
+ *      A tap outside the frame or with w == 0 is dropped.
+ *   4. A tap is valid when k^h_q > 0, S^h_q and Q^h_q are finite in r, g and b, F^h_q[3] != 0 (a hit), and a_n + a_p <= 1:
+ *          c = 1 - dot(n', n_q);  a_n = (c < 0 ? 0 : c) / sigma_n
+ *          D = P_q - P';  foot = length(v) * 2 / max_dim   -- one pixel's footprint at that distance
+ *          a_p = fabsf(dot(n', D)) / (sigma_p * fmaxf(length(D), foot))
+ *      -- mirt_denoise's a_n and a_p, but a displacement below a pixel's footprint is measured against the footprint: the
+ *      rounding noise between a recomputed P' and a stored P_q is not a direction.  A NaN in either term makes the tap invalid.
+ *   5. A valid tap with w == 1 (both axes snapped; the other taps had weight 0): S_h = S^h_q, Q_h = Q^h_q, k_h = k^h_q as they
+ *      are.  Otherwise sw = the sum of w over the valid taps in tap order, and over the valid taps in tap order, from 0,
+ *          m_ch = m_ch + (w / sw) * (S^h_q.ch / (float)k^h_q);  s_ch = s_ch + (w / sw) * (Q^h_q.ch / (float)k^h_q)   (r, g, b, a)
+ *      k_h = the smallest k^h_q of the valid taps;  S_h = m * (float)k_h;  Q_h = s * (float)k_h.
+ *   6. Cap: k_h > max_history:  c = (float)max_history / (float)k_h;  S_h = S_h * c;  Q_h = Q_h * c;  k_h = max_history.
+ *   7. out = (S_p + S_h, Q_p + Q_h, k_p + k_h), all four channels.
+ * A lane reads S_p, Q_p, k_p at its own pixel only and before it writes: each output may be EXACTLY its own current-frame buffer
+ * (d_out_accum_f32 == d_accum_f32, ...).  Every pixel depends on its inputs only: the result does not depend on timing.
+ * MIRT_ERR_ARG (all checked on the host, before any device work): a null pointer; p->num_parts != 1 (whole frames only);
+ * prev_camera not a pinhole (fisheye, panorama or dof_focus not 0); max_history < 1; sigma_n or sigma_p not finite and
+ * positive (the drivers use MIRT_DENOISE_SIGMA_N and MIRT_DENOISE_SIGMA_P: no new constant); a misaligned buffer (16 bytes;
+ * counts 4); an output range (16 N, 16 N, 4 N bytes) overlapping another output, d_prev_features or a history buffer (32 N, 16 N,
+ * 16 N, 4 N, 32 N), or a current-frame buffer in any way but the one allowed above. */
+int mirt_temporal_accumulate(const MirtRenderParams* p, const MirtCamera* prev_camera, const void* d_accum_f32, const void* d_accum_sq_f32,
+                             const uint32_t* d_counts, const void* d_prev_features, const void* d_hist_accum_f32, const void* d_hist_accum_sq_f32,
+                             const uint32_t* d_hist_counts, const void* d_hist_features, int max_history, float sigma_n, float sigma_p,
+                             void* d_out_accum_f32, void* d_out_accum_sq_f32, uint32_t* d_out_counts, void* stream);
 
 /* ---- several GPUs in one process --------------------------------------------------------------- */
 /* Not in the reference (single GPU, main.cu:25-94).  The scene is uploaded to every listed device and every device builds

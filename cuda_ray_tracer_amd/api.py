@@ -393,8 +393,7 @@ class MultiGpu:
         out = np.zeros((height, width, 4), np.uint8)
         st = MultiStats()
         _check(lib().mirt_render_frame_multi(self._h, width, height, spp, stripe_rows, out.ctypes.data, C.byref(st)))
-        n = st.num_gpus
-        return out, dict(num_gpus=n, build_ms=st.build_ms, render_ms=list(st.render_ms)[:n], gather_ms=st.gather_ms, frame_ms=st.frame_ms)
+        return out, self._stats(st)
 
     @staticmethod
     def _stats(st):
@@ -451,6 +450,50 @@ def _stream_ptr(stream):
     return C.c_void_p(int(stream))
 
 
+def _ptr(x):
+    """A tensor's device address (or an int that is one) as a void* argument; None and an empty tensor give NULL."""
+    if x is None:
+        return None
+    if not hasattr(x, "data_ptr"):
+        return C.c_void_p(int(x)) if int(x) else None
+    return C.c_void_p(x.data_ptr()) if x.numel() else None
+
+
+def _tensor(x, name, dtypes, shape=None, numel=None):
+    """ValueError unless x is a contiguous torch tensor of one of the dtypes, of `shape` (a list; None stands for any size, as in
+    [None, 8]) or, without a shape, of `numel` elements in any shape."""
+    import torch
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor")
+    if x.dtype not in dtypes:
+        raise ValueError(f"{name} has dtype {x.dtype}; expected one of {[str(d) for d in dtypes]}")
+    if shape is not None:
+        if x.dim() != len(shape) or any(want is not None and have != want for have, want in zip(x.shape, shape)):
+            raise ValueError(f"{name} has shape {list(x.shape)}; expected [{', '.join('n' if k is None else str(k) for k in shape)}]")
+    elif x.numel() != numel:
+        raise ValueError(f"{name} has shape {list(x.shape)}; expected {numel} elements")
+    if not x.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def _on_device(tensors, device=None):
+    """ValueError unless every (tensor, name) is on cuda device `device` (None: on the device of the first).  Returns its index."""
+    import torch
+    for x, name in tensors:
+        index = None
+        if x.device.type == "cuda":
+            index = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        if index is None or (device is not None and index != device):
+            raise ValueError(f"{name} is on {x.device}; expected " + ("a cuda device" if device is None else f"cuda:{device}"))
+        device = index
+    return device
+
+
+def _f32():
+    import torch
+    return (torch.float32,)
+
+
 def build_lbvh_karas(raw, morton_bits=30, stream=None):
     """build_lbvh_karas(RawConfig&, int morton_bits = 30), lbvh_builder.cu:401-521.  morton_bits is accepted and
     ignored exactly as in the reference (10 bits per axis are hard-coded there, lbvh_utils.cu:84)."""
@@ -484,53 +527,29 @@ def render(d_image, img_width, img_height, aa, raw, d_float=None, params=None, s
     params : optional RenderParams selecting one part of a striped frame (multi-GPU); default = whole frame.
     Asynchronous on `stream` (default: torch's current stream)."""
     p = params if params is not None else render_params(img_width, img_height, aa)
-    img_ptr = d_image.data_ptr() if hasattr(d_image, "data_ptr") else int(d_image)
-    f_ptr = None
-    if d_float is not None:
-        f_ptr = d_float.data_ptr() if hasattr(d_float, "data_ptr") else int(d_float)
-    _check(lib().mirt_render(raw._h, C.byref(p), C.c_void_p(img_ptr), C.c_void_p(f_ptr) if f_ptr else None, _stream_ptr(stream)))
+    _check(lib().mirt_render(raw._h, C.byref(p), _ptr(d_image), _ptr(d_float), _stream_ptr(stream)))
 
 
 def render_accumulate(d_accum, img_width, img_height, sample_first, sample_count, raw, params=None, stream=None):
     """render_kernel_atomic_aa, draw.cu:49-92: adds samples [sample_first, sample_first + sample_count) of every pixel to the
     float32 accumulation buffer d_accum (num_pixels * 4, zeroed by the caller before the first call)."""
     p = params if params is not None else render_params(img_width, img_height, max(sample_first + sample_count, 2))
-    _check(lib().mirt_render_accumulate(raw._h, C.byref(p), C.c_void_p(d_accum.data_ptr()), int(sample_first), int(sample_count), _stream_ptr(stream)))
+    _check(lib().mirt_render_accumulate(raw._h, C.byref(p), _ptr(d_accum), int(sample_first), int(sample_count), _stream_ptr(stream)))
 
 
 def finalize(d_image, d_accum, img_width, img_height, total_samples, params=None, stream=None):
     """finalize_kernel, draw.cu:13-47: mean over total_samples, sRGB, 8-bit with rounding."""
     p = params if params is not None else render_params(img_width, img_height, max(total_samples, 2))
-    _check(lib().mirt_finalize(C.byref(p), C.c_void_p(d_accum.data_ptr()), int(total_samples), C.c_void_p(d_image.data_ptr()), _stream_ptr(stream)))
+    _check(lib().mirt_finalize(C.byref(p), _ptr(d_accum), int(total_samples), _ptr(d_image), _stream_ptr(stream)))
 
 
 def scatter_part(params, d_part, d_frame, stream=None):
-    _check(lib().mirt_scatter_part(C.byref(params), C.c_void_p(d_part.data_ptr()), C.c_void_p(d_frame.data_ptr()), _stream_ptr(stream)))
+    _check(lib().mirt_scatter_part(C.byref(params), _ptr(d_part), _ptr(d_frame), _stream_ptr(stream)))
 
 
 # ------------------------------------------------------------------------------------------------------
 # Ray queries (mirt_trace_rays / mirt_camera_rays): rays are float32 [n, 8] tensors (MirtRay), hits 4-byte [n, 6] tensors (MirtHit)
 # ------------------------------------------------------------------------------------------------------
-def _query_layout(x, name, dtypes, cols, rows):
-    """ValueError unless x is a contiguous [rows, cols] tensor of one of the dtypes."""
-    import torch
-    if not isinstance(x, torch.Tensor):
-        raise ValueError(f"{name} must be a torch tensor")
-    if x.dtype not in dtypes:
-        raise ValueError(f"{name} has dtype {x.dtype}; expected one of {[str(d) for d in dtypes]}")
-    if x.dim() != 2 or x.shape[1] != cols or (rows is not None and x.shape[0] != rows):
-        raise ValueError(f"{name} has shape {list(x.shape)}; expected [{rows if rows is not None else 'n'}, {cols}]")
-    if not x.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-
-
-def _query_device(x, name, raw):
-    """ValueError unless x is on the scene's device."""
-    import torch
-    if x.device.type != "cuda" or (x.device.index if x.device.index is not None else torch.cuda.current_device()) != raw.device:
-        raise ValueError(f"{name} is on {x.device}; the scene is on cuda:{raw.device}")
-
-
 def _hit_dtypes():
     import torch
     return tuple(d for d in (torch.float32, torch.int32, getattr(torch, "uint32", None)) if d is not None)
@@ -540,25 +559,21 @@ def trace_rays(raw, d_rays, d_hits, any_hit=False, stream=None):
     """mirt_trace_rays: closest hit (hitNearest, draw.cu:292-318) or, with any_hit, occlusion of every ray of d_rays (float32
     [n, 8], MirtRay rows: pack_rays) into d_hits (a 4-byte dtype, [n, 6], MirtHit rows: unpack_hits).  Both contiguous and on
     the scene's device.  Asynchronous on `stream` (default: torch's current stream)."""
-    import torch
-    _query_layout(d_rays, "d_rays", (torch.float32,), 8, None)
-    _query_layout(d_hits, "d_hits", _hit_dtypes(), 6, d_rays.shape[0])
-    _query_device(d_rays, "d_rays", raw)
-    _query_device(d_hits, "d_hits", raw)
+    _tensor(d_rays, "d_rays", _f32(), [None, 8])
     n = d_rays.shape[0]
-    _check(lib().mirt_trace_rays(raw._h, C.c_void_p(d_rays.data_ptr()) if n else None, n, C.c_void_p(d_hits.data_ptr()) if n else None,
-                                 MIRT_QUERY_ANY_HIT if any_hit else 0, _stream_ptr(stream)))
+    _tensor(d_hits, "d_hits", _hit_dtypes(), [n, 6])
+    _on_device(((d_rays, "d_rays"), (d_hits, "d_hits")), raw.device)
+    _check(lib().mirt_trace_rays(raw._h, _ptr(d_rays), n, _ptr(d_hits), MIRT_QUERY_ANY_HIT if any_hit else 0, _stream_ptr(stream)))
 
 
 def camera_rays(raw, d_rays, img_width, img_height, aa, params=None, stream=None):
     """mirt_camera_rays: the primary ray of sample 0 of every pixel of the frame (or of the part `params` selects), in the order
     render writes pixels, into d_rays (float32 [num_pixels, 8], contiguous, on the scene's device).  trace_rays of these rays
     gives the render's primary hits."""
-    import torch
     p = params if params is not None else render_params(img_width, img_height, aa)
-    _query_layout(d_rays, "d_rays", (torch.float32,), 8, num_pixels(p))
-    _query_device(d_rays, "d_rays", raw)
-    _check(lib().mirt_camera_rays(raw._h, C.byref(p), C.c_void_p(d_rays.data_ptr()), _stream_ptr(stream)))
+    _tensor(d_rays, "d_rays", _f32(), [num_pixels(p), 8])
+    _on_device(((d_rays, "d_rays"),), raw.device)
+    _check(lib().mirt_camera_rays(raw._h, C.byref(p), _ptr(d_rays), _stream_ptr(stream)))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -568,22 +583,18 @@ def update_spheres(raw, d_xyzr, first=0, stream=None):
     """mirt_scene_update_spheres: spheres first .. first+n-1 (file order) take cx, cy, cz, r from d_xyzr (float32 [n, 4],
     contiguous, on the scene's device).  Asynchronous on `stream` (default: torch's current stream); the scene is not built
     until the next build_lbvh_karas (n = 0 changes nothing)."""
-    import torch
-    _query_layout(d_xyzr, "d_xyzr", (torch.float32,), 4, None)
-    _query_device(d_xyzr, "d_xyzr", raw)
-    n = d_xyzr.shape[0]
-    _check(lib().mirt_scene_update_spheres(raw._h, C.c_void_p(d_xyzr.data_ptr()) if n else None, int(first), n, _stream_ptr(stream)))
+    _tensor(d_xyzr, "d_xyzr", _f32(), [None, 4])
+    _on_device(((d_xyzr, "d_xyzr"),), raw.device)
+    _check(lib().mirt_scene_update_spheres(raw._h, _ptr(d_xyzr), int(first), d_xyzr.shape[0], _stream_ptr(stream)))
 
 
 def update_triangles(raw, d_verts, first=0, stream=None):
     """mirt_scene_update_triangles: triangles first .. first+n-1 (file order) take p0, p1, p2 from d_verts (float32 [n, 9],
     contiguous, on the scene's device); nor, e1 and e2 are computed on the device as the parser computes them
     (object.cuh:177-191).  Asynchronous on `stream`; the scene is not built until the next build_lbvh_karas."""
-    import torch
-    _query_layout(d_verts, "d_verts", (torch.float32,), 9, None)
-    _query_device(d_verts, "d_verts", raw)
-    n = d_verts.shape[0]
-    _check(lib().mirt_scene_update_triangles(raw._h, C.c_void_p(d_verts.data_ptr()) if n else None, int(first), n, _stream_ptr(stream)))
+    _tensor(d_verts, "d_verts", _f32(), [None, 9])
+    _on_device(((d_verts, "d_verts"),), raw.device)
+    _check(lib().mirt_scene_update_triangles(raw._h, _ptr(d_verts), int(first), d_verts.shape[0], _stream_ptr(stream)))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -595,56 +606,30 @@ def _int_dtypes():
     return tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
 
 
-def _flat_layout(x, name, dtypes, numel):
-    """ValueError unless x is a contiguous tensor of one of the dtypes with `numel` elements (None: one-dimensional, any length)."""
-    import torch
-    if not isinstance(x, torch.Tensor):
-        raise ValueError(f"{name} must be a torch tensor")
-    if x.dtype not in dtypes:
-        raise ValueError(f"{name} has dtype {x.dtype}; expected one of {[str(d) for d in dtypes]}")
-    if numel is None:
-        if x.dim() != 1:
-            raise ValueError(f"{name} has shape {list(x.shape)}; expected [n]")
-    elif x.numel() != numel:
-        raise ValueError(f"{name} has shape {list(x.shape)}; expected {numel} elements")
-    if not x.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-
-
-def _same_device(x, name, device):
-    import torch
-    index = x.device.index if x.device.index is not None else (torch.cuda.current_device() if x.device.type == "cuda" else None)
-    if x.device.type != "cuda" or index != device:
-        raise ValueError(f"{name} is on {x.device}; expected cuda:{device}")
-
-
 def render_accumulate_pixels(raw, d_accum, img_width, img_height, sample_first, sample_count, pixels=None, d_accum_sq=None, d_counts=None,
                              params=None, stream=None):
     """mirt_render_accumulate_pixels: render_accumulate for the pixels of `pixels` (int32 / uint32 [n], distinct local pixel
     indices, any order; None: every pixel), adding as well the squared samples to d_accum_sq and sample_count to d_counts (both
     optional).  Unlisted pixels are neither traced nor written.  Asynchronous on `stream` (default: torch's current stream)."""
-    import torch
     p = params if params is not None else render_params(img_width, img_height, max(sample_first + sample_count, 2))
     n = num_pixels(p)
-    _flat_layout(d_accum, "d_accum", (torch.float32,), 4 * n)
-    _query_device(d_accum, "d_accum", raw)
+    _tensor(d_accum, "d_accum", _f32(), numel=4 * n)
+    _on_device(((d_accum, "d_accum"),), raw.device)
     if d_accum_sq is not None:
-        _flat_layout(d_accum_sq, "d_accum_sq", (torch.float32,), 4 * n)
-        _query_device(d_accum_sq, "d_accum_sq", raw)
+        _tensor(d_accum_sq, "d_accum_sq", _f32(), numel=4 * n)
+        _on_device(((d_accum_sq, "d_accum_sq"),), raw.device)
     if d_counts is not None:
-        _flat_layout(d_counts, "d_counts", _int_dtypes(), n)
-        _query_device(d_counts, "d_counts", raw)
+        _tensor(d_counts, "d_counts", _int_dtypes(), numel=n)
+        _on_device(((d_counts, "d_counts"),), raw.device)
     listed = 0
     if pixels is not None:
-        _flat_layout(pixels, "pixels", _int_dtypes(), None)
-        _query_device(pixels, "pixels", raw)
+        _tensor(pixels, "pixels", _int_dtypes(), [None])
+        _on_device(((pixels, "pixels"),), raw.device)
         listed = pixels.shape[0]
         if listed == 0:      # (an empty tensor has no address to pass: an empty list renders nothing)
             return
-    _check(lib().mirt_render_accumulate_pixels(raw._h, C.byref(p), C.c_void_p(pixels.data_ptr()) if pixels is not None else None, listed,
-                                               C.c_void_p(d_accum.data_ptr()), C.c_void_p(d_accum_sq.data_ptr()) if d_accum_sq is not None else None,
-                                               C.c_void_p(d_counts.data_ptr()) if d_counts is not None else None, int(sample_first), int(sample_count),
-                                               _stream_ptr(stream)))
+    _check(lib().mirt_render_accumulate_pixels(raw._h, C.byref(p), _ptr(pixels), listed, _ptr(d_accum), _ptr(d_accum_sq), _ptr(d_counts),
+                                               int(sample_first), int(sample_count), _stream_ptr(stream)))
 
 
 def select_pixels(d_accum, d_accum_sq, d_counts, img_width, img_height, min_samples, max_samples, max_variance, d_pixels_out, d_num_out,
@@ -655,20 +640,15 @@ def select_pixels(d_accum, d_accum_sq, d_counts, img_width, img_height, min_samp
     import torch
     p = params if params is not None else render_params(img_width, img_height, 2)
     n = num_pixels(p)
-    _flat_layout(d_accum, "d_accum", (torch.float32,), 4 * n)
-    _flat_layout(d_accum_sq, "d_accum_sq", (torch.float32,), 4 * n)
-    _flat_layout(d_counts, "d_counts", _int_dtypes(), n)
-    _flat_layout(d_pixels_out, "d_pixels_out", _int_dtypes(), n)
-    _flat_layout(d_num_out, "d_num_out", _int_dtypes(), 1)
-    if d_accum.device.type != "cuda":
-        raise ValueError(f"d_accum is on {d_accum.device}; expected a cuda device")
-    device = d_accum.device.index if d_accum.device.index is not None else torch.cuda.current_device()
-    for x, name in ((d_accum_sq, "d_accum_sq"), (d_counts, "d_counts"), (d_pixels_out, "d_pixels_out"), (d_num_out, "d_num_out")):
-        _same_device(x, name, device)
+    _tensor(d_accum, "d_accum", _f32(), numel=4 * n)
+    _tensor(d_accum_sq, "d_accum_sq", _f32(), numel=4 * n)
+    _tensor(d_counts, "d_counts", _int_dtypes(), numel=n)
+    _tensor(d_pixels_out, "d_pixels_out", _int_dtypes(), numel=n)
+    _tensor(d_num_out, "d_num_out", _int_dtypes(), numel=1)
+    device = _on_device(((d_accum, "d_accum"), (d_accum_sq, "d_accum_sq"), (d_counts, "d_counts"), (d_pixels_out, "d_pixels_out"), (d_num_out, "d_num_out")))
     with torch.cuda.device(device):
-        _check(lib().mirt_select_pixels(C.byref(p), C.c_void_p(d_accum.data_ptr()), C.c_void_p(d_accum_sq.data_ptr()), C.c_void_p(d_counts.data_ptr()),
-                                        int(min_samples), int(max_samples), float(max_variance), C.c_void_p(d_pixels_out.data_ptr()),
-                                        C.c_void_p(d_num_out.data_ptr()), _stream_ptr(stream)))
+        _check(lib().mirt_select_pixels(C.byref(p), _ptr(d_accum), _ptr(d_accum_sq), _ptr(d_counts), int(min_samples), int(max_samples),
+                                        float(max_variance), _ptr(d_pixels_out), _ptr(d_num_out), _stream_ptr(stream)))
 
 
 def finalize_counts(d_image, d_accum, d_counts, img_width, img_height, params=None, stream=None):
@@ -676,17 +656,12 @@ def finalize_counts(d_image, d_accum, d_counts, img_width, img_height, params=No
     import torch
     p = params if params is not None else render_params(img_width, img_height, 2)
     n = num_pixels(p)
-    _flat_layout(d_image, "d_image", (torch.uint8,), 4 * n)
-    _flat_layout(d_accum, "d_accum", (torch.float32,), 4 * n)
-    _flat_layout(d_counts, "d_counts", _int_dtypes(), n)
-    if d_accum.device.type != "cuda":
-        raise ValueError(f"d_accum is on {d_accum.device}; expected a cuda device")
-    device = d_accum.device.index if d_accum.device.index is not None else torch.cuda.current_device()
-    _same_device(d_image, "d_image", device)
-    _same_device(d_counts, "d_counts", device)
+    _tensor(d_image, "d_image", (torch.uint8,), numel=4 * n)
+    _tensor(d_accum, "d_accum", _f32(), numel=4 * n)
+    _tensor(d_counts, "d_counts", _int_dtypes(), numel=n)
+    device = _on_device(((d_accum, "d_accum"), (d_image, "d_image"), (d_counts, "d_counts")))
     with torch.cuda.device(device):
-        _check(lib().mirt_finalize_counts(C.byref(p), C.c_void_p(d_accum.data_ptr()), C.c_void_p(d_counts.data_ptr()), C.c_void_p(d_image.data_ptr()),
-                                          _stream_ptr(stream)))
+        _check(lib().mirt_finalize_counts(C.byref(p), _ptr(d_accum), _ptr(d_counts), _ptr(d_image), _stream_ptr(stream)))
 
 
 def render_adaptive(raw, width, height, min_spp, max_spp, step, max_variance, params=None, stream=None):
@@ -736,15 +711,12 @@ def hit_features(raw, d_rays, d_hits, d_features, stream=None):
     """mirt_hit_features: rays (float32 [n, 8]) and their closest-hit records (a 4-byte dtype, [n, 6]) -> d_features (float32
     [n, 8]): hit point and hit flag, normal and 0; a miss gives a zero row.  All contiguous and on the scene's device.
     Asynchronous on `stream` (default: torch's current stream)."""
-    import torch
-    _query_layout(d_rays, "d_rays", (torch.float32,), 8, None)
+    _tensor(d_rays, "d_rays", _f32(), [None, 8])
     n = d_rays.shape[0]
-    _query_layout(d_hits, "d_hits", _hit_dtypes(), 6, n)
-    _query_layout(d_features, "d_features", (torch.float32,), 8, n)
-    for x, name in ((d_rays, "d_rays"), (d_hits, "d_hits"), (d_features, "d_features")):
-        _query_device(x, name, raw)
-    _check(lib().mirt_hit_features(raw._h, C.c_void_p(d_rays.data_ptr()) if n else None, C.c_void_p(d_hits.data_ptr()) if n else None, n,
-                                   C.c_void_p(d_features.data_ptr()) if n else None, _stream_ptr(stream)))
+    _tensor(d_hits, "d_hits", _hit_dtypes(), [n, 6])
+    _tensor(d_features, "d_features", _f32(), [n, 8])
+    _on_device(((d_rays, "d_rays"), (d_hits, "d_hits"), (d_features, "d_features")), raw.device)
+    _check(lib().mirt_hit_features(raw._h, _ptr(d_rays), _ptr(d_hits), n, _ptr(d_features), _stream_ptr(stream)))
 
 
 def denoise_work_bytes(img_width, img_height, params=None):
@@ -765,26 +737,22 @@ def denoise(d_out, d_accum, d_accum_sq, d_counts, d_features, img_width, img_hei
     if p.num_parts != 1:
         raise ValueError("denoise works on whole frames: params.num_parts must be 1")
     n = num_pixels(p)
-    _flat_layout(d_out, "d_out", (torch.float32,), 4 * n)
-    _flat_layout(d_accum, "d_accum", (torch.float32,), 4 * n)
-    _flat_layout(d_accum_sq, "d_accum_sq", (torch.float32,), 4 * n)
-    _flat_layout(d_counts, "d_counts", _int_dtypes(), n)
-    _query_layout(d_features, "d_features", (torch.float32,), 8, n)
-    _flat_layout(d_work, "d_work", (torch.float32,), 10 * n)
+    _tensor(d_out, "d_out", _f32(), numel=4 * n)
+    _tensor(d_accum, "d_accum", _f32(), numel=4 * n)
+    _tensor(d_accum_sq, "d_accum_sq", _f32(), numel=4 * n)
+    _tensor(d_counts, "d_counts", _int_dtypes(), numel=n)
+    _tensor(d_features, "d_features", _f32(), [n, 8])
+    _tensor(d_work, "d_work", _f32(), numel=10 * n)
     if not 0 <= int(iterations) <= 8:
         raise ValueError(f"iterations is {iterations}; expected 0..8")
     for s, name in ((sigma_c, "sigma_c"), (sigma_n, "sigma_n"), (sigma_p, "sigma_p")):
         if not (0.0 < float(s) < float("inf")):
             raise ValueError(f"{name} is {s}; expected a finite positive number")
-    if d_accum.device.type != "cuda":
-        raise ValueError(f"d_accum is on {d_accum.device}; expected a cuda device")
-    device = d_accum.device.index if d_accum.device.index is not None else torch.cuda.current_device()
-    for x, name in ((d_out, "d_out"), (d_accum_sq, "d_accum_sq"), (d_counts, "d_counts"), (d_features, "d_features"), (d_work, "d_work")):
-        _same_device(x, name, device)
+    device = _on_device(((d_accum, "d_accum"), (d_out, "d_out"), (d_accum_sq, "d_accum_sq"), (d_counts, "d_counts"), (d_features, "d_features"),
+                         (d_work, "d_work")))
     with torch.cuda.device(device):
-        _check(lib().mirt_denoise(C.byref(p), C.c_void_p(d_accum.data_ptr()), C.c_void_p(d_accum_sq.data_ptr()), C.c_void_p(d_counts.data_ptr()),
-                                  C.c_void_p(d_features.data_ptr()), int(iterations), float(sigma_c), float(sigma_n), float(sigma_p),
-                                  C.c_void_p(d_work.data_ptr()), C.c_void_p(d_out.data_ptr()), _stream_ptr(stream)))
+        _check(lib().mirt_denoise(C.byref(p), _ptr(d_accum), _ptr(d_accum_sq), _ptr(d_counts), _ptr(d_features), int(iterations), float(sigma_c),
+                                  float(sigma_n), float(sigma_p), _ptr(d_work), _ptr(d_out), _stream_ptr(stream)))
 
 
 def denoise_frame(raw, accum, accum_sq, counts, width, height, spp, iterations=5, sigma_c=DENOISE_SIGMA_C, sigma_n=DENOISE_SIGMA_N,
@@ -818,43 +786,36 @@ def get_spheres(raw, d_xyzr, first=0, stream=None):
     """mirt_scene_get_spheres: cx, cy, cz, r of spheres first .. first+n-1 (file order) into d_xyzr (float32 [n, 4], contiguous,
     on the scene's device): what update_spheres was given, or the file's values.  Asynchronous on `stream`; the scene stays as
     built as it was."""
-    import torch
-    _query_layout(d_xyzr, "d_xyzr", (torch.float32,), 4, None)
-    _query_device(d_xyzr, "d_xyzr", raw)
-    n = d_xyzr.shape[0]
-    _check(lib().mirt_scene_get_spheres(raw._h, int(first), n, C.c_void_p(d_xyzr.data_ptr()) if n else None, _stream_ptr(stream)))
+    _tensor(d_xyzr, "d_xyzr", _f32(), [None, 4])
+    _on_device(((d_xyzr, "d_xyzr"),), raw.device)
+    _check(lib().mirt_scene_get_spheres(raw._h, int(first), d_xyzr.shape[0], _ptr(d_xyzr), _stream_ptr(stream)))
 
 
 def get_triangles(raw, d_verts, first=0, stream=None):
     """mirt_scene_get_triangles: p0, p1, p2 of triangles first .. first+n-1 (file order) into d_verts (float32 [n, 9], contiguous,
     on the scene's device).  Asynchronous on `stream`; the scene stays as built as it was."""
-    import torch
-    _query_layout(d_verts, "d_verts", (torch.float32,), 9, None)
-    _query_device(d_verts, "d_verts", raw)
-    n = d_verts.shape[0]
-    _check(lib().mirt_scene_get_triangles(raw._h, int(first), n, C.c_void_p(d_verts.data_ptr()) if n else None, _stream_ptr(stream)))
+    _tensor(d_verts, "d_verts", _f32(), [None, 9])
+    _on_device(((d_verts, "d_verts"),), raw.device)
+    _check(lib().mirt_scene_get_triangles(raw._h, int(first), d_verts.shape[0], _ptr(d_verts), _stream_ptr(stream)))
 
 
 def prev_features(raw, d_rays, d_hits, d_features, d_prev_xyzr=None, d_prev_verts=None, stream=None):
     """mirt_prev_features: hit_features' rows with the hit point and normal as they were in the previous geometry: d_prev_xyzr
     (float32 [num_spheres, 4]) and d_prev_verts (float32 [num_triangles, 9]) are get_spheres / get_triangles of the whole scene
     before it moved; None: that kind did not move.  All contiguous and on the scene's device.  Asynchronous on `stream`."""
-    import torch
-    _query_layout(d_rays, "d_rays", (torch.float32,), 8, None)
+    _tensor(d_rays, "d_rays", _f32(), [None, 8])
     n = d_rays.shape[0]
-    _query_layout(d_hits, "d_hits", _hit_dtypes(), 6, n)
-    _query_layout(d_features, "d_features", (torch.float32,), 8, n)
+    _tensor(d_hits, "d_hits", _hit_dtypes(), [n, 6])
+    _tensor(d_features, "d_features", _f32(), [n, 8])
     tensors = [(d_rays, "d_rays"), (d_hits, "d_hits"), (d_features, "d_features")]
     if d_prev_xyzr is not None:
-        _query_layout(d_prev_xyzr, "d_prev_xyzr", (torch.float32,), 4, raw.desc.num_spheres)
+        _tensor(d_prev_xyzr, "d_prev_xyzr", _f32(), [raw.desc.num_spheres, 4])
         tensors.append((d_prev_xyzr, "d_prev_xyzr"))
     if d_prev_verts is not None:
-        _query_layout(d_prev_verts, "d_prev_verts", (torch.float32,), 9, raw.desc.num_triangles)
+        _tensor(d_prev_verts, "d_prev_verts", _f32(), [raw.desc.num_triangles, 9])
         tensors.append((d_prev_verts, "d_prev_verts"))
-    for x, name in tensors:
-        _query_device(x, name, raw)
-    ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None and x.numel() else None
-    _check(lib().mirt_prev_features(raw._h, ptr(d_rays), ptr(d_hits), n, ptr(d_prev_xyzr), ptr(d_prev_verts), ptr(d_features), _stream_ptr(stream)))
+    _on_device(tensors, raw.device)
+    _check(lib().mirt_prev_features(raw._h, _ptr(d_rays), _ptr(d_hits), n, _ptr(d_prev_xyzr), _ptr(d_prev_verts), _ptr(d_features), _stream_ptr(stream)))
 
 
 def _is_pinhole(cam):
@@ -879,11 +840,11 @@ def temporal_accumulate(d_out_accum, d_out_accum_sq, d_out_counts, d_accum, d_ac
     counts = ((d_out_counts, "d_out_counts"), (d_counts, "d_counts"), (d_hist_counts, "d_hist_counts"))
     feats = ((d_prev_features, "d_prev_features"), (d_hist_features, "d_hist_features"))
     for x, name in moments:
-        _flat_layout(x, name, (torch.float32,), 4 * n)
+        _tensor(x, name, _f32(), numel=4 * n)
     for x, name in counts:
-        _flat_layout(x, name, _int_dtypes(), n)
+        _tensor(x, name, _int_dtypes(), numel=n)
     for x, name in feats:
-        _query_layout(x, name, (torch.float32,), 8, n)
+        _tensor(x, name, _f32(), [n, 8])
     if not isinstance(prev_camera, Camera):
         raise ValueError("prev_camera must be a Camera")
     if not _is_pinhole(prev_camera):
@@ -893,16 +854,11 @@ def temporal_accumulate(d_out_accum, d_out_accum_sq, d_out_counts, d_accum, d_ac
     for s, name in ((sigma_n, "sigma_n"), (sigma_p, "sigma_p")):
         if not (0.0 < float(s) < float("inf")):
             raise ValueError(f"{name} is {s}; expected a finite positive number")
-    if d_accum.device.type != "cuda":
-        raise ValueError(f"d_accum is on {d_accum.device}; expected a cuda device")
-    device = d_accum.device.index if d_accum.device.index is not None else torch.cuda.current_device()
-    for x, name in moments + counts + feats:
-        _same_device(x, name, device)
-    ptr = lambda x: C.c_void_p(x.data_ptr())
+    device = _on_device(((d_accum, "d_accum"),) + moments + counts + feats)
     with torch.cuda.device(device):
-        _check(lib().mirt_temporal_accumulate(C.byref(p), C.byref(prev_camera), ptr(d_accum), ptr(d_accum_sq), ptr(d_counts), ptr(d_prev_features),
-                                              ptr(d_hist_accum), ptr(d_hist_accum_sq), ptr(d_hist_counts), ptr(d_hist_features), int(max_history),
-                                              float(sigma_n), float(sigma_p), ptr(d_out_accum), ptr(d_out_accum_sq), ptr(d_out_counts),
+        _check(lib().mirt_temporal_accumulate(C.byref(p), C.byref(prev_camera), _ptr(d_accum), _ptr(d_accum_sq), _ptr(d_counts), _ptr(d_prev_features),
+                                              _ptr(d_hist_accum), _ptr(d_hist_accum_sq), _ptr(d_hist_counts), _ptr(d_hist_features), int(max_history),
+                                              float(sigma_n), float(sigma_p), _ptr(d_out_accum), _ptr(d_out_accum_sq), _ptr(d_out_counts),
                                               _stream_ptr(stream)))
 
 

@@ -1,5 +1,7 @@
-// Adaptive sampling (include/mirt.h, mirt_render_accumulate_pixels / mirt_select_pixels / mirt_finalize_counts; DESIGN.md
-// section 6e).  Not in the reference, whose progressive pair (draw.cu:13-92) adds the same samples to every pixel.
+// Accumulation buffers: what adds to them, selects from them and turns them into pixels (include/mirt.h, the resolve of
+// mirt_render_accumulate and mirt_render_accumulate_pixels, mirt_select_pixels, mirt_finalize, mirt_finalize_counts; DESIGN.md
+// section 6e).  The reference's progressive pair (draw.cu:13-92) adds the same samples to every pixel; the pixel lists, the second
+// moment and the per-pixel counts are not in it.
 //
 // compact_*_kernel   ordered stream compaction in three launches -- per-block counts (wave ballot + popcount), one block's
 //                    exclusive scan of the counts, scatter (ballot prefix inside a wave, wave offsets inside a block, the
@@ -9,10 +11,12 @@
 // sparse_table_kernel  the kept pixels -> RenderArgs::sample_order of the launch: position j * count + s of the hand-out is
 //                    launch sample (pixel - slab base) * count + s.  The trace kernels are the dense call's, untouched.
 // moments_tree_kernel / moments_kernel
-//                    the resolve of mirt_render_accumulate_pixels: per pixel the butterfly sum of its samples (draw.cu:181-189,
-//                    the arithmetic of resolve_tree_kernel / resolve_kernel) and the same butterfly over their squares, then
-//                    one read-modify-write per pixel and buffer.
-// finalize_counts_kernel  finalize_kernel (draw.cu:13-47) with a per-pixel sample count.
+//                    the accumulating resolve of mirt_render_accumulate and mirt_render_accumulate_pixels: per pixel the butterfly
+//                    sum of its samples (draw.cu:181-189; one lane per sample when the butterfly fits a wave, one thread per pixel
+//                    otherwise) and, SQUARE, the same butterfly over their squares, then one read-modify-write per pixel and
+//                    buffer.  These are the only kernels that add to an accumulation buffer.
+// finalize_kernel    finalize_kernel (draw.cu:13-47) with one sample count for the frame (mirt_finalize) or one per pixel
+//                    (mirt_finalize_counts).
 #include "scene_dev.h"
 #include "host_scene.h"
 
@@ -26,7 +30,7 @@ namespace {
 constexpr int CBLOCK = 1024;          // compaction: items per block (one per thread)
 constexpr int CWAVES = CBLOCK / 64;
 constexpr int RBLOCK = 256;
-constexpr int TBLOCK = 1024;          // moments_tree_kernel, as resolve_tree_kernel
+constexpr int TBLOCK = 1024;          // moments_tree_kernel
 
 // mirt_select_pixels: pixel i is kept when n < max && (n < min || e > max_variance), e the largest estimated variance of the
 // mean over r, g, b -- float32, one rounding per operation (include/mirt.h spells the formula out)
@@ -40,16 +44,8 @@ struct SelectPred {
     if (n < min_samples) return true;
     const float4 S = sum[i], Q = sq[i];
     const float nf = (float)n;
-    const float e = fmaxf(chan(S.x, Q.x, nf), fmaxf(chan(S.y, Q.y, nf), chan(S.z, Q.z, nf)));
+    const float e = fmaxf(variance_of_mean(S.x, Q.x, nf), fmaxf(variance_of_mean(S.y, Q.y, nf), variance_of_mean(S.z, Q.z, nf)));
     return e > max_variance;
-  }
-  __device__ static float chan(float s, float q, float nf)
-  {
-    const float m = s / nf;
-    const float qq = q / nf;
-    float v = qq - m * m;
-    v = v > 0.0f ? v : 0.0f;      // (also a NaN: a non-finite pixel is not chased to max_samples)
-    return v / (nf - 1.0f);
   }
   __device__ uint32_t value(long long i) const { return (uint32_t)i; }
 };
@@ -165,22 +161,25 @@ struct MomentArgs {
 
 MIRT_DEV long long moment_pixels(const MomentArgs& a) { return a.kept ? (long long)*a.num_kept : a.num_pixels; }
 
+template <bool SQUARE>
 MIRT_DEV void add_moments(const MomentArgs& a, long long lp, const float4 s, const float4 q)
 {
   const float4 o = a.accum[lp];
   a.accum[lp] = make_float4(o.x + s.x, o.y + s.y, o.z + s.z, o.w + s.w);
-  if (a.accum_sq) {
+  if (SQUARE) {
     const float4 r = a.accum_sq[lp];
     a.accum_sq[lp] = make_float4(r.x + q.x, r.y + q.y, r.z + q.z, r.w + q.w);
   }
   if (a.counts) a.counts[lp] += (uint32_t)a.count;
 }
 
-// P <= 64, one lane per sample: resolve_tree_kernel's butterfly, over the samples and over their squares
+// P <= 64, one lane per sample: coalesced 16-byte loads, then literally the reference's butterfly `for (mask = P/2; mask > 0;
+// mask /= 2) v += shfl_xor(v, mask)` (draw.cu:181-189) inside each group of P lanes, over the samples and (SQUARE: a.accum_sq is
+// given) over their squares; the group's lane 0 parks its sums in LDS and the first threads of the block add the block's pixels
+template <bool SQUARE>
 __global__ void __launch_bounds__(TBLOCK) moments_tree_kernel(const MomentArgs a, int P, int lg)
 {
-  __shared__ float4 sums[TBLOCK / 2];
-  __shared__ float4 sqs[TBLOCK / 2];
+  __shared__ float4 park[SQUARE ? 2 : 1][TBLOCK / 2];      // [0]: sums, [1]: sums of squares
   const int tid = threadIdx.x;
   const int ppb = TBLOCK >> lg;                       // pixels per block
   const int si = tid & (P - 1);
@@ -194,37 +193,16 @@ __global__ void __launch_bounds__(TBLOCK) moments_tree_kernel(const MomentArgs a
   float4 w = make_float4(v.x * v.x, v.y * v.y, v.z * v.z, v.w * v.w);
   for (int mask = P >> 1; mask > 0; mask >>= 1) {
     v.x += __shfl_xor(v.x, mask); v.y += __shfl_xor(v.y, mask); v.z += __shfl_xor(v.z, mask); v.w += __shfl_xor(v.w, mask);
-    w.x += __shfl_xor(w.x, mask); w.y += __shfl_xor(w.y, mask); w.z += __shfl_xor(w.z, mask); w.w += __shfl_xor(w.w, mask);
+    if (SQUARE) { w.x += __shfl_xor(w.x, mask); w.y += __shfl_xor(w.y, mask); w.z += __shfl_xor(w.z, mask); w.w += __shfl_xor(w.w, mask); }
   }
-  if (si == 0) { sums[tid >> lg] = v; sqs[tid >> lg] = w; }
+  if (si == 0) { park[0][tid >> lg] = v; if (SQUARE) park[1][tid >> lg] = w; }
   __syncthreads();
   const long long h = (long long)blockIdx.x * ppb + tid;
-  if (tid < ppb && h < n) add_moments(a, a.kept ? (long long)a.kept[h] : a.pixel_base + h, sums[tid], sqs[tid]);
-}
-
-// resolve_kernel's sum for any count: the butterfly as lane 0 sees it, a pairwise tree over the samples in bit-reversed order
-template <bool SQUARE>
-MIRT_DEV float4 butterfly_sum(const float4* __restrict__ s, int count, int P, int lg)
-{
-  float4 stk[13];
-  int top = 0;
-  for (int i = 0; i < P; ++i) {
-    const int idx = (int)(__brev((unsigned)i) >> (32 - lg));
-    float4 x = (idx < count) ? s[idx] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (SQUARE) x = make_float4(x.x * x.x, x.y * x.y, x.z * x.z, x.w * x.w);
-    int j = i;
-    while (j & 1) {
-      --top;
-      const float4 l = stk[top];
-      x = make_float4(l.x + x.x, l.y + x.y, l.z + x.z, l.w + x.w);
-      j >>= 1;
-    }
-    stk[top++] = x;
-  }
-  return stk[0];
+  if (tid < ppb && h < n) add_moments<SQUARE>(a, a.kept ? (long long)a.kept[h] : a.pixel_base + h, park[0][tid], park[SQUARE ? 1 : 0][tid]);
 }
 
 // one thread per pixel: count 1, and P > 64
+template <bool SQUARE>
 __global__ void __launch_bounds__(RBLOCK) moments_kernel(const MomentArgs a)
 {
   const long long g = (long long)blockIdx.x * RBLOCK + threadIdx.x;
@@ -239,24 +217,28 @@ __global__ void __launch_bounds__(RBLOCK) moments_kernel(const MomentArgs a)
     int P = 1, lg = 0;
     while (P < a.count) { P <<= 1; ++lg; }
     m = butterfly_sum<false>(s, a.count, P, lg);
-    q = a.accum_sq ? butterfly_sum<true>(s, a.count, P, lg) : m;
+    q = SQUARE ? butterfly_sum<true>(s, a.count, P, lg) : m;
   }
-  add_moments(a, lp, m, q);
+  add_moments<SQUARE>(a, lp, m, q);
 }
 
-__global__ void __launch_bounds__(RBLOCK) finalize_counts_kernel(const float4* __restrict__ accum, const uint32_t* __restrict__ counts,
-                                                                 uchar4* __restrict__ rgba8, long long n)
+// counts null: every pixel is the mean over `aa` samples; otherwise over its own count, and a count of 0 gives a zero pixel
+__global__ void __launch_bounds__(RBLOCK) finalize_kernel(const float4* __restrict__ accum, const uint32_t* __restrict__ counts, uchar4* __restrict__ rgba8,
+                                                          long long n, int aa)
 {
   const long long i = (long long)blockIdx.x * RBLOCK + threadIdx.x;
   if (i >= n) return;
-  const uint32_t c = counts[i];
-  uchar4 o = make_uchar4(0, 0, 0, 0);
-  if (c != 0) {
-    // finalize_kernel, draw.cu:13-47, with this pixel's own count
-    const float4 m = mean_of(accum[i], (int)c);
-    o.x = to_uchar_round(rgb_to_srgb(m.x)); o.y = to_uchar_round(rgb_to_srgb(m.y)); o.z = to_uchar_round(rgb_to_srgb(m.z)); o.w = to_uchar_round(m.w);
-  }
-  rgba8[i] = o;
+  const int c = counts ? (int)counts[i] : aa;
+  // finalize_kernel, draw.cu:13-47
+  rgba8[i] = c != 0 ? to_srgb8(mean_of(accum[i], c)) : make_uchar4(0, 0, 0, 0);
+}
+
+int launch_finalize(const void* d_accum, const uint32_t* d_counts, void* d_rgba8, int64_t n, int aa, hipStream_t stream)
+{
+  hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + RBLOCK - 1) / RBLOCK)), dim3(RBLOCK), 0, stream, (const float4*)d_accum, d_counts, (uchar4*)d_rgba8,
+                     (long long)n, aa);
+  MIRT_HIP(hipGetLastError());
+  return MIRT_OK;
 }
 
 // mirt_select_pixels has no scene to keep its block counts in: one buffer per (device, stream), grown on demand and kept, so
@@ -286,8 +268,8 @@ int sparse_expand(RenderCtx& cx, const uint32_t* list, long long num_listed, lon
   return MIRT_OK;
 }
 
-// The resolve of one launch of mirt_render_accumulate_pixels: the pixels sparse_expand kept (ax.list given), or the slab's
-// pixels [p0, p0 + pn).
+// The resolve of one launch of mirt_render_accumulate (an empty ax) or mirt_render_accumulate_pixels: the pixels sparse_expand
+// kept (ax.list given), or the slab's pixels [p0, p0 + pn).
 int resolve_moments(RenderCtx& cx, const float4* samples, const AdaptiveArgs& ax, float4* accum, long long p0, long long pn, long long num_listed,
                     int count, hipStream_t stream)
 {
@@ -301,9 +283,13 @@ int resolve_moments(RenderCtx& cx, const float4* samples, const AdaptiveArgs& ax
   while (P < count) { P <<= 1; ++lg; }
   if (count > 1 && P <= 64) {
     const long long ppb = TBLOCK >> lg;
-    hipLaunchKernelGGL(moments_tree_kernel, dim3((unsigned)((bound + ppb - 1) / ppb)), dim3(TBLOCK), 0, stream, m, P, lg);
+    const dim3 grid((unsigned)((bound + ppb - 1) / ppb));
+    if (m.accum_sq) hipLaunchKernelGGL(moments_tree_kernel<true>, grid, dim3(TBLOCK), 0, stream, m, P, lg);
+    else hipLaunchKernelGGL(moments_tree_kernel<false>, grid, dim3(TBLOCK), 0, stream, m, P, lg);
   } else {
-    hipLaunchKernelGGL(moments_kernel, dim3((unsigned)((bound + RBLOCK - 1) / RBLOCK)), dim3(RBLOCK), 0, stream, m);
+    const dim3 grid((unsigned)((bound + RBLOCK - 1) / RBLOCK));
+    if (m.accum_sq) hipLaunchKernelGGL(moments_kernel<true>, grid, dim3(RBLOCK), 0, stream, m);
+    else hipLaunchKernelGGL(moments_kernel<false>, grid, dim3(RBLOCK), 0, stream, m);
   }
   MIRT_HIP(hipGetLastError());
   return MIRT_OK;
@@ -339,15 +325,20 @@ int select_pixels(const MirtRenderParams* p, const void* d_accum, const void* d_
   return compact(pr, n, blocks, d_pixels_out, d_num_out, nullptr, 0, stream);
 }
 
+int finalize(const MirtRenderParams* p, const void* d_accum, int total_samples, void* d_rgba8, hipStream_t stream)
+{
+  const int64_t n = render_num_pixels(p);
+  if (n < 0 || !d_accum || !d_rgba8 || total_samples < 1) { set_error("mirt_finalize: bad parameters"); return MIRT_ERR_ARG; }
+  if (n == 0) return MIRT_OK;
+  return launch_finalize(d_accum, nullptr, d_rgba8, n, total_samples, stream);
+}
+
 int finalize_counts(const MirtRenderParams* p, const void* d_accum, const uint32_t* d_counts, void* d_rgba8, hipStream_t stream)
 {
   const int64_t n = render_num_pixels(p);
   if (n < 0 || !d_accum || !d_counts || !d_rgba8) { set_error("mirt_finalize_counts: bad parameters"); return MIRT_ERR_ARG; }
   if (n == 0) return MIRT_OK;
-  hipLaunchKernelGGL(finalize_counts_kernel, dim3((unsigned)((n + RBLOCK - 1) / RBLOCK)), dim3(RBLOCK), 0, stream, (const float4*)d_accum, d_counts,
-                     (uchar4*)d_rgba8, (long long)n);
-  MIRT_HIP(hipGetLastError());
-  return MIRT_OK;
+  return launch_finalize(d_accum, d_counts, d_rgba8, n, 0, stream);
 }
 
 } // namespace mirt

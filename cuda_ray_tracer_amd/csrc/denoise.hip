@@ -5,9 +5,10 @@
 // context, a counter or a hand-out table.
 //
 // hit_features_kernel    one lane per ray: (P, hit), (n, 0) from the ray and its closest-hit record.
-// denoise_prepare_kernel one lane per pixel: mean colour S / n and the variance of the mean (mirt_select_pixels' e).
-// denoise_iter_kernel    one lane per pixel, a 64 x 4 pixel tile per block (one wave per row of the tile: a wave's loads of a
-//                        tap are 64 consecutive pixels, 1 KiB of colour, 2 KiB of features): the 3 x 3 variance prefilter,
+// denoise_prepare_kernel one lane per pixel: mean colour S / n and the variance of the mean (mirt_select_pixels' e:
+//                        variance_of_mean, device_common.h).
+// denoise_iter_kernel    one lane per pixel, a 64 x 4 pixel tile per block (tile_xy, device_common.h; one wave per row of the tile:
+//                        a wave's loads of a tap are 64 consecutive pixels, 1 KiB of colour, 2 KiB of features): the 3 x 3 variance prefilter,
 //                        then the 25 taps at distance s, from global memory (the L1 / L2 serve the reuse between neighbours;
 //                        DESIGN.md section 6f has the measurement against a tile staged in LDS, or says that there is none).
 //                        No atomics, no LDS, no communication between lanes: every output depends on its inputs only, so the
@@ -21,7 +22,7 @@ namespace mirt {
 namespace {
 
 constexpr int DBLOCK = 256;
-constexpr int TILE_W = 64, TILE_H = 4;      // denoise_iter_kernel: TILE_W * TILE_H == DBLOCK
+static_assert(TILE_W * TILE_H == DBLOCK, "denoise_iter_kernel: one lane per pixel of the tile");
 
 __global__ void __launch_bounds__(DBLOCK) hit_features_kernel(const float4* __restrict__ rays, const uint32_t* __restrict__ hits, long long n,
                                                                float4* __restrict__ features)
@@ -30,26 +31,9 @@ __global__ void __launch_bounds__(DBLOCK) hit_features_kernel(const float4* __re
   if (i >= n) return;
   const uint32_t* const h = hits + 6 * i;
   float4 f0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), f1 = f0;
-  if (h[1] != (uint32_t)MIRT_HIT_NONE) {
-    const float4 r0 = rays[2 * i], r1 = rays[2 * i + 1];
-    const float t = __uint_as_float(h[0]);
-    const f3 d = normalize(mk3(r1.x, r1.y, r1.z));      // the direction mirt_trace_rays measured t along
-    const float px = t * d.x, py = t * d.y, pz = t * d.z;
-    f0 = make_float4(r0.x + px, r0.y + py, r0.z + pz, 1.0f);
-    f1 = make_float4(__uint_as_float(h[3]), __uint_as_float(h[4]), __uint_as_float(h[5]), 0.0f);
-  }
+  if (h[1] != (uint32_t)MIRT_HIT_NONE) hit_feature_rows(rays[2 * i], rays[2 * i + 1], h, f0, f1);
   features[2 * i] = f0;
   features[2 * i + 1] = f1;
-}
-
-// mirt_select_pixels' e_c (adaptive.hip, SelectPred::chan)
-MIRT_DEV float variance_of_mean(float s, float q, float nf)
-{
-  const float m = s / nf;
-  const float qq = q / nf;
-  float v = qq - m * m;
-  v = v > 0.0f ? v : 0.0f;      // (also a NaN)
-  return v / (nf - 1.0f);
 }
 
 __global__ void __launch_bounds__(DBLOCK) denoise_prepare_kernel(const float4* __restrict__ accum, const float4* __restrict__ accum_sq,
@@ -82,16 +66,10 @@ struct IterArgs {
   float sigma_c, sigma_n, sigma_p;
 };
 
-MIRT_DEV bool finite3(const float4& c)
-{
-  // (x - x is 0 for a finite x and NaN for an infinity or a NaN)
-  return (c.x - c.x) == 0.0f && (c.y - c.y) == 0.0f && (c.z - c.z) == 0.0f;
-}
-
 __global__ void __launch_bounds__(DBLOCK) denoise_iter_kernel(const IterArgs a)
 {
-  const int x = (int)blockIdx.x * TILE_W + ((int)threadIdx.x & (TILE_W - 1));
-  const int y = (int)blockIdx.y * TILE_H + ((int)threadIdx.x >> 6);
+  int x, y;
+  tile_xy(x, y);
   if (x >= a.width || y >= a.height) return;
   const long long W = a.width;
   const long long p = (long long)y * W + x;
@@ -166,21 +144,13 @@ __global__ void __launch_bounds__(DBLOCK) denoise_iter_kernel(const IterArgs a)
   a.var_out[p] = sv / (sw * sw);
 }
 
-bool overlaps(const void* a, size_t na, const void* b, size_t nb)
-{
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
-bool positive_finite(float x) { return x > 0.0f && std::isfinite(x); }
-
 } // namespace
 
 int hit_features(MirtScene* sc, const void* d_rays, const void* d_hits, int64_t n, void* d_features, hipStream_t stream)
 {
   if (n < 0) { set_error("mirt_hit_features: negative n"); return MIRT_ERR_ARG; }
   if (n > 0 && (!d_rays || !d_hits || !d_features)) { set_error("mirt_hit_features: null buffer"); return MIRT_ERR_ARG; }
-  if (((uintptr_t)d_rays & 15u) != 0u || ((uintptr_t)d_hits & 3u) != 0u || ((uintptr_t)d_features & 15u) != 0u) {
+  if (!is_aligned(16, d_rays, d_features) || !is_aligned(4, d_hits)) {
     set_error("mirt_hit_features: d_rays and d_features must be 16-byte aligned, d_hits 4-byte aligned"); return MIRT_ERR_ARG;
   }
   if (n >= 0x7fffffffll * DBLOCK) { set_error("mirt_hit_features: too many rays"); return MIRT_ERR_ARG; }
@@ -210,7 +180,7 @@ int denoise(const MirtRenderParams* p, const void* d_accum, const void* d_accum_
     set_error("mirt_denoise: sigma_c, sigma_n and sigma_p must be finite and positive"); return MIRT_ERR_ARG;
   }
   if (!d_accum || !d_accum_sq || !d_counts || !d_features || !d_work || !d_out) { set_error("mirt_denoise: null pointer"); return MIRT_ERR_ARG; }
-  if ((((uintptr_t)d_accum | (uintptr_t)d_accum_sq | (uintptr_t)d_features | (uintptr_t)d_work | (uintptr_t)d_out) & 15u) != 0u || ((uintptr_t)d_counts & 3u) != 0u) {
+  if (!is_aligned(16, d_accum, d_accum_sq, d_features, d_work, d_out) || !is_aligned(4, d_counts)) {
     set_error("mirt_denoise: the float buffers must be 16-byte aligned, d_counts 4-byte aligned"); return MIRT_ERR_ARG;
   }
   if (n >= 0x7fffffffll || p->height > 65535 * TILE_H) { set_error("mirt_denoise: frame too large"); return MIRT_ERR_ARG; }
@@ -227,7 +197,7 @@ int denoise(const MirtRenderParams* p, const void* d_accum, const void* d_accum_
   float* const var[2] = {(float*)((float4*)d_work + 2 * N), (float*)((float4*)d_work + 2 * N) + N};
   hipLaunchKernelGGL(denoise_prepare_kernel, dim3((unsigned)((n + DBLOCK - 1) / DBLOCK)), dim3(DBLOCK), 0, stream, (const float4*)d_accum,
                      (const float4*)d_accum_sq, d_counts, (long long)n, iterations == 0 ? (float4*)d_out : colour[0], var[0]);
-  const dim3 grid((unsigned)((p->width + TILE_W - 1) / TILE_W), (unsigned)((p->height + TILE_H - 1) / TILE_H));
+  const dim3 grid = tile_grid(p->width, p->height);
   for (int i = 0; i < iterations; ++i) {
     IterArgs a;
     a.colour_in = colour[i & 1]; a.var_in = var[i & 1];

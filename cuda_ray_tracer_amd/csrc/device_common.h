@@ -1,9 +1,11 @@
-// Device-side building blocks shared by the LBVH build and the render kernels (gfx950 only).
+// Device-side building blocks shared by the LBVH build, the render kernels and the image-space stages (gfx950 only).
 //   * f3: float3 arithmetic with the reference's operator semantics (vec3.cuh:21-107)
 //   * dm_*: deterministic logf/expf/sinf/cosf/powf built from IEEE double +,-,*,/ only, so that every
 //     value the kernels compute is reproducible bit for bit on any IEEE machine (built with -ffp-contract=off;
 //     hipcc's default correctly rounded fp32 divide/sqrt)
 //   * Xorwow: cuRAND-compatible generator state kept in registers
+//   * what the image-space stages share: the butterfly sum of a pixel's samples, mean -> sRGB -> 8 bits, the variance of the
+//     mean, a hit's feature rows, the 64 x 4 pixel tile
 #ifndef MIRT_DEVICE_COMMON_H
 #define MIRT_DEVICE_COMMON_H
 
@@ -44,6 +46,9 @@ MIRT_DEV f3 normalize(const f3& v)
   float inv = 1.0f / mag;
   return mk3(v.x * inv, v.y * inv, v.z * inv);
 }
+MIRT_DEV f3 cross(const f3& a, const f3& b) { return mk3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+// (x - x is 0 for a finite x and NaN for an infinity or a NaN)
+MIRT_DEV bool finite3(const float4& c) { return (c.x - c.x) == 0.0f && (c.y - c.y) == 0.0f && (c.z - c.z) == 0.0f; }
 // RGB == RGB(0,0,0), struct.cuh:20-23
 MIRT_DEV bool is_black(const f3& c) { return is_zero(c.x) && is_zero(c.y) && is_zero(c.z); }
 
@@ -267,6 +272,62 @@ MIRT_DEV float4 mean_of(const float4 sum, int spp)
   const float inv = 1.0f / (float)spp;
   return make_float4(sum.x * inv, sum.y * inv, sum.z * inv, sum.w * inv);
 }
+// a mean -> the 8-bit pixel of finalize_kernel and of render with spp > 1 (draw.cu:27-30, 202-205)
+MIRT_DEV uchar4 to_srgb8(const float4 m)
+{
+  return make_uchar4(to_uchar_round(rgb_to_srgb(m.x)), to_uchar_round(rgb_to_srgb(m.y)), to_uchar_round(rgb_to_srgb(m.z)), to_uchar_round(m.w));
+}
+// The sum of a pixel's samples (SQUARE: of their squares) in the order of `for (mask = P/2; mask > 0; mask /= 2) v += shfl_xor(v, mask)`
+// as lane 0 sees it (draw.cu:181-189), P = 2^lg = the next power of two >= count, absent samples = 0: a pairwise tree over the
+// samples in bit-reversed order.  The stack holds log2(4096) + 1 partial sums.
+template <bool SQUARE>
+MIRT_DEV float4 butterfly_sum(const float4* __restrict__ s, int count, int P, int lg)
+{
+  float4 stk[13];
+  int top = 0;
+  for (int i = 0; i < P; ++i) {
+    const int idx = (int)(__brev((unsigned)i) >> (32 - lg));
+    float4 x = (idx < count) ? s[idx] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (SQUARE) x = make_float4(x.x * x.x, x.y * x.y, x.z * x.z, x.w * x.w);
+    int j = i;
+    while (j & 1) {
+      --top;
+      const float4 l = stk[top];
+      x = make_float4(l.x + x.x, l.y + x.y, l.z + x.z, l.w + x.w);
+      j >>= 1;
+    }
+    stk[top++] = x;
+  }
+  return stk[0];
+}
+// The estimated variance of the mean of one channel from its sum s, its sum of squares q and the sample count nf >= 2 (include/mirt.h,
+// mirt_select_pixels, spells the formula out): float32, one rounding per operation
+MIRT_DEV float variance_of_mean(float s, float q, float nf)
+{
+  const float m = s / nf;
+  const float qq = q / nf;
+  float v = qq - m * m;
+  v = v > 0.0f ? v : 0.0f;      // (also a NaN: a non-finite pixel is not chased to max_samples)
+  return v / (nf - 1.0f);
+}
+// The feature rows (P, 1), (n, 0) of a hit: a MirtRay row (r0, r1) and its MirtHit row h (t, kind, id, n), kind not MIRT_HIT_NONE
+MIRT_DEV void hit_feature_rows(const float4 r0, const float4 r1, const uint32_t* __restrict__ h, float4& f0, float4& f1)
+{
+  const float t = __uint_as_float(h[0]);
+  const f3 d = normalize(mk3(r1.x, r1.y, r1.z));      // the direction mirt_trace_rays measured t along
+  const float px = t * d.x, py = t * d.y, pz = t * d.z;
+  f0 = make_float4(r0.x + px, r0.y + py, r0.z + pz, 1.0f);
+  f1 = make_float4(__uint_as_float(h[3]), __uint_as_float(h[4]), __uint_as_float(h[5]), 0.0f);
+}
+// One lane per pixel, a 64 x 4 pixel tile per block of 256 (one wave per row of the tile: a wave's loads of a tap are 64 consecutive
+// pixels): the image-space kernels of denoise.hip and temporal.hip
+constexpr int TILE_W = 64, TILE_H = 4;
+MIRT_DEV void tile_xy(int& x, int& y)
+{
+  x = (int)blockIdx.x * TILE_W + ((int)threadIdx.x & (TILE_W - 1));
+  y = (int)blockIdx.y * TILE_H + ((int)threadIdx.x >> 6);
+}
+inline dim3 tile_grid(int width, int height) { return dim3((unsigned)((width + TILE_W - 1) / TILE_W), (unsigned)((height + TILE_H - 1) / TILE_H)); }
 
 // ---- XORWOW (curand_kernel.h semantics) -----------------------------------------
 struct Xorwow {

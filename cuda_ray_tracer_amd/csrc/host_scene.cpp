@@ -16,6 +16,18 @@ namespace mirt {
 thread_local std::string g_last_error;
 void set_error(const std::string& s) { g_last_error = s; }
 
+int check_range(const char* who, const void* d_array, int first, int count, int total, size_t align, bool* go)
+{
+  *go = false;
+  if (first < 0 || count < 0) { set_error(std::string(who) + ": negative first or count"); return MIRT_ERR_ARG; }
+  if ((long long)first + count > total) { set_error(std::string(who) + ": range beyond the scene's primitives"); return MIRT_ERR_ARG; }
+  if (count == 0) return MIRT_OK;
+  if (!d_array) { set_error(std::string(who) + ": null pointer"); return MIRT_ERR_ARG; }
+  if (!is_aligned(align, d_array)) { set_error(std::string(who) + ": misaligned pointer"); return MIRT_ERR_ARG; }
+  *go = true;
+  return MIRT_OK;
+}
+
 namespace {
 
 inline MirtVec3 v3(float x, float y, float z) { MirtVec3 v; v.x = x; v.y = y; v.z = z; return v; }

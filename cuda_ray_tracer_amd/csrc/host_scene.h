@@ -1,7 +1,11 @@
-// Host-side scene container (the reference's StlConfig, config.hpp:24-73) and parser.
+// Host-side scene container (the reference's StlConfig, config.hpp:24-73) and parser; the last-error string and the argument
+// checks the C entry points share.
 #ifndef MIRT_HOST_SCENE_H
 #define MIRT_HOST_SCENE_H
 
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
 #include <istream>
 #include <string>
 #include <vector>
@@ -12,6 +16,20 @@ namespace mirt {
 
 extern thread_local std::string g_last_error;
 void set_error(const std::string& s);
+
+// do the byte ranges [a, a + na) and [b, b + nb) share a byte
+inline bool overlaps(const void* a, size_t na, const void* b, size_t nb)
+{
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+inline bool positive_finite(float x) { return x > 0.0f && std::isfinite(x); }
+// is every one of the pointers a multiple of n, a power of two (a null pointer is)
+template <class... T>
+bool is_aligned(size_t n, const T*... p) { return ((... | (uintptr_t)p) & (n - 1)) == 0; }
+// A range [first, first + count) of a scene's `total` spheres or triangles and the device array that gives or receives it
+// (mirt_scene_update_* / mirt_scene_get_*).  MIRT_OK with *go = false: nothing to do (count 0).
+int check_range(const char* who, const void* d_array, int first, int count, int total, size_t align, bool* go);
 
 class HostScene {
 public:

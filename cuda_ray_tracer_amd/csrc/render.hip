@@ -10,9 +10,10 @@
 //                 is one wave; the loop header (who traverses, who waits, is the wave draining, are enough primitive
 //                 tests pending) runs once per four traversal steps; only what the loop touches is passed by value.
 // resolve_tree_kernel / resolve_kernel
-//                 per pixel: sum the samples in the reference's xor-butterfly order (draw.cu:181-189), mean, sRGB,
+//                 mirt_render's pixels: sum the samples in the reference's xor-butterfly order (draw.cu:181-189), mean, sRGB,
 //                 quantise (draw.cu:129-132 for spp <= 1, draw.cu:9-11,202-205 otherwise); one lane per sample when
-//                 the butterfly fits a wave, one thread per pixel otherwise.
+//                 the butterfly fits a wave, one thread per pixel otherwise.  (mirt_render_accumulate's sums go through
+//                 adaptive.hip's resolve_moments, as do mirt_finalize's pixels.)
 // order_kernel    sorts the frame's sample chunks by their measured cost: later frames hand them out longest first.
 //
 // The ray tree is evaluated top-down (every ray carries the product of the mixing weights above it) instead of the
@@ -378,7 +379,7 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
 }
 #undef MIRT_HELD
 
-// (to_uchar_round, draw.cu:9-11, and mean_of: device_common.h)
+// (to_srgb8, draw.cu:9-11, and mean_of: device_common.h)
 // draw.cu:129-132: plain float -> unsigned char conversion
 MIRT_DEV unsigned char to_uchar_trunc(float f)
 {
@@ -391,11 +392,6 @@ MIRT_DEV unsigned char to_uchar_trunc(float f)
 MIRT_DEV void write_pixel(const ResolveArgs& a, long long lq, const float4 sum)
 {
   const long long lp = a.pixel_base + lq;
-  if (a.accum) {      // mirt_render_accumulate: one add per pixel and call
-    const float4 o = a.accum[lp];
-    a.accum[lp] = make_float4(o.x + sum.x, o.y + sum.y, o.z + sum.z, o.w + sum.w);
-    return;
-  }
   const float4 m = a.count > 1 ? mean_of(sum, a.count) : sum;
   if (a.rgba_f32) a.rgba_f32[lp] = m;
   uchar4 o;
@@ -405,10 +401,7 @@ MIRT_DEV void write_pixel(const ResolveArgs& a, long long lq, const float4 sum)
     o.z = to_uchar_trunc(rgb_to_srgb(m.z) * 255);
     o.w = to_uchar_trunc(m.w * 255);
   } else {
-    o.x = to_uchar_round(rgb_to_srgb(m.x));
-    o.y = to_uchar_round(rgb_to_srgb(m.y));
-    o.z = to_uchar_round(rgb_to_srgb(m.z));
-    o.w = to_uchar_round(m.w);
+    o = to_srgb8(m);
   }
   reinterpret_cast<uchar4*>(a.rgba8)[lp] = o;
 }
@@ -422,27 +415,9 @@ __global__ void __launch_bounds__(RBLOCK) resolve_kernel(const ResolveArgs a)
   if (a.count <= 1) {
     m = a.samples[lp];
   } else {
-    // Sum in the order of `for (mask = P/2; mask > 0; mask /= 2) v += shfl_xor(v, mask)` as lane 0 sees it
-    // (draw.cu:181-189), P = next power of two >= spp, absent samples = 0: a pairwise tree over the samples in
-    // bit-reversed order.
     int P = 1, lg = 0;
     while (P < a.count) { P <<= 1; ++lg; }
-    const float4* s = a.samples + lp * a.count;
-    float4 stk[13];
-    int top = 0;
-    for (int i = 0; i < P; ++i) {
-      const int idx = (int)(__brev((unsigned)i) >> (32 - lg));
-      float4 x = (idx < a.count) ? s[idx] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      int j = i;
-      while (j & 1) {
-        --top;
-        const float4 l = stk[top];
-        x = make_float4(l.x + x.x, l.y + x.y, l.z + x.z, l.w + x.w);
-        j >>= 1;
-      }
-      stk[top++] = x;
-    }
-    m = stk[0];
+    m = butterfly_sum<false>(a.samples + lp * a.count, a.count, P, lg);
   }
   write_pixel(a, lp, m);
 }
@@ -633,7 +608,8 @@ static int grid_blocks(int device)
 // 2.1 G samples) takes 8 slabs instead of a 34 GB buffer.  Each slab is a trace launch + a resolve launch; a slab boundary
 // costs one drain of the persistent grid (~1-2 ms per 64 M samples).
 //   d_accum == null: pixels are written (mean, sRGB, quantise);  sample_first must be 0 and sample_count max(spp, 1)
-//   d_accum != null: the sum of each pixel's samples [sample_first, sample_first + sample_count) is ADDED to d_accum
+//   d_accum != null: the sum of each pixel's samples [sample_first, sample_first + sample_count) is ADDED to d_accum (adaptive.hip,
+//                    resolve_moments)
 //   ax != null (with d_accum): mirt_render_accumulate_pixels -- the second moment and the counts are added as well, and with
 //                    ax->list only the listed pixels are rendered: every launch hands out, through RenderArgs::sample_order, the
 //                    samples of the listed pixels of its slab (adaptive.hip) instead of the scene's measured order, to the same
@@ -972,10 +948,11 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
     if (slab == nslabs - 1) MIRT_HIP(hipEventRecord(cx.ev2, stream));
 
     ResolveArgs ra;
-    ra.samples = cx.samples; ra.rgba8 = (unsigned char*)d_rgba8; ra.rgba_f32 = (float4*)d_rgba_f32; ra.accum = (float4*)d_accum;
+    ra.samples = cx.samples; ra.rgba8 = (unsigned char*)d_rgba8; ra.rgba_f32 = (float4*)d_rgba_f32;
     ra.num_local_pixels = pn; ra.pixel_base = p0; ra.spp = p->spp; ra.count = sample_count;
-    if (ax) {
-      int rc = resolve_moments(cx, cx.samples, *ax, (float4*)d_accum, p0, pn, ax->num_listed, sample_count, stream);
+    if (d_accum) {
+      const AdaptiveArgs mx = ax ? *ax : AdaptiveArgs();      // (mirt_render_accumulate: every pixel, the sums only)
+      int rc = resolve_moments(cx, cx.samples, mx, (float4*)d_accum, p0, pn, mx.num_listed, sample_count, stream);
       if (rc != MIRT_OK) return rc;
     } else if (sample_count > 1 && P <= 64) {
       const long long ppb = TBLOCK >> lg;
@@ -1048,27 +1025,6 @@ int render_accumulate_pixels(MirtScene* sc, const MirtRenderParams* p, const Ada
   if (!sc->built) { set_error("mirt_render_accumulate_pixels: call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
   if (ax.list && ax.num_listed == 0) return MIRT_OK;
   return render_impl(sc, p, nullptr, nullptr, d_accum, sample_first, sample_count, stream, &ax);
-}
-
-__global__ void __launch_bounds__(RBLOCK) finalize_kernel_dev(const float4* __restrict__ accum, uchar4* __restrict__ rgba8, long long n, int aa)
-{
-  // finalize_kernel, draw.cu:13-47
-  const long long i = (long long)blockIdx.x * RBLOCK + threadIdx.x;
-  if (i >= n) return;
-  const float4 m = mean_of(accum[i], aa);
-  uchar4 o;
-  o.x = to_uchar_round(rgb_to_srgb(m.x)); o.y = to_uchar_round(rgb_to_srgb(m.y)); o.z = to_uchar_round(rgb_to_srgb(m.z)); o.w = to_uchar_round(m.w);
-  rgba8[i] = o;
-}
-
-int finalize(const MirtRenderParams* p, const void* d_accum, int total_samples, void* d_rgba8, hipStream_t stream)
-{
-  const int64_t n = local_pixels(p);
-  if (n < 0 || !d_accum || !d_rgba8 || total_samples < 1) { set_error("mirt_finalize: bad parameters"); return MIRT_ERR_ARG; }
-  if (n == 0) return MIRT_OK;
-  hipLaunchKernelGGL(finalize_kernel_dev, dim3((unsigned)((n + RBLOCK - 1) / RBLOCK)), dim3(RBLOCK), 0, stream, (const float4*)d_accum, (uchar4*)d_rgba8, (long long)n, total_samples);
-  MIRT_HIP(hipGetLastError());
-  return MIRT_OK;
 }
 
 int scatter_part(const MirtRenderParams* p, const void* d_part, void* d_frame, hipStream_t stream)

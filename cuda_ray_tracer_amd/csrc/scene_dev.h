@@ -131,11 +131,10 @@ struct HotArgs {
 
 struct ResolveArgs {
   const float4* samples;          // this launch's samples: [num_local_pixels][count]
-  unsigned char* rgba8;           // the call's part buffer (nullable when accumulating)
+  unsigned char* rgba8;           // the call's part buffer
   float4* rgba_f32;               // nullable
-  float4* accum;                  // non-null: add the per-pixel sample sums here instead of writing pixels (mirt_render_accumulate)
   long long num_local_pixels;     // pixels of this launch
-  long long pixel_base;           // where they start in rgba8 / rgba_f32 / accum
+  long long pixel_base;           // where they start in rgba8 / rgba_f32
   int spp;                        // the call's spp (quantiser choice: draw.cu:129-132 for spp <= 1, :9-11,202-205 otherwise)
   int count;                      // samples per pixel in `samples`
 };
@@ -212,8 +211,8 @@ struct RenderCtx {
   uint32_t* sp_blocks = nullptr; size_t sp_blocks_cap = 0;
 };
 
-// What mirt_render_accumulate_pixels adds to mirt_render_accumulate: the pixels to render (null: every pixel of the part) and
-// the two optional outputs.
+// What mirt_render_accumulate_pixels adds to mirt_render_accumulate (which renders with an empty one): the pixels to render
+// (null: every pixel of the part) and the two optional outputs.
 struct AdaptiveArgs {
   const uint32_t* list = nullptr;          // device: num_listed distinct local pixels of the part, any order
   long long num_listed = 0;
@@ -310,7 +309,6 @@ int probe_math(int device, int which, int n, const float* in, float* out);
 int probe_xorwow(int device, int spp, int nstreams, int draws, uint32_t* out);
 int ensure_rng_tables(RngCache* rc, int sample_tables, long long frame_pixels, hipStream_t stream, RngTablesDev* out, bool allow_larger);
 int render_accumulate(MirtScene* sc, const MirtRenderParams* p, void* d_accum, int sample_first, int sample_count, hipStream_t stream);
-int finalize(const MirtRenderParams* p, const void* d_accum, int total_samples, void* d_rgba8, hipStream_t stream);
 void rng_cache_free(RngCache* rc);
 int render_accumulate_pixels(MirtScene* sc, const MirtRenderParams* p, const AdaptiveArgs& ax, void* d_accum, int sample_first, int sample_count, hipStream_t stream);
 // adaptive.hip
@@ -320,6 +318,7 @@ int resolve_moments(RenderCtx& cx, const float4* samples, const AdaptiveArgs& ax
                     int count, hipStream_t stream);
 int select_pixels(const MirtRenderParams* p, const void* d_accum, const void* d_accum_sq, const uint32_t* d_counts, int min_samples, int max_samples,
                   float max_variance, uint32_t* d_pixels_out, uint32_t* d_num_out, hipStream_t stream);
+int finalize(const MirtRenderParams* p, const void* d_accum, int total_samples, void* d_rgba8, hipStream_t stream);
 int finalize_counts(const MirtRenderParams* p, const void* d_accum, const uint32_t* d_counts, void* d_rgba8, hipStream_t stream);
 // query.hip
 int trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits, uint32_t flags, hipStream_t stream);

@@ -6,8 +6,9 @@
 // mirt_finalize_counts consume as they are.  Nothing here touches a render context, a counter or a hand-out table.
 //
 // get_spheres_kernel / get_triangles_kernel  one lane per primitive: the scene's file-order arrays back out, the inverse of update.hip.
-// prev_features_kernel      one lane per ray: the hit point and normal as they were in the previous geometry.
-// temporal_kernel           one lane per pixel, denoise_iter_kernel's 64 x 4 pixel tile per block (one wave per row of the tile: a
+// prev_features_kernel      one lane per ray: hit_features' rows (hit_feature_rows, device_common.h), then what moved replaced by
+//                           the hit point and normal as they were in the previous geometry.
+// temporal_kernel           one lane per pixel, a 64 x 4 pixel tile per block (tile_xy, device_common.h; one wave per row of the tile: a
 //                           wave's own-pixel traffic is consecutive 16-byte loads and stores); the four bilinear taps of the
 //                           history are gathers from global memory that neighbouring lanes share through the L1 / L2.  No atomics,
 //                           no LDS, no communication between lanes: every output depends on its inputs only.  A lane reads the
@@ -22,10 +23,7 @@ namespace mirt {
 namespace {
 
 constexpr int TBLOCK = 256;
-constexpr int TILE_W = 64, TILE_H = 4;      // temporal_kernel: TILE_W * TILE_H == TBLOCK
-
-// (update.hip's)
-MIRT_DEV f3 cross(const f3& a, const f3& b) { return mk3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+static_assert(TILE_W * TILE_H == TBLOCK, "temporal_kernel: one lane per pixel of the tile");
 
 __global__ __launch_bounds__(TBLOCK) void get_spheres_kernel(const float4* __restrict__ spheres, float4* __restrict__ out, int count)
 {
@@ -58,15 +56,8 @@ __global__ void __launch_bounds__(TBLOCK) prev_features_kernel(const float4* __r
   const uint32_t kind = h[1], id = h[2];
   float4 f0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), f1 = f0;
   if (kind != (uint32_t)MIRT_HIT_NONE) {
-    // hit_features_kernel's P and n
-    const float4 r0 = rays[2 * i], r1 = rays[2 * i + 1];
-    const float t = __uint_as_float(h[0]);
-    const f3 d = normalize(mk3(r1.x, r1.y, r1.z));
-    const float px = t * d.x, py = t * d.y, pz = t * d.z;
-    const f3 P = mk3(r0.x + px, r0.y + py, r0.z + pz);
-    const f3 nr = mk3(__uint_as_float(h[3]), __uint_as_float(h[4]), __uint_as_float(h[5]));
-    f0 = make_float4(P.x, P.y, P.z, 1.0f);
-    f1 = make_float4(nr.x, nr.y, nr.z, 0.0f);
+    hit_feature_rows(rays[2 * i], rays[2 * i + 1], h, f0, f1);
+    const f3 P = mk3(f0.x, f0.y, f0.z), nr = mk3(f1.x, f1.y, f1.z);
     if (kind == (uint32_t)MIRT_HIT_SPHERE && prev_xyzr) {
       if (id >= (uint32_t)num_spheres) {
         f0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f); f1 = f0;
@@ -112,12 +103,6 @@ struct TemporalArgs {
   f3 eye, forward, right, up;      // the previous camera
 };
 
-MIRT_DEV bool finite3(const float4& c)
-{
-  // (x - x is 0 for a finite x and NaN for an infinity or a NaN)
-  return (c.x - c.x) == 0.0f && (c.y - c.y) == 0.0f && (c.z - c.z) == 0.0f;
-}
-
 // One axis of the reprojected position: snapped to a pixel centre within 1 / 1024, split into the first tap's coordinate and the
 // second tap's weight.  false: both taps are outside [0, size) (or the position is a NaN).
 MIRT_DEV bool split_axis(float x, int size, int* first, float* frac)
@@ -133,8 +118,8 @@ MIRT_DEV bool split_axis(float x, int size, int* first, float* frac)
 
 __global__ void __launch_bounds__(TBLOCK) temporal_kernel(const TemporalArgs a)
 {
-  const int x = (int)blockIdx.x * TILE_W + ((int)threadIdx.x & (TILE_W - 1));
-  const int y = (int)blockIdx.y * TILE_H + ((int)threadIdx.x >> 6);
+  int x, y;
+  tile_xy(x, y);
   if (x >= a.width || y >= a.height) return;
   const long long W = a.width;
   const long long p = (long long)y * W + x;
@@ -238,27 +223,6 @@ __global__ void __launch_bounds__(TBLOCK) temporal_kernel(const TemporalArgs a)
   a.out_counts[p] = ck + hk;
 }
 
-bool overlaps(const void* a, size_t na, const void* b, size_t nb)
-{
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
-bool positive_finite(float x) { return x > 0.0f && std::isfinite(x); }
-
-// update.hip's check_range, for the calls that read the arrays back.  MIRT_OK with *go = false: nothing to do (count 0).
-int check_range(const char* who, const void* d_out, int first, int count, int total, size_t align, bool* go)
-{
-  *go = false;
-  if (first < 0 || count < 0) { set_error(std::string(who) + ": negative first or count"); return MIRT_ERR_ARG; }
-  if ((long long)first + count > total) { set_error(std::string(who) + ": range beyond the scene's primitives"); return MIRT_ERR_ARG; }
-  if (count == 0) return MIRT_OK;
-  if (!d_out) { set_error(std::string(who) + ": null pointer"); return MIRT_ERR_ARG; }
-  if (reinterpret_cast<uintptr_t>(d_out) % align != 0) { set_error(std::string(who) + ": misaligned pointer"); return MIRT_ERR_ARG; }
-  *go = true;
-  return MIRT_OK;
-}
-
 f3 host3(const MirtVec3& v) { f3 r; r.x = v.x; r.y = v.y; r.z = v.z; return r; }
 
 } // namespace
@@ -290,8 +254,7 @@ int prev_features(MirtScene* sc, const void* d_rays, const void* d_hits, int64_t
 {
   if (n < 0) { set_error("mirt_prev_features: negative n"); return MIRT_ERR_ARG; }
   if (n > 0 && (!d_rays || !d_hits || !d_features)) { set_error("mirt_prev_features: null buffer"); return MIRT_ERR_ARG; }
-  if (((uintptr_t)d_rays & 15u) != 0u || ((uintptr_t)d_hits & 3u) != 0u || ((uintptr_t)d_features & 15u) != 0u || ((uintptr_t)d_prev_xyzr & 15u) != 0u ||
-      ((uintptr_t)d_prev_verts & 3u) != 0u) {
+  if (!is_aligned(16, d_rays, d_features, d_prev_xyzr) || !is_aligned(4, d_hits, d_prev_verts)) {
     set_error("mirt_prev_features: d_rays, d_features and d_prev_xyzr must be 16-byte aligned, d_hits and d_prev_verts 4-byte aligned"); return MIRT_ERR_ARG;
   }
   if (n >= 0x7fffffffll * TBLOCK) { set_error("mirt_prev_features: too many rays"); return MIRT_ERR_ARG; }
@@ -321,9 +284,8 @@ int temporal_accumulate(const MirtRenderParams* p, const MirtCamera* prev_camera
       !d_out_accum_sq || !d_out_counts) {
     set_error(std::string(who) + ": null pointer"); return MIRT_ERR_ARG;
   }
-  if ((((uintptr_t)d_accum | (uintptr_t)d_accum_sq | (uintptr_t)d_prev_features | (uintptr_t)d_hist_accum | (uintptr_t)d_hist_accum_sq |
-        (uintptr_t)d_hist_features | (uintptr_t)d_out_accum | (uintptr_t)d_out_accum_sq) & 15u) != 0u ||
-      (((uintptr_t)d_counts | (uintptr_t)d_hist_counts | (uintptr_t)d_out_counts) & 3u) != 0u) {
+  if (!is_aligned(16, d_accum, d_accum_sq, d_prev_features, d_hist_accum, d_hist_accum_sq, d_hist_features, d_out_accum, d_out_accum_sq) ||
+      !is_aligned(4, d_counts, d_hist_counts, d_out_counts)) {
     set_error(std::string(who) + ": the float buffers must be 16-byte aligned, the counts 4-byte aligned"); return MIRT_ERR_ARG;
   }
   const size_t N = (size_t)n;
@@ -360,8 +322,7 @@ int temporal_accumulate(const MirtRenderParams* p, const MirtCamera* prev_camera
   a.max_history = (uint32_t)max_history;
   a.sigma_n = sigma_n; a.sigma_p = sigma_p;
   a.eye = host3(prev_camera->eye); a.forward = host3(prev_camera->forward); a.right = host3(prev_camera->right); a.up = host3(prev_camera->up);
-  const dim3 grid((unsigned)((p->width + TILE_W - 1) / TILE_W), (unsigned)((p->height + TILE_H - 1) / TILE_H));
-  hipLaunchKernelGGL(temporal_kernel, grid, dim3(TBLOCK), 0, stream, a);
+  hipLaunchKernelGGL(temporal_kernel, tile_grid(p->width, p->height), dim3(TBLOCK), 0, stream, a);
   MIRT_HIP(hipGetLastError());
   return MIRT_OK;
 }

@@ -6,15 +6,12 @@
 #include "scene_dev.h"
 #include "host_scene.h"
 
-#include <string>
 
 namespace mirt {
 
 namespace {
 
 constexpr int UPDATE_BLOCK = 256;
-
-MIRT_DEV f3 cross(const f3& a, const f3& b) { return mk3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 
 // one lane per sphere: (cx, cy, cz, r) as given
 __global__ __launch_bounds__(UPDATE_BLOCK) void update_spheres_kernel(const float4* __restrict__ in, float4* __restrict__ spheres, int count)
@@ -48,19 +45,6 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void update_triangles_kernel(const fl
   to[0] = make_float4(p0.x, p0.y, p0.z, nor.x);
   to[1] = make_float4(nor.y, nor.z, e1.x, e1.y);
   to[2] = make_float4(e1.z, e2.x, e2.y, e2.z);
-}
-
-// The argument checks both updates share.  MIRT_OK with *go = false: nothing to do (count 0).
-int check_range(const char* who, const void* d_in, int first, int count, int total, size_t align, bool* go)
-{
-  *go = false;
-  if (first < 0 || count < 0) { set_error(std::string(who) + ": negative first or count"); return MIRT_ERR_ARG; }
-  if ((long long)first + count > total) { set_error(std::string(who) + ": range beyond the scene's primitives"); return MIRT_ERR_ARG; }
-  if (count == 0) return MIRT_OK;
-  if (!d_in) { set_error(std::string(who) + ": null pointer"); return MIRT_ERR_ARG; }
-  if (reinterpret_cast<uintptr_t>(d_in) % align != 0) { set_error(std::string(who) + ": misaligned pointer"); return MIRT_ERR_ARG; }
-  *go = true;
-  return MIRT_OK;
 }
 
 // Frames in flight read the record heap, which the build that follows an update rewrites: wait for every context's last

@@ -602,10 +602,11 @@ def gpu_accumulate(raw, w, h, passes, total):
     return img.cpu().numpy().reshape(h, w, 4), acc.cpu().numpy().reshape(h, w, 4)
 
 
-@pytest.mark.parametrize("name,w,h,spp", [("tenthousand", 96, 54, 16), ("redchair", 64, 36, 32), ("spiral", 48, 27, 20)])
+@pytest.mark.parametrize("name,w,h,spp", [("tenthousand", 96, 54, 16), ("redchair", 64, 36, 32), ("spiral", 48, 27, 20),
+                                              ("spiral", 48, 27, 100)])
 def test_accumulate_then_finalize_gives_the_bytes_of_render(name, w, h, spp, gpu_scenes):
     """render_kernel_atomic_aa + finalize_kernel (draw.cu:13-92) as mirt_render_accumulate + mirt_finalize: all samples in one
-    call is the same sum tree as mirt_render -> identical bytes."""
+    call is the same sum tree as mirt_render -> identical bytes.  (100 samples: P = 128, the one-thread-per-pixel sum in both.)"""
     stl, raw = gpu_scenes(name)
     r8, rf = gpu_render(raw, w, h, spp)
     a8, acc = gpu_accumulate(raw, w, h, [(0, spp)], spp)

@@ -59,7 +59,7 @@ def build(force=False, verbose=False):
     hipcc = _hipcc()
     deps = _all_deps()
     extra = []
-    for var in ("MIRT_WAVES_PER_SIMD", "MIRT_STACK_LDS", "MIRT_WF_WAVES_PER_SIMD", "MIRT_WF_SHADE_WAVES", "MIRT_TRACE_BLOCK"):      # tuning experiments only; defaults live in render.hip
+    for var in ("MIRT_WAVES_PER_SIMD", "MIRT_STACK_LDS", "MIRT_WF_WAVES_PER_SIMD", "MIRT_WF_SHADE_WAVES", "MIRT_TRACE_BLOCK"):      # tuning experiments only; defaults live in render_plan.h and render.hip
         if os.environ.get(var):
             extra.append(f"-D{var}=" + os.environ[var])
     objs = []

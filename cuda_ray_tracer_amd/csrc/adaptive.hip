@@ -311,12 +311,8 @@ int select_pixels(const MirtRenderParams* p, const void* d_accum, const void* d_
   {
     std::lock_guard<std::mutex> lock(select_mu);
     SelectWs& ws = select_ws[std::make_pair(device, stream)];
-    if (ws.cap < need) {
-      MIRT_HIP(hipStreamSynchronize(stream));      // an earlier call on this stream may still be using the smaller buffer
-      hipFree(ws.blocks); ws.blocks = nullptr; ws.cap = 0;
-      MIRT_HIP(hipMalloc(&ws.blocks, 4 * need));
-      ws.cap = need;
-    }
+    const int rc = grow(ws.blocks, ws.cap, need, 4 * need, stream);
+    if (rc != MIRT_OK) return rc;
     blocks = ws.blocks;
   }
   SelectPred pr;

@@ -478,13 +478,7 @@ int mirt_get_stats(MirtScene* sc, MirtStats* out)
       MIRT_HIP(hipMemcpy(&ov, c.counters + 10, sizeof(ov), hipMemcpyDeviceToHost));
       sc->overflow_events += ov;
     }
-    if (c.used && !c.timed) {
-      MIRT_HIP(hipEventSynchronize(c.ev3));
-      float ms = 0.0f;
-      int rc = trace_ms_of(c, &ms);
-      if (rc != MIRT_OK) return rc;
-      sc->trace_ms_sum += ms; sc->trace_frames += 1; c.timed = true;
-    }
+    if (c.used) { int rc = fold_trace_time(sc, c); if (rc != MIRT_OK) return rc; }      // (finished: waited for above)
   }
   out->frames_timed = sc->trace_frames;
   out->trace_kernel_ms_mean = sc->trace_frames ? (float)(sc->trace_ms_sum / sc->trace_frames) : 0.0f;

@@ -28,6 +28,16 @@ int check_range(const char* who, const void* d_array, int first, int count, int 
   return MIRT_OK;
 }
 
+int check_frame(const char* who, const MirtRenderParams* p, int64_t npix, bool* go)
+{
+  *go = false;
+  if ((int64_t)p->width * p->height > 0x7fffffffll - 1234) { set_error(std::string(who) + ": frame too large for the 32-bit pixel seed"); return MIRT_ERR_ARG; }
+  if (npix == 0) return MIRT_OK;
+  if (npix >= 0x7fffffffll || (long long)p->stripe_rows * p->width >= 0x7fffffffll) { set_error(std::string(who) + ": part too large"); return MIRT_ERR_ARG; }
+  *go = true;
+  return MIRT_OK;
+}
+
 namespace {
 
 inline MirtVec3 v3(float x, float y, float z) { MirtVec3 v; v.x = x; v.y = y; v.z = z; return v; }

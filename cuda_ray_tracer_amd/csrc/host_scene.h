@@ -30,6 +30,9 @@ bool is_aligned(size_t n, const T*... p) { return ((... | (uintptr_t)p) & (n - 1
 // A range [first, first + count) of a scene's `total` spheres or triangles and the device array that gives or receives it
 // (mirt_scene_update_* / mirt_scene_get_*).  MIRT_OK with *go = false: nothing to do (count 0).
 int check_range(const char* who, const void* d_array, int first, int count, int total, size_t align, bool* go);
+// The frame and the part of it (npix pixels, render_num_pixels) that a call renders or makes rays for: both within the 32-bit
+// pixel seed and sample index.  MIRT_OK with *go = false: nothing to do (an empty part).
+int check_frame(const char* who, const MirtRenderParams* p, int64_t npix, bool* go);
 
 class HostScene {
 public:

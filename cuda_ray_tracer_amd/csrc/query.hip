@@ -182,16 +182,6 @@ __global__ void __launch_bounds__(QBLOCK) camera_rays_kernel(const RenderArgs a,
   rays[2 * i + 1] = make_float4(r.d.x, r.d.y, r.d.z, 0.0f);
 }
 
-int query_grid_blocks(int device)
-{
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess) return 1024;
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_rays_kernel<false>, QBLOCK, 0) != hipSuccess || per_cu < 1)
-    per_cu = QWAVES_PER_SIMD * 4 * 64 / QBLOCK;
-  return prop.multiProcessorCount * per_cu;
-}
-
 } // namespace
 
 int trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits, uint32_t flags, hipStream_t stream)
@@ -204,7 +194,8 @@ int trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits
   }
   if (!sc->built) { set_error("mirt_trace_rays: call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
   if (num_rays == 0) return MIRT_OK;
-  if (!sc->query_blocks) sc->query_blocks = query_grid_blocks(sc->device);      // per scene, i.e. per device
+  if (!sc->query_blocks && persistent_grid_blocks(sc->device, trace_rays_kernel<false>, QBLOCK, QWAVES_PER_SIMD * 4 * 64 / QBLOCK, &sc->query_blocks) != hipSuccess)
+    sc->query_blocks = 1024;      // per scene, i.e. per device
   QueryArgs q;
   q.rays = reinterpret_cast<const float4*>(d_rays);
   q.hits = reinterpret_cast<uint32_t*>(d_hits);
@@ -228,25 +219,19 @@ int camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, hipStrea
   if (npix < 0 || p->spp < 0) { set_error("mirt_camera_rays: bad parameters"); return MIRT_ERR_ARG; }
   if (npix > 0 && !d_rays) { set_error("mirt_camera_rays: null buffer"); return MIRT_ERR_ARG; }
   if (((uintptr_t)d_rays & 15u) != 0u) { set_error("mirt_camera_rays: d_rays must be 16-byte aligned"); return MIRT_ERR_ARG; }
-  if ((int64_t)p->width * p->height > 0x7fffffffll - 1234) { set_error("mirt_camera_rays: frame too large for the 32-bit pixel seed"); return MIRT_ERR_ARG; }
-  if (npix == 0) return MIRT_OK;
-  if (npix >= 0x7fffffffll || (long long)p->stripe_rows * p->width >= 0x7fffffffll) { set_error("mirt_camera_rays: part too large"); return MIRT_ERR_ARG; }
+  bool go = false;
+  int rc = check_frame("mirt_camera_rays", p, npix, &go);
+  if (rc != MIRT_OK || !go) return rc;
   RenderArgs a;
   memset(&a, 0, sizeof(a));
-  a.width = p->width; a.height = p->height; a.bounces = sc->d.bounces; a.spp = p->spp;
-  a.fisheye = sc->d.fisheye; a.panorama = sc->d.panorama;
-  a.dof_focus = sc->d.dof_focus; a.dof_lens = sc->d.dof_lens;
-  a.forward.x = sc->d.forward.x; a.forward.y = sc->d.forward.y; a.forward.z = sc->d.forward.z;
-  a.right.x = sc->d.right.x; a.right.y = sc->d.right.y; a.right.z = sc->d.right.z;
-  a.up.x = sc->d.up.x; a.up.y = sc->d.up.y; a.up.z = sc->d.up.z;
-  a.eye.x = sc->d.eye.x; a.eye.y = sc->d.eye.y; a.eye.z = sc->d.eye.z;
-  a.stripe_rows = p->stripe_rows; a.num_parts = p->num_parts; a.part = p->part;
+  fill_camera(a, sc, p);
+  a.spp = p->spp;
   // the primary ray consumes random numbers for the jitter (spp >= 1) and the lens (depth of field), nothing else
   a.needs_rng = (p->spp >= 1) || (sc->d.dof_focus != 0.0f && !sc->d.fisheye && !sc->d.panorama);
   if (a.needs_rng) {
     // spp > 1: sample 0's tables -- any cached sample table covers it (a render's larger one is not evicted); else the per-pixel
     // tables of the frame
-    int rc = ensure_rng_tables(&sc->rng, p->spp > 1 ? 1 : 0, (long long)p->width * p->height, stream, &a.rng, true);
+    rc = ensure_rng_tables(&sc->rng, p->spp > 1 ? 1 : 0, (long long)p->width * p->height, stream, &a.rng, true);
     if (rc != MIRT_OK) return rc;
   }
   const int blocks = (int)((npix + QBLOCK - 1) / QBLOCK);

@@ -35,21 +35,10 @@ namespace {
 constexpr int RBLOCK = 256;
 constexpr int MAX_SPP = 4096;         // resolve_kernel's partial-sum stack holds log2(4096) + 1 entries
 constexpr int MAX_SLAB_ARGS = 4;      // device copies of RenderArgs a context cycles through (one per slab in flight on its stream)
-// The trace kernel's waves never talk to each other, so a workgroup is one wave: a finished wave frees its slot (and its
-// 10 KB of LDS) at once instead of waiting for the slowest of four, which is what lets the next frame's waves move in
-// while this frame drains.
-#ifndef MIRT_TRACE_BLOCK
-#define MIRT_TRACE_BLOCK 64
-#endif
-constexpr int TRACE_BLOCK = MIRT_TRACE_BLOCK;
-constexpr int MAX_CHUNK_SHIFT = 8, MIN_CHUNK_SHIFT = 6;   // a wave takes 64..256 consecutive samples from the frame per atomic
+// (TRACE_BLOCK, STACK_LDS and the chunk sizes: render_plan.h, where the call plan reads them)
 #ifndef MIRT_WAVES_PER_SIMD
 #define MIRT_WAVES_PER_SIMD 4   // 128 VGPRs: measured best (2: 86 ms, 3: 76 ms, 4: 68 ms, 5: 79 ms on tenthousand 1080p16)
 #endif
-#ifndef MIRT_STACK_LDS
-#define MIRT_STACK_LDS 24
-#endif
-constexpr int STACK_LDS = MIRT_STACK_LDS;
 // The quantised walk found a triangle hit it is about to accept (scene_dev.h): does the reference's walk reach this leaf?  Yes,
 // provably, if the triangle's exact leaf box passes the order-independent clauses of hit_aabb_adapted (bvh_traversal.cu:11-44)
 // and the ray enters it before the hit: every ancestor's exact box contains the leaf box and the slab arithmetic is monotone in
@@ -593,16 +582,6 @@ void rng_cache_free(RngCache* rc)
   rc->A = nullptr; rc->B = nullptr; rc->K = nullptr; rc->R2 = nullptr; rc->key = -1;
 }
 
-static int grid_blocks(int device)
-{
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess) return 1024;
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_kernel<false, 8, false>, TRACE_BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 4 * 256 / TRACE_BLOCK;
-  return prop.multiProcessorCount * per_cu;
-}
-
-
 // One call of mirt_render / mirt_render_accumulate.  The part's pixels are rendered in slabs of at most 2^slab_log2 samples,
 // so the per-sample workspace is bounded (4 GiB by default) whatever the frame: BASELINE config 5 (3840x2160 x 256 spp,
 // 2.1 G samples) takes 8 slabs instead of a 34 GB buffer.  Each slab is a trace launch + a resolve launch; a slab boundary
@@ -614,373 +593,390 @@ static int grid_blocks(int device)
 //                    ax->list only the listed pixels are rendered: every launch hands out, through RenderArgs::sample_order, the
 //                    samples of the listed pixels of its slab (adaptive.hip) instead of the scene's measured order, to the same
 //                    trace kernels.  The workspace stays indexed by the slab's dense sample number.
-static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, void* d_rgba_f32, void* d_accum, int sample_first,
-                       int sample_count, hipStream_t stream, const AdaptiveArgs* ax = nullptr)
+// What the call decides without the device is plan_call's (render_plan.h); render_impl, at the end, carries the plan out
+// through the steps below, in this order.
+struct RenderCall {
+  MirtScene* sc; const MirtRenderParams* p;
+  void* d_rgba8; void* d_rgba_f32; void* d_accum; const AdaptiveArgs* ax;      // outputs; the list and moments of ..._accumulate_pixels
+  int sample_first, sample_count;
+  hipStream_t stream;
+  bool sparse() const { return ax && ax->list; }
+  bool count() const { return (p->flags & MIRT_RENDER_COUNTERS) != 0; }
+};
+
+static SceneFacts scene_facts(const MirtScene* sc)
 {
-  const char* who = ax ? "mirt_render_accumulate_pixels" : (d_accum ? "mirt_render_accumulate" : "mirt_render");
-  const bool sparse = ax && ax->list;
-  if (!sc->built) { set_error(std::string(who) + ": call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
-  const int64_t npix = local_pixels(p);
-  if (npix < 0 || p->spp < 0 || (!d_rgba8 && !d_accum)) { set_error(std::string(who) + ": bad parameters"); return MIRT_ERR_ARG; }
-  if (sample_first < 0 || sample_count < 1 || (long long)sample_first + sample_count > MAX_SPP) {
+  SceneFacts f;
+  f.N = sc->N; f.Nt = sc->Nt; f.grid_ok = sc->grid_ok;
+  f.has_quantised = sc->root_ref_q != REF_NONE; f.has_wide = sc->root_ref_w != REF_NONE;
+  f.colors_finite = sc->colors_finite; f.any_trans = sc->any_trans; f.any_rough = sc->any_rough;
+  f.gi = sc->d.gi; f.bounces = sc->d.bounces; f.num_suns = sc->d.num_suns; f.num_bulbs = sc->d.num_bulbs;
+  return f;
+}
+
+// step 1: the call's arguments.  MIRT_OK with *npix = 0: an empty part, nothing to do.
+static int check_call(const RenderCall& c, int64_t* npix)
+{
+  const char* who = c.ax ? "mirt_render_accumulate_pixels" : (c.d_accum ? "mirt_render_accumulate" : "mirt_render");
+  *npix = 0;
+  if (!c.sc->built) { set_error(std::string(who) + ": call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
+  const int64_t n = local_pixels(c.p);
+  if (n < 0 || c.p->spp < 0 || (!c.d_rgba8 && !c.d_accum)) { set_error(std::string(who) + ": bad parameters"); return MIRT_ERR_ARG; }
+  if (c.sample_first < 0 || c.sample_count < 1 || (long long)c.sample_first + c.sample_count > MAX_SPP) {
     set_error(std::string(who) + ": more than 4096 samples per pixel (mirt_render_accumulate renders any number in several calls of at most 4096)"); return MIRT_ERR_ARG;
   }
-  if ((int64_t)p->width * p->height > 0x7fffffffll - 1234) { set_error(std::string(who) + ": frame too large for the 32-bit pixel seed"); return MIRT_ERR_ARG; }
-  if (npix == 0) return MIRT_OK;
-  if (npix >= 0x7fffffffll || (long long)p->stripe_rows * p->width >= 0x7fffffffll) { set_error(std::string(who) + ": part too large"); return MIRT_ERR_ARG; }
-  if (sparse && sc->opt.wavefront != 0) { set_error(std::string(who) + ": a pixel list is not supported with wavefront = 1 (the trace / shade kernel pair does not hand samples out through a table)"); return MIRT_ERR_ARG; }
-  const bool per_pixel_seed = d_accum != nullptr || p->spp > 1;      // draw.cu:74,162 vs draw.cu:105
-  const int sppe = sample_count;
-  const Options& opt = sc->opt;
-  // slabs: whole pixels, at most 2^slab_log2 samples each
-  long long slab_pixels = (1ll << opt.slab_log2) / sppe;
-  if (slab_pixels < 1) slab_pixels = 1;
-  if (slab_pixels > npix) slab_pixels = npix;
-  const int nslabs = (int)((npix + slab_pixels - 1) / slab_pixels);
-  const long long slab_samples_max = slab_pixels * sppe;
-  // (a sparse launch hands out at most this many samples: the listed pixels of one slab)
-  const long long listed_max = sparse ? (ax->num_listed < slab_pixels ? ax->num_listed : slab_pixels) : 0;
-  const long long launch_samples_max = sparse ? listed_max * sppe : slab_samples_max;
-  const bool count = (p->flags & MIRT_RENDER_COUNTERS) != 0;
+  bool go = false;
+  const int rc = check_frame(who, c.p, n, &go);
+  if (rc != MIRT_OK || !go) return rc;
+  if (c.sparse() && c.sc->opt.wavefront != 0) { set_error(std::string(who) + ": a pixel list is not supported with wavefront = 1 (the trace / shade kernel pair does not hand samples out through a table)"); return MIRT_ERR_ARG; }
+  *npix = n;
+  return MIRT_OK;
+}
 
-  if (!sc->grid_blocks) sc->grid_blocks = grid_blocks(sc->device);      // per scene, i.e. per device
+// step 2: the persistent grid of the call's trace launches
+static int size_grid(MirtScene* sc, const CallPlan& pl, bool count, hipStream_t stream)
+{
+  if (!sc->grid_blocks && persistent_grid_blocks(sc->device, trace_kernel<false, 8, false>, TRACE_BLOCK, 4 * 256 / TRACE_BLOCK, &sc->grid_blocks) != hipSuccess)
+    sc->grid_blocks = 1024;      // per scene, i.e. per device
   const int blocks_cached = sc->grid_blocks;
-  long long want_blocks = (launch_samples_max + TRACE_BLOCK - 1) / TRACE_BLOCK;
+  const long long want_blocks = (pl.launch_samples_max + TRACE_BLOCK - 1) / TRACE_BLOCK;
   int blocks = (int)(want_blocks < blocks_cached ? want_blocks : blocks_cached);
   // A small frame (one GPU's stripe set of an 8-GPU job) rendered while another frame is in flight gets half the grid:
   // every wave ends with a drain -- its last samples, few live lanes, 0.5-2.5 ms -- during which it holds its slot, and
   // with two half-grid frames resident at a time there are half as many drains per frame (1/8 of 1080p x 16: 5.8 -> 5.4
   // ms per frame; no gain from 1/4 of a frame up, a loss for a frame rendered alone).
-  if (!count && blocks == blocks_cached && launch_samples_max < 20ll * blocks_cached * TRACE_BLOCK) {
+  if (!count && blocks == blocks_cached && pl.launch_samples_max < 20ll * blocks_cached * TRACE_BLOCK) {
     for (int i = 0; i < MIRT_MAX_FRAMES; ++i) {
       const RenderCtx& c = sc->ctx[i];
       if (c.used && c.stream != stream && hipEventQuery(c.ev3) == hipErrorNotReady) { blocks = blocks_cached > 1 ? blocks_cached / 2 : 1; break; }   // (a frame on this same stream does not overlap)
     }
   }
-  if (opt.trace_waves >= 1 && opt.trace_waves <= blocks_cached) blocks = opt.trace_waves;
-  const size_t gthreads = (size_t)blocks * TRACE_BLOCK;
+  if (sc->opt.trace_waves >= 1 && sc->opt.trace_waves <= blocks_cached) blocks = sc->opt.trace_waves;
+  return blocks;
+}
 
-  // this frame's context; wait for the frame that used it MIRT_MAX_FRAMES renders ago (the frame counter moves only once
-  // the frame is actually issued, below)
+// the finished frame's trace-kernel time goes into the running mean (mirt_get_stats), once
+int fold_trace_time(MirtScene* sc, RenderCtx& cx)
+{
+  if (cx.timed) return MIRT_OK;
+  float ms = 0.0f;
+  int rc = trace_ms_of(cx, &ms);
+  if (rc != MIRT_OK) return rc;
+  sc->trace_ms_sum += ms; sc->trace_frames += 1; cx.timed = true;
+  return MIRT_OK;
+}
+
+// step 3: this frame's context; wait for the frame that used it MIRT_MAX_FRAMES renders ago (the frame counter moves only
+// once the frame is actually issued, at the end of render_impl)
+static int take_context(MirtScene* sc, RenderCtx** out)
+{
   RenderCtx& cx = sc->ctx[sc->frame_no % MIRT_MAX_FRAMES];
-  if (cx.used) {
-    MIRT_HIP(hipEventSynchronize(cx.ev3));
-    if (!cx.timed) {   // fold the finished frame's trace-kernel time into the running mean (mirt_get_stats)
-      float ms = 0.0f;
-      int rc = trace_ms_of(cx, &ms);
-      if (rc != MIRT_OK) return rc;
-      sc->trace_ms_sum += ms; sc->trace_frames += 1; cx.timed = true;
-    }
-  }
-  // workspace
-  if (cx.samples_cap < (size_t)slab_samples_max) {
-    MIRT_HIP(hipStreamSynchronize(stream));
-    hipFree(cx.samples); cx.samples = nullptr; cx.samples_cap = 0;
-    MIRT_HIP(hipMalloc(&cx.samples, sizeof(float4) * (size_t)slab_samples_max));
-    cx.samples_cap = (size_t)slab_samples_max;
-  }
-  const size_t spill_need = (size_t)STACK_TOTAL_WIDE * gthreads;      // (the wide walk pushes up to three entries per two levels)
-  if (cx.spill_cap < spill_need) {
-    MIRT_HIP(hipStreamSynchronize(stream));
-    hipFree(cx.stack_spill); cx.stack_spill = nullptr; cx.spill_cap = 0;
-    MIRT_HIP(hipMalloc(&cx.stack_spill, sizeof(uint32_t) * spill_need));
-    cx.spill_cap = spill_need;
-  }
-  if (sparse) {
-    const size_t blocks_need = sparse_blocks_words(ax->num_listed);
-    if (cx.sp_list_cap < (size_t)ax->num_listed || cx.sp_table_cap < (size_t)launch_samples_max || cx.sp_blocks_cap < blocks_need) {
-      MIRT_HIP(hipStreamSynchronize(stream));
-      if (cx.sp_list_cap < (size_t)ax->num_listed) {
-        hipFree(cx.sp_list); cx.sp_list = nullptr; cx.sp_list_cap = 0;
-        MIRT_HIP(hipMalloc(&cx.sp_list, 4 * (size_t)ax->num_listed));
-        cx.sp_list_cap = (size_t)ax->num_listed;
-      }
-      if (cx.sp_table_cap < (size_t)launch_samples_max) {
-        hipFree(cx.sp_table); cx.sp_table = nullptr; cx.sp_table_cap = 0;
-        MIRT_HIP(hipMalloc(&cx.sp_table, 4 * (size_t)launch_samples_max));
-        cx.sp_table_cap = (size_t)launch_samples_max;
-      }
-      if (cx.sp_blocks_cap < blocks_need) {
-        hipFree(cx.sp_blocks); cx.sp_blocks = nullptr; cx.sp_blocks_cap = 0;
-        MIRT_HIP(hipMalloc(&cx.sp_blocks, 4 * blocks_need));
-        cx.sp_blocks_cap = blocks_need;
-      }
-    }
-  }
-  const bool need_pending = sc->any_trans || sc->d.gi != 0;
-  const int pending_slots = need_pending ? 2 * (sc->d.bounces + (sc->d.gi > 0 ? sc->d.gi : 0) + 2) : 0;
-  const size_t pending_need = (size_t)pending_slots * PENDING_WORDS * gthreads;
-  if (cx.pending_cap < pending_need) {
-    MIRT_HIP(hipStreamSynchronize(stream));
-    hipFree(cx.pending); cx.pending = nullptr; cx.pending_cap = 0;
-    MIRT_HIP(hipMalloc(&cx.pending, sizeof(float) * pending_need));
-    cx.pending_cap = pending_need;
-  }
+  *out = &cx;
+  if (!cx.used) return MIRT_OK;
+  MIRT_HIP(hipEventSynchronize(cx.ev3));
+  return fold_trace_time(sc, cx);
+}
 
-  RenderArgs a;
+// step 4: the context's buffers, at least as large as this call needs them
+static int ensure_workspace(const RenderCall& c, RenderCtx& cx, const CallPlan& pl, int blocks)
+{
+  const hipStream_t stream = c.stream;
+  const size_t gthreads = (size_t)blocks * TRACE_BLOCK;
+  const size_t samples = (size_t)pl.slab_samples_max;
+  const size_t spill_need = (size_t)STACK_TOTAL_WIDE * gthreads;      // (the wide walk pushes up to three entries per two levels)
+  const size_t pending_need = (size_t)pl.pending_slots * PENDING_WORDS * gthreads;
+  int rc = grow(cx.samples, cx.samples_cap, samples, sizeof(float4) * samples, stream);
+  if (rc == MIRT_OK) rc = grow(cx.stack_spill, cx.spill_cap, spill_need, sizeof(uint32_t) * spill_need, stream);
+  if (rc == MIRT_OK && c.sparse()) {
+    const size_t listed = (size_t)c.ax->num_listed, table = (size_t)pl.launch_samples_max, blocks_need = sparse_blocks_words(c.ax->num_listed);
+    rc = grow(cx.sp_list, cx.sp_list_cap, listed, 4 * listed, stream);
+    if (rc == MIRT_OK) rc = grow(cx.sp_table, cx.sp_table_cap, table, 4 * table, stream);
+    if (rc == MIRT_OK) rc = grow(cx.sp_blocks, cx.sp_blocks_cap, blocks_need, 4 * blocks_need, stream);
+  }
+  if (rc == MIRT_OK) rc = grow(cx.pending, cx.pending_cap, pending_need, sizeof(float) * pending_need, stream);
+  if (rc != MIRT_OK) return rc;
+  if (c.sc->opt.wavefront == 0 && !cx.args_dev) MIRT_HIP(hipMalloc(&cx.args_dev, sizeof(RenderArgs) * MAX_SLAB_ARGS));
+  // one event pair per trace launch: a call of several slabs reports the SUM of its launches, not a bracket that would take in
+  // the resolve kernels between them
+  while ((int)cx.slab_ev.size() < 2 * pl.nslabs) { hipEvent_t e = nullptr; MIRT_HIP(hipEventCreate(&e)); cx.slab_ev.push_back(e); }
+  return MIRT_OK;
+}
+
+// step 5: the kernel arguments every slab of the call shares (the slab's own are launch_slab's; the hand-out order's follow)
+static int fill_args(const RenderCall& c, RenderCtx& cx, const CallPlan& pl, int chunk_shift, RenderArgs& a, HotArgs& h)
+{
+  MirtScene* sc = c.sc;
+  const Options& opt = sc->opt;
   memset(&a, 0, sizeof(a));
-  a.width = p->width; a.height = p->height; a.bounces = sc->d.bounces; a.gi = sc->d.gi;
-  a.spp = d_accum ? (p->spp > 1 ? p->spp : 2) : p->spp;      // only "is it >= 1" matters to the kernel: jittered samples (draw.cu:78-84,110-118,165-171)
-  a.fisheye = sc->d.fisheye; a.panorama = sc->d.panorama;
-  a.dof_focus = sc->d.dof_focus; a.dof_lens = sc->d.dof_lens; a.expose = sc->d.expose;
-  a.forward.x = sc->d.forward.x; a.forward.y = sc->d.forward.y; a.forward.z = sc->d.forward.z;
-  a.right.x = sc->d.right.x; a.right.y = sc->d.right.y; a.right.z = sc->d.right.z;
-  a.up.x = sc->d.up.x; a.up.y = sc->d.up.y; a.up.z = sc->d.up.z;
-  a.eye.x = sc->d.eye.x; a.eye.y = sc->d.eye.y; a.eye.z = sc->d.eye.z;
-  a.stripe_rows = p->stripe_rows; a.num_parts = p->num_parts; a.part = p->part;
-  a.sample_first = sample_first; a.sample_count = sample_count; a.seed_per_pixel = per_pixel_seed ? 1 : 0;
+  fill_camera(a, sc, c.p);
+  a.gi = sc->d.gi; a.spp = pl.args_spp; a.expose = sc->d.expose;
+  a.sample_first = c.sample_first; a.sample_count = c.sample_count; a.seed_per_pixel = pl.per_pixel_seed ? 1 : 0;
   a.nodes = sc->nodes; a.unit_prim = sc->unit_prim; a.mats = sc->mats;
-  // Quantised node records: single-kernel path, any order but the reference's own.  A sphere-only scene: the 32-byte records,
-  // always.  A scene with triangles: the wide records -- the reference's order at every node, so traversal = 1 only -- when the
-  // scene is large enough for memory to matter (qnodes = 1: N >= 65536, the exact records no longer fit an L2; redchair.txt's
-  // 1.7 k primitives are 12 % faster on the exact records, the 2 M-primitive scene 25 % faster on the wide ones) or always (2).
-  const bool notri = sc->Nt == 0;
-  const bool qwant = opt.qnodes != 0 && opt.wavefront == 0;
-  // (and only if the grid of the quantised records resolves the scene's coordinates: grid_ok, lbvh_build.hip -- a scene that
-  // sits hundreds of its own extents away from the world origin walks the exact records, in the reference's order)
-  const bool qn = sc->grid_ok && (notri ? (qwant && opt.traversal >= 1 && sc->root_ref_q != REF_NONE)
-                                        : (qwant && opt.traversal == 1 && sc->root_ref_w != REF_NONE && (opt.qnodes >= 2 || sc->N >= 65536)));
-  // kernels specialised for what the scene does not have (SPEC_*, shade_common.h)
-  // (a scene with a non-finite colour gets the general kernels: only they carry the colour * 0 terms, gi_zero_term)
-  const bool specialise = opt.specialise != 0 && sc->colors_finite;
-  const bool nobulb = specialise && sc->d.num_bulbs == 0, nopend = specialise && !need_pending;
-  a.root_ref = qn ? (notri ? sc->root_ref_q : sc->root_ref_w) : sc->root_ref; a.num_spheres = sc->Ns; a.num_prims = sc->N;
-  a.qparams = qn ? sc->qparams : nullptr;
+  a.root_ref = pl.qn ? (pl.notri ? sc->root_ref_q : sc->root_ref_w) : sc->root_ref; a.num_spheres = sc->Ns; a.num_prims = sc->N;
+  a.qparams = pl.qn ? sc->qparams : nullptr;
   a.tri_boxes = sc->tri_boxes;
   a.prim_base16 = sc->prim_base / 16u;
-  // traversal = 1: near child first on the quantised records of a sphere-only scene, nowhere else.  Over the exact boxes the
-  // reordered walk can cull a box over a sphere whose hit distance rounds below that box's entry distance (one ulp is enough; the
-  // reference, in its order, gets there first): 13 of 4 000 far-camera fuzz scenes differed by a pixel or a ray.  The quantised
-  // boxes are rounded outwards by more than that rounding as long as the grid resolves it (grid_ok, a condition of qn) -- no differing byte
-  // in 10 000 sphere scenes, 3 000 of them far-camera ones.  Everything else walks in the reference's order.
-  a.swap_mask = opt.traversal == 1 ? ((qn && notri) ? NODE_SWAP_PURE : 0u) : (opt.traversal == 2 ? NODE_SWAP_ANY : 0u);
-  a.skip_unlit = (opt.skip_unlit != 0 && sc->colors_finite && sc->d.num_suns + sc->d.num_bulbs <= 32) ? 1 : 0;
-  a.shadow_anyhit = opt.shadow_anyhit != 0 ? 1 : 0;
+  a.swap_mask = pl.swap_mask; a.skip_unlit = pl.skip_unlit; a.shadow_anyhit = pl.shadow_anyhit;
+  a.reach_check = pl.reach_check;
+  a.reach_slack = 4.76837158203125e-07f * sc->coord_max;
   a.nonfinite_colours = sc->colors_finite ? 0 : 1;
   a.planes = sc->planes; a.num_planes = sc->d.num_planes;
   a.suns = sc->suns; a.num_suns = sc->d.num_suns;
   a.bulbs = sc->bulbs; a.num_bulbs = sc->d.num_bulbs;
   // random numbers are consumed only by jitter (spp >= 1), depth of field, rough normals and GI
-  a.needs_rng = (a.spp >= 1) || (sc->d.dof_focus != 0.0f && !sc->d.fisheye && !sc->d.panorama) || sc->any_rough || sc->d.gi != 0;
+  a.needs_rng = (a.spp >= 1) || (sc->d.dof_focus != 0.0f && !sc->d.fisheye && !sc->d.panorama) || pl.shading_rng;
   if (a.needs_rng) {
-    int rc = ensure_rng_tables(&sc->rng, per_pixel_seed ? sample_first + sample_count : 0, (long long)p->width * p->height, stream, &a.rng, d_accum != nullptr);
+    int rc = ensure_rng_tables(&sc->rng, pl.rng_sample_tables, (long long)c.p->width * c.p->height, c.stream, &a.rng, c.d_accum != nullptr);
     if (rc != MIRT_OK) return rc;
   }
   a.samples = cx.samples;
   a.stack_spill = cx.stack_spill;
-  a.pending = cx.pending; a.pending_slots = pending_slots;
-  a.counters = count ? cx.counters : nullptr;
+  a.pending = cx.pending; a.pending_slots = pl.pending_slots;
+  a.counters = c.count() ? cx.counters : nullptr;
   a.overflow = cx.counters + 9;
-  a.lds_depth = (opt.stack_lds_depth >= 0 && opt.stack_lds_depth <= STACK_LDS) ? opt.stack_lds_depth : STACK_LDS;   // tests force the spill path
-  // Thresholds of the two expensive divergent pieces of work, measured per kind of kernel (round 3, tools/r03_i.sh, r03_x.sh): lanes
-  // wait to shade until refill_k of them do, lanes without a sample until init_k of them do.  Sphere-only scenes 32 / 10; wide
-  // records (2 M-primitive scene) 24 / 8; exact records (redchair.txt) 64 / 64 -- with the samples handed out by cost class
-  // (sched = 2) the lanes of a wave run samples of one kind, and redchair.txt's short ray trees are fastest in lock step: the whole
-  // wave traverses, the whole wave shades, the whole wave takes 64 new samples (1080p16: 20.6 ms at 52 / 48, 18.1 at 64 / 64;
-  // tenthousand.txt's deep reflection chains want the opposite: 28.0 ms at 64 / 64 against 21.7).  Refilling finished lanes at
-  // every shade phase (init_k = 1, rounds 1-2) cost redchair.txt 14 % of its frame, the sphere scenes 1.5 %.
-  a.refill_k = opt.refill_k > 0 ? opt.refill_k : (qn ? (notri ? 32 : 24) : 64);
-  a.drain_lanes = opt.drain_lanes;
-  const int init_k = opt.init_k > 0 ? opt.init_k : (qn ? (notri ? 10 : 8) : 64);
-  a.init_k = init_k < a.refill_k ? init_k : a.refill_k;      // (<= refill_k: lanes waiting for a sample count as waiting in the loop header)
-  a.batch_k = opt.batch_k;
-
-  // ---- longest-first chunk order (single-kernel path, one-slab calls) ------------------------------------------------
-  // chunk size: 256 samples, smaller for a small (part of a) frame so that every wave still gets a dozen chunks or more --
-  // with four chunks per wave (1/8 of a 1080p frame) the waves finished up to a chunk apart
-  int chunk_shift = MAX_CHUNK_SHIFT;
-  while (chunk_shift > MIN_CHUNK_SHIFT && (launch_samples_max >> chunk_shift) < 16ll * blocks * (TRACE_BLOCK / 64)) --chunk_shift;
-  if (opt.chunk_shift >= 4) chunk_shift = opt.chunk_shift;
+  a.work_counter = cx.counters + 8;
+  a.lds_depth = pl.lds_depth;
+  a.refill_k = opt.wavefront != 0 ? opt.wf_refill_k : pl.refill_k;
+  a.drain_lanes = opt.drain_lanes; a.init_k = pl.init_k; a.batch_k = opt.batch_k;
   a.chunk_shift = chunk_shift;
-  const size_t nchunks = (size_t)((slab_samples_max + (1ll << chunk_shift) - 1) >> chunk_shift);
-  // sched = 1 (by chunk): one-slab calls only; sched = 2 (by sample): any call
-  const bool wavefront = opt.wavefront != 0;
-  // (a sparse call is handed out in list order: it neither measures an order nor uses one, and leaves the chunk orders and the
-  // scene's by-sample table -- which belong to the dense shape rendered last -- as they are)
-  const bool sched = opt.sched == 1 && nslabs == 1 && !wavefront && !sparse;
-  if (sched && cx.chunk_cap < nchunks) {
-    MIRT_HIP(hipDeviceSynchronize());   // a frame on another stream may still be reading one of these orders
+  h.nodes = a.nodes; h.root_ref = a.root_ref; h.swap_mask = a.swap_mask; h.qparams = a.qparams;
+  h.planes = a.planes; h.num_planes = a.num_planes; h.suns = a.suns; h.num_suns = a.num_suns; h.bulbs = a.bulbs; h.num_bulbs = a.num_bulbs; h.shadow_anyhit = a.shadow_anyhit;
+  h.stack_spill = a.stack_spill; h.lds_depth = a.lds_depth; h.refill_k = pl.refill_k; h.batch_k = a.batch_k; h.drain_lanes = a.drain_lanes;
+  h.reach_check = a.reach_check; h.leaf_k = pl.leaf_k; h.reps = pl.reps;
+  return MIRT_OK;
+}
+
+// ---- step 6a, sched = 1: longest-first CHUNK order (single-kernel path, one-slab calls), per context ---------------------
+// The newest finished frame with the same sample count (and chunk size) that MEASURED its chunks provides the order; a frame
+// that is still running does not.  The scene is immutable and samples are seeded by pixel and sample index only, so a frame's
+// chunk costs are the same every time: once an order exists for this frame size it is reused, and the frame neither stamps
+// costs nor sorts them again (the sort took 0.34 ms of a 24 ms frame, on the stream's critical path).
+// Returns the order in *order, or null: this frame measures one (chunk_order_finish).
+static int chunk_order_find(MirtScene* sc, RenderCtx& cx, size_t nchunks, long long okey, const uint32_t** order)
+{
+  if (cx.chunk_cap < nchunks) {
+    MIRT_HIP(hipDeviceSynchronize());   // (not grow(): a frame on another stream may still be reading one of these orders)
     hipFree(cx.chunk_cost); cx.chunk_cost = nullptr; cx.chunk_cap = 0; cx.order_key = -1;
     for (uint32_t*& o : cx.order_out) { hipFree(o); o = nullptr; }
     MIRT_HIP(hipMalloc(&cx.chunk_cost, 4 * nchunks));
     for (uint32_t*& o : cx.order_out) MIRT_HIP(hipMalloc(&o, 4 * nchunks));
     cx.chunk_cap = nchunks;
   }
-  // The newest finished frame with the same sample count (and chunk size) that MEASURED its chunks provides the order; a frame
-  // that is still running does not.  The scene is immutable and samples are seeded by pixel and sample index only, so a frame's
-  // chunk costs are the same every time: once an order exists for this frame size it is reused, and the frame neither stamps
-  // costs nor sorts them again (the sort took 0.34 ms of a 24 ms frame, on the stream's critical path).
-  const long long okey = slab_samples_max * 16 + chunk_shift;
-  const uint32_t* order = nullptr;
-  if (sched) {
-    unsigned long long best = 0;
-    for (int i = 0; i < MIRT_MAX_FRAMES; ++i) {
-      RenderCtx& c = sc->ctx[i];
-      if (&c == &cx || !c.used || c.order_key != okey || c.order_frame <= best) continue;
-      if (hipEventQuery(c.order_ev) != hipSuccess) continue;
-      best = c.order_frame; order = c.order_out[(c.order_writes - 1) % RenderCtx::ORDER_BUFS];
-    }
-    if (!order && cx.used && cx.order_key == okey) order = cx.order_out[(cx.order_writes - 1) % RenderCtx::ORDER_BUFS];   // cx's own earlier frame (finished: synchronised above)
+  unsigned long long best = 0;
+  *order = nullptr;
+  for (int i = 0; i < MIRT_MAX_FRAMES; ++i) {
+    RenderCtx& c = sc->ctx[i];
+    if (&c == &cx || !c.used || c.order_key != okey || c.order_frame <= best) continue;
+    if (hipEventQuery(c.order_ev) != hipSuccess) continue;
+    best = c.order_frame; *order = c.order_out[(c.order_writes - 1) % RenderCtx::ORDER_BUFS];
   }
-  // sched = 2 (default): the same idea by SAMPLE -- the samples of every launch in order of decreasing cost class, positions within
-  // a class kept (a stable one-byte radix pass: neighbours in the frame stay neighbours in the hand-out, and the lanes of a wave
-  // work on samples of one kind).  One table per scene (4 B per sample of the call, at most 12 GiB), for the call shape rendered
-  // last; measured by the first call of that shape (counting kernels + one sort per launch), reused afterwards.  Against the
-  // chunk order: a 1/8 stripe share of the headline frame 4.16 -> 3.22 ms alone (its last expensive samples no longer start
-  // late), redchair.txt 1080p16 23.8 -> 20.5 ms, tenthousand.txt 22.5 -> 21.7.
-  const long long total_samples = (long long)npix * sppe;
-  const bool by_sample = opt.sched == 2 && !wavefront && !sparse && slab_samples_max < 0x7fffffffll && total_samples <= (3ll << 30);
-  bool measure_samples = false, ordered_samples = false;
-  a.sample_order = nullptr; a.sample_key = nullptr;
-  if (by_sample) {
-    order = nullptr;
-    if (sc->so_busy && hipEventQuery(sc->so_ev) == hipSuccess) sc->so_busy = false;      // the measurement in flight has landed
-    // (the table is a permutation of every launch's sample range: valid for exactly this total and this slab size)
-    if (sc->so_key == okey && sc->so_total == total_samples && !sc->so_busy) ordered_samples = true;
-    else if (!sc->so_busy) {
-      // (no frame in flight reads the old table once every context's frame has finished: wait for them before rewriting it)
-      for (int i = 0; i < MIRT_MAX_FRAMES; ++i) if (sc->ctx[i].used) MIRT_HIP(hipEventSynchronize(sc->ctx[i].ev3));
-      if (sc->so_cap < (size_t)total_samples || sc->so_slab_cap < (size_t)slab_samples_max) {
-        hipFree(sc->so_order); hipFree(sc->so_keys); hipFree(sc->so_keys2); hipFree(sc->so_ws);
-        sc->so_order = sc->so_keys = sc->so_keys2 = sc->so_ws = nullptr; sc->so_cap = 0; sc->so_slab_cap = 0; sc->so_key = -1;
-        // (the table is an optimisation: without the memory for it the call is rendered in frame order)
-        const bool got = hipMalloc(&sc->so_order, 4 * (size_t)total_samples) == hipSuccess && hipMalloc(&sc->so_keys, 4 * (size_t)slab_samples_max) == hipSuccess &&
-                         hipMalloc(&sc->so_keys2, 4 * (size_t)slab_samples_max) == hipSuccess && hipMalloc(&sc->so_ws, 4 * sort_low_byte_ws_words(slab_samples_max)) == hipSuccess;
-        if (got) { sc->so_cap = (size_t)total_samples; sc->so_slab_cap = (size_t)slab_samples_max; }
-        else {
-          (void)hipGetLastError();
-          hipFree(sc->so_order); hipFree(sc->so_keys); hipFree(sc->so_keys2); hipFree(sc->so_ws);
-          sc->so_order = sc->so_keys = sc->so_keys2 = sc->so_ws = nullptr;
-        }
-      }
-      if (sc->so_cap >= (size_t)total_samples && sc->so_slab_cap >= (size_t)slab_samples_max) {
-        measure_samples = true;
-        sc->so_key = -1;
-        sc->so_pending_key = okey; sc->so_total = total_samples;
-      }
+  if (!*order && cx.used && cx.order_key == okey) *order = cx.order_out[(cx.order_writes - 1) % RenderCtx::ORDER_BUFS];   // cx's own earlier frame (finished: take_context waited)
+  return MIRT_OK;
+}
+
+// The order for later frames.  It overwrites the buffer this context wrote three orders ago; every frame that could have read
+// that one has finished -- the host waited for each of them when it reused their contexts.
+static int chunk_order_finish(RenderCtx& cx, size_t nchunks, long long okey, hipStream_t stream)
+{
+  uint32_t* out = cx.order_out[cx.order_writes % RenderCtx::ORDER_BUFS];
+  hipLaunchKernelGGL(order_kernel, dim3(1), dim3(SORT_BINS), 0, stream, cx.chunk_cost, (uint32_t)nchunks, out);
+  MIRT_HIP(hipGetLastError());
+  MIRT_HIP(hipEventRecord(cx.order_ev, stream));
+  cx.order_key = okey;
+  cx.order_frame = cx.frame_id;
+  ++cx.order_writes;
+  return MIRT_OK;
+}
+
+// ---- step 6b, sched = 2 (default): the same idea by SAMPLE -- the samples of every launch in order of decreasing cost class,
+// positions within a class kept (a stable one-byte radix pass: neighbours in the frame stay neighbours in the hand-out, and the
+// lanes of a wave work on samples of one kind).  One table per scene (4 B per sample of the call, at most 12 GiB), for the call
+// shape rendered last; measured by the first call of that shape (counting kernels + one sort per launch), reused afterwards.
+// Against the chunk order: a 1/8 stripe share of the headline frame 4.16 -> 3.22 ms alone (its last expensive samples no longer
+// start late), redchair.txt 1080p16 23.8 -> 20.5 ms, tenthousand.txt 22.5 -> 21.7.
+// *ordered: the table serves this call.  *measure: this call measures it (sample_table_finish).  Neither: frame order.
+static int sample_table_find(MirtScene* sc, const CallPlan& pl, long long okey, bool* ordered, bool* measure)
+{
+  const size_t total = (size_t)pl.total_samples, slab = (size_t)pl.slab_samples_max;
+  *ordered = *measure = false;
+  if (sc->so_busy && hipEventQuery(sc->so_ev) == hipSuccess) sc->so_busy = false;      // the measurement in flight has landed
+  if (sc->so_busy) return MIRT_OK;
+  // (the table is a permutation of every launch's sample range: valid for exactly this total and this slab size)
+  if (sc->so_key == okey && sc->so_total == pl.total_samples) { *ordered = true; return MIRT_OK; }
+  // (no frame in flight reads the old table once every context's frame has finished: wait for them before rewriting it)
+  for (int i = 0; i < MIRT_MAX_FRAMES; ++i) if (sc->ctx[i].used) MIRT_HIP(hipEventSynchronize(sc->ctx[i].ev3));
+  if (sc->so_cap < total || sc->so_slab_cap < slab) {
+    hipFree(sc->so_order); hipFree(sc->so_keys); hipFree(sc->so_keys2); hipFree(sc->so_ws);
+    sc->so_order = sc->so_keys = sc->so_keys2 = sc->so_ws = nullptr; sc->so_cap = 0; sc->so_slab_cap = 0; sc->so_key = -1;
+    // (the table is an optimisation: without the memory for it the call is rendered in frame order)
+    const bool got = hipMalloc(&sc->so_order, 4 * total) == hipSuccess && hipMalloc(&sc->so_keys, 4 * slab) == hipSuccess &&
+                     hipMalloc(&sc->so_keys2, 4 * slab) == hipSuccess && hipMalloc(&sc->so_ws, 4 * sort_low_byte_ws_words(pl.slab_samples_max)) == hipSuccess;
+    if (!got) {
+      (void)hipGetLastError();
+      hipFree(sc->so_order); hipFree(sc->so_keys); hipFree(sc->so_keys2); hipFree(sc->so_ws);
+      sc->so_order = sc->so_keys = sc->so_keys2 = sc->so_ws = nullptr;
+      return MIRT_OK;
     }
+    sc->so_cap = total; sc->so_slab_cap = slab;
   }
-  const bool measure = (sched && !by_sample && !order) || measure_samples;
-  a.chunk_order = order;
-  a.chunk_cost = (measure && !by_sample) ? cx.chunk_cost : nullptr;
+  *measure = true;
+  sc->so_key = -1;
+  sc->so_pending_key = okey; sc->so_total = pl.total_samples;
+  return MIRT_OK;
+}
+
+static int sample_table_finish(MirtScene* sc, hipStream_t stream)
+{
+  MIRT_HIP(hipEventRecord(sc->so_ev, stream));
+  sc->so_key = sc->so_pending_key; sc->so_busy = true;
+  return MIRT_OK;
+}
+
+// one instantiation per form of the random-number tables (device_common.h, xw_init), per node format and per specialisation:
+// 2 (counting) x 2 (tables) x 8 = 32 kernels
+using TraceKernel = void (*)(const RenderArgs*, HotArgs);
+template <bool C, bool Q, int P>
+static TraceKernel trace_kernel_tables(bool t8) { return t8 ? trace_kernel<C, 8, Q, P> : trace_kernel<C, 4, Q, P>; }
+template <bool C>
+static TraceKernel trace_kernel_spec(bool t8, const CallPlan& pl)
+{
+  const bool both = pl.nobulb && pl.nopend;
+  if (pl.qn && pl.notri) return both ? trace_kernel_tables<C, true, SPEC_NOTRI | SPEC_NOBULB | SPEC_NOPEND>(t8) : trace_kernel_tables<C, true, SPEC_NOTRI>(t8);
+  if (pl.qn) return both ? trace_kernel_tables<C, true, SPEC_NOBULB | SPEC_NOPEND>(t8) : pl.nobulb ? trace_kernel_tables<C, true, SPEC_NOBULB>(t8) : trace_kernel_tables<C, true, 0>(t8);
+  return both ? trace_kernel_tables<C, false, SPEC_NOBULB | SPEC_NOPEND>(t8) : pl.nobulb ? trace_kernel_tables<C, false, SPEC_NOBULB>(t8) : trace_kernel_tables<C, false, 0>(t8);
+}
+static TraceKernel trace_kernel_for(bool count, bool t8, const CallPlan& pl) { return count ? trace_kernel_spec<true>(t8, pl) : trace_kernel_spec<false>(t8, pl); }
+
+// step 7: the trace launch of one slab, pixels [p0, p0 + pn) of the part.  `a` holds the slab's arguments already.
+// (the work counter, counters[8], and the count of waves that ran past its end, counters[12], are left at zero by the launch
+// itself; counters[9], the overflow events, is only reset by mirt_get_stats)
+static int launch_slab(const RenderCall& c, RenderCtx& cx, const CallPlan& pl, RenderArgs& a, const HotArgs& h, int slab, long long p0, long long pn,
+                       int blocks, TraceKernel kernel)
+{
+  const hipStream_t stream = c.stream;
+  if (c.sc->opt.wavefront != 0) {
+    float tms = 0.0f;
+    int rc = wavefront_trace(c.sc, cx, a, c.count(), stream, &tms);
+    if (rc != MIRT_OK) return rc;
+    cx.wf_trace_ms = (cx.wf_trace_ms < 0.0f ? 0.0f : cx.wf_trace_ms) + tms;
+    MIRT_HIP(hipGetLastError());
+    return MIRT_OK;
+  }
+  // this slab's arguments: the kernel reads them from device memory; a ring of copies, so that the copy for slab k + 1
+  // does not wait for the kernel of slab k (the stream orders a copy after the kernel that used the same slot)
+  // (a frame like the one before it finds its arguments in place: nothing is copied)
+  const int slot = slab % MAX_SLAB_ARGS;
+  RenderArgs* adev = cx.args_dev + slot;
+  if (!cx.args_valid[slot] || memcmp(&cx.args_host[slot], &a, sizeof(RenderArgs)) != 0) {
+    MIRT_HIP(hipMemcpyAsync(adev, &a, sizeof(RenderArgs), hipMemcpyHostToDevice, stream));
+    cx.args_host[slot] = a; cx.args_valid[slot] = true;
+  }
+  if (c.sparse()) {
+    // this slab's listed pixels -> the hand-out table and, in the device copy of the arguments, the number of samples
+    cx.args_valid[slot] = false;      // (the device copy no longer equals the host's)
+    int rc = sparse_expand(cx, c.ax->list, c.ax->num_listed, p0, pn, c.sample_count, &adev->num_samples, stream);
+    if (rc != MIRT_OK) return rc;
+  }
+  MIRT_HIP(hipEventRecord(cx.slab_ev[2 * slab], stream));
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(TRACE_BLOCK), 0, stream, adev, h);
+  MIRT_HIP(hipGetLastError());
+  MIRT_HIP(hipEventRecord(cx.slab_ev[2 * slab + 1], stream));
+  return MIRT_OK;
+}
+
+// step 8: the slab's samples -> pixels (mirt_render) or sums (mirt_render_accumulate*)
+static int resolve_slab(const RenderCall& c, RenderCtx& cx, long long p0, long long pn)
+{
+  const hipStream_t stream = c.stream;
+  if (c.d_accum) {
+    const AdaptiveArgs mx = c.ax ? *c.ax : AdaptiveArgs();      // (mirt_render_accumulate: every pixel, the sums only)
+    return resolve_moments(cx, cx.samples, mx, (float4*)c.d_accum, p0, pn, mx.num_listed, c.sample_count, stream);
+  }
+  ResolveArgs ra;
+  ra.samples = cx.samples; ra.rgba8 = (unsigned char*)c.d_rgba8; ra.rgba_f32 = (float4*)c.d_rgba_f32;
+  ra.num_local_pixels = pn; ra.pixel_base = p0; ra.spp = c.p->spp; ra.count = c.sample_count;
+  int P = 1, lg = 0;
+  while (P < c.sample_count) { P <<= 1; ++lg; }
+  if (c.sample_count > 1 && P <= 64) {
+    const long long ppb = TBLOCK >> lg;
+    hipLaunchKernelGGL(resolve_tree_kernel, dim3((unsigned)((pn + ppb - 1) / ppb)), dim3(TBLOCK), 0, stream, ra, P, lg);
+  } else {
+    hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)((pn + RBLOCK - 1) / RBLOCK)), dim3(RBLOCK), 0, stream, ra);
+  }
+  MIRT_HIP(hipGetLastError());
+  return MIRT_OK;
+}
+
+static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, void* d_rgba_f32, void* d_accum, int sample_first,
+                       int sample_count, hipStream_t stream, const AdaptiveArgs* ax = nullptr)
+{
+  const RenderCall c{sc, p, d_rgba8, d_rgba_f32, d_accum, ax, sample_first, sample_count, stream};
+  int64_t npix = 0;
+  int rc = check_call(c, &npix);
+  if (rc != MIRT_OK || npix == 0) return rc;
+  const bool count = c.count();
+  CallShape shape;
+  shape.npix = npix; shape.sample_first = sample_first; shape.sample_count = sample_count; shape.spp = p->spp;
+  shape.accumulate = d_accum != nullptr; shape.num_listed = c.sparse() ? ax->num_listed : -1; shape.counters = count;
+  const CallPlan pl = plan_call(scene_facts(sc), sc->opt, shape);
+  const int blocks = size_grid(sc, pl, count, stream);
+  const int chunk_shift = plan_chunk_shift(pl.launch_samples_max, blocks, sc->opt.chunk_shift);
+  const size_t nchunks = (size_t)((pl.slab_samples_max + (1ll << chunk_shift) - 1) >> chunk_shift);
+  const long long okey = pl.slab_samples_max * 16 + chunk_shift;      // names the shape a measured order belongs to
+
+  RenderCtx* cxp = nullptr;
+  rc = take_context(sc, &cxp);
+  if (rc != MIRT_OK) return rc;
+  RenderCtx& cx = *cxp;
+  rc = ensure_workspace(c, cx, pl, blocks);
+  if (rc != MIRT_OK) return rc;
+  RenderArgs a;
+  HotArgs h;
+  rc = fill_args(c, cx, pl, chunk_shift, a, h);
+  if (rc != MIRT_OK) return rc;
+
+  // the hand-out order: found, or measured by this call for the calls after it
+  bool measure_chunks = false, measure_samples = false, ordered_samples = false;
+  if (pl.hand_out == HAND_BY_CHUNK) {
+    rc = chunk_order_find(sc, cx, nchunks, okey, &a.chunk_order);
+    measure_chunks = !a.chunk_order;
+    if (measure_chunks) a.chunk_cost = cx.chunk_cost;
+  } else if (pl.hand_out == HAND_BY_SAMPLE) {
+    rc = sample_table_find(sc, pl, okey, &ordered_samples, &measure_samples);
+  }
+  if (rc != MIRT_OK) return rc;
+  const TraceKernel kernel = trace_kernel_for(count || measure_chunks || measure_samples,      // (measure: cost stamps need the step counter)
+                                              a.needs_rng && a.rng.mode == 0 && a.rng.chunk_bits == 8, pl);
+
   cx.frame_id = ++sc->frame_seq;
   MIRT_HIP(hipEventRecord(cx.ev0, stream));
-  if (measure && !by_sample) MIRT_HIP(hipMemsetAsync(cx.chunk_cost, 0, 4 * nchunks, stream));
+  if (measure_chunks) MIRT_HIP(hipMemsetAsync(cx.chunk_cost, 0, 4 * nchunks, stream));
   if (count) { MIRT_HIP(hipMemsetAsync(cx.counters, 0, 8 * sizeof(unsigned long long), stream)); MIRT_HIP(hipMemsetAsync(cx.counters + 11, 0, sizeof(unsigned long long), stream)); }
-  a.work_counter = cx.counters + 8;
   cx.wf_trace_ms = -1.0f;
-  float wf_ms_total = 0.0f;
-  HotArgs h;
-  h.nodes = a.nodes; h.root_ref = a.root_ref; h.swap_mask = a.swap_mask; h.qparams = a.qparams;
-  h.planes = a.planes; h.num_planes = a.num_planes; h.suns = a.suns; h.num_suns = a.num_suns; h.bulbs = a.bulbs; h.num_bulbs = a.num_bulbs; h.shadow_anyhit = a.shadow_anyhit;
-  h.stack_spill = a.stack_spill; h.lds_depth = a.lds_depth; h.refill_k = a.refill_k; h.batch_k = a.batch_k; h.drain_lanes = a.drain_lanes;
-  // (the quantised walks; the exact records are walked in the reference's own order, or -- traversal = 2 -- in one that promises nothing)
-  a.reach_check = (qn && sc->N > 1) ? 1 : 0;
-  a.reach_slack = 4.76837158203125e-07f * sc->coord_max;
-  h.reach_check = a.reach_check;
-  h.leaf_k = opt.leaf_k > 0 ? opt.leaf_k : (qn ? 8 : 4);      // (exact records, redchair.txt: 4 is 1.3 % better than 8)
-  h.reps = opt.reps > 0 ? opt.reps : ((qn && !notri) ? 5 : 4);      // (wide records: 5 is 1 % better on the 2 M-primitive scene, worse elsewhere)
-  if (!wavefront && !cx.args_dev) MIRT_HIP(hipMalloc(&cx.args_dev, sizeof(RenderArgs) * MAX_SLAB_ARGS));
-  int P = 1, lg = 0;
-  while (P < sample_count) { P <<= 1; ++lg; }
-
+  cx.launches = pl.nslabs;
+  cx.node_bytes = pl.node_bytes;
   MIRT_HIP(hipEventRecord(cx.ev1, stream));
-  // one event pair per trace launch: a call of several slabs reports the SUM of its launches, not a bracket that would take in
-  // the resolve kernels between them
-  while ((int)cx.slab_ev.size() < 2 * nslabs) { hipEvent_t e = nullptr; MIRT_HIP(hipEventCreate(&e)); cx.slab_ev.push_back(e); }
-  cx.launches = nslabs;
-  cx.node_bytes = (qn && notri) ? 32 : 64;
-  for (int slab = 0; slab < nslabs; ++slab) {
-    const long long p0 = (long long)slab * slab_pixels;
-    const long long pn = (p0 + slab_pixels < npix ? p0 + slab_pixels : npix) - p0;
-    a.pixel_base = p0; a.num_local_pixels = pn; a.num_samples = pn * sppe;
-    a.sample_order = ordered_samples ? sc->so_order + (size_t)p0 * sppe : nullptr;      // (this launch's part of the table)
+  for (int slab = 0; slab < pl.nslabs; ++slab) {
+    const long long p0 = (long long)slab * pl.slab_pixels;
+    const long long pn = (p0 + pl.slab_pixels < npix ? p0 + pl.slab_pixels : npix) - p0;
+    a.pixel_base = p0; a.num_local_pixels = pn; a.num_samples = pn * sample_count;
+    a.sample_order = ordered_samples ? sc->so_order + (size_t)p0 * sample_count : nullptr;      // (this launch's part of the table)
     a.sample_key = measure_samples ? sc->so_keys : nullptr;
-    if (sparse) {
+    if (c.sparse()) {
       a.sample_order = cx.sp_table;
-      a.num_samples = (pn < listed_max ? pn : listed_max) * sppe;      // (an upper bound: sparse_expand writes the launch's own number over it)
+      a.num_samples = (pn < pl.listed_max ? pn : pl.listed_max) * sample_count;      // (an upper bound: sparse_expand writes the launch's own number over it)
     }
-    // (the work counter, counters[8], and the count of waves that ran past its end, counters[12], are left at zero by the launch
-    // itself; counters[9], the overflow events, is only reset by mirt_get_stats)
-    if (wavefront) {
-      a.refill_k = opt.wf_refill_k;
-      float tms = 0.0f;
-      int rc = wavefront_trace(sc, cx, a, count, stream, &tms);
-      if (rc != MIRT_OK) return rc;
-      wf_ms_total += tms;
-      cx.wf_trace_ms = wf_ms_total;
-    } else {
-      // this slab's arguments: the kernel reads them from device memory; a ring of copies, so that the copy for slab k + 1
-      // does not wait for the kernel of slab k (the stream orders a copy after the kernel that used the same slot)
-      // (a frame like the one before it finds its arguments in place: nothing is copied)
-      const int slot = slab % MAX_SLAB_ARGS;
-      RenderArgs* adev = cx.args_dev + slot;
-      if (!cx.args_valid[slot] || memcmp(&cx.args_host[slot], &a, sizeof(RenderArgs)) != 0) {
-        MIRT_HIP(hipMemcpyAsync(adev, &a, sizeof(RenderArgs), hipMemcpyHostToDevice, stream));
-        cx.args_host[slot] = a; cx.args_valid[slot] = true;
-      }
-      if (sparse) {
-        // this slab's listed pixels -> the hand-out table and, in the device copy of the arguments, the number of samples
-        cx.args_valid[slot] = false;      // (the device copy no longer equals the host's)
-        int rc = sparse_expand(cx, ax->list, ax->num_listed, p0, pn, sppe, &adev->num_samples, stream);
-        if (rc != MIRT_OK) return rc;
-      }
-      MIRT_HIP(hipEventRecord(cx.slab_ev[2 * slab], stream));
-      // one instantiation per form of the random-number tables (device_common.h, xw_init) and per node format
-      {
-        const bool t8 = a.needs_rng && a.rng.mode == 0 && a.rng.chunk_bits == 8;
-#define MIRT_LAUNCH(C, T, Q, P) hipLaunchKernelGGL((trace_kernel<C, T, Q, P>), dim3(blocks), dim3(TRACE_BLOCK), 0, stream, adev, h)
-#define MIRT_LAUNCH_T(C, Q, P) do { if (t8) MIRT_LAUNCH(C, 8, Q, P); else MIRT_LAUNCH(C, 4, Q, P); } while (0)
-#define MIRT_LAUNCH_S(C, Q) do { if (nobulb && nopend) MIRT_LAUNCH_T(C, Q, SPEC_NOBULB | SPEC_NOPEND); else if (nobulb) MIRT_LAUNCH_T(C, Q, SPEC_NOBULB); \
-                                 else MIRT_LAUNCH_T(C, Q, 0); } while (0)
-#define MIRT_LAUNCH_Q(C) do { if (qn && notri && nobulb && nopend) MIRT_LAUNCH_T(C, true, SPEC_NOTRI | SPEC_NOBULB | SPEC_NOPEND); \
-                              else if (qn && notri) MIRT_LAUNCH_T(C, true, SPEC_NOTRI); \
-                              else if (qn) MIRT_LAUNCH_S(C, true); else MIRT_LAUNCH_S(C, false); } while (0)
-        if (count || measure) MIRT_LAUNCH_Q(true); else MIRT_LAUNCH_Q(false);      // (measure: cost stamps need the step counter)
-#undef MIRT_LAUNCH_Q
-#undef MIRT_LAUNCH_S
-#undef MIRT_LAUNCH_T
-#undef MIRT_LAUNCH
-      }
-    }
-    MIRT_HIP(hipGetLastError());
-    if (!wavefront) MIRT_HIP(hipEventRecord(cx.slab_ev[2 * slab + 1], stream));
-    if (slab == nslabs - 1) MIRT_HIP(hipEventRecord(cx.ev2, stream));
-
-    ResolveArgs ra;
-    ra.samples = cx.samples; ra.rgba8 = (unsigned char*)d_rgba8; ra.rgba_f32 = (float4*)d_rgba_f32;
-    ra.num_local_pixels = pn; ra.pixel_base = p0; ra.spp = p->spp; ra.count = sample_count;
-    if (d_accum) {
-      const AdaptiveArgs mx = ax ? *ax : AdaptiveArgs();      // (mirt_render_accumulate: every pixel, the sums only)
-      int rc = resolve_moments(cx, cx.samples, mx, (float4*)d_accum, p0, pn, mx.num_listed, sample_count, stream);
-      if (rc != MIRT_OK) return rc;
-    } else if (sample_count > 1 && P <= 64) {
-      const long long ppb = TBLOCK >> lg;
-      hipLaunchKernelGGL(resolve_tree_kernel, dim3((unsigned)((pn + ppb - 1) / ppb)), dim3(TBLOCK), 0, stream, ra, P, lg);
-    } else {
-      hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)((pn + RBLOCK - 1) / RBLOCK)), dim3(RBLOCK), 0, stream, ra);
-    }
-    MIRT_HIP(hipGetLastError());
-    if (measure_samples) {
-      // this launch's part of the cost-ordered sample table, for later calls of this shape (the key buffer is reused by the next slab)
-      int rc = sort_low_byte(sc->so_keys, sc->so_keys2, sc->so_order + (size_t)p0 * sppe, pn * sppe, sc->so_ws, stream);
-      if (rc != MIRT_OK) return rc;
-    }
+    rc = launch_slab(c, cx, pl, a, h, slab, p0, pn, blocks, kernel);
+    if (rc != MIRT_OK) return rc;
+    if (slab == pl.nslabs - 1) MIRT_HIP(hipEventRecord(cx.ev2, stream));
+    rc = resolve_slab(c, cx, p0, pn);
+    // this launch's part of the cost-ordered sample table, for later calls of this shape (the key buffer is reused by the next slab)
+    if (rc == MIRT_OK && measure_samples) rc = sort_low_byte(sc->so_keys, sc->so_keys2, sc->so_order + (size_t)p0 * sample_count, pn * sample_count, sc->so_ws, stream);
+    if (rc != MIRT_OK) return rc;
   }
-  if (measure_samples) {
-    MIRT_HIP(hipEventRecord(sc->so_ev, stream));
-    sc->so_key = sc->so_pending_key; sc->so_busy = true;
-  } else if (measure) {
-    // order for later frames.  It overwrites the buffer this context wrote three orders ago; every frame that could have read
-    // that one has finished -- the host waited for each of them when it reused their contexts.
-    uint32_t* out = cx.order_out[cx.order_writes % RenderCtx::ORDER_BUFS];
-    hipLaunchKernelGGL(order_kernel, dim3(1), dim3(SORT_BINS), 0, stream, cx.chunk_cost, (uint32_t)nchunks, out);
-    MIRT_HIP(hipGetLastError());
-    MIRT_HIP(hipEventRecord(cx.order_ev, stream));
-    cx.order_key = okey;
-    cx.order_frame = cx.frame_id;
-    ++cx.order_writes;
-  }
+  if (measure_samples) rc = sample_table_finish(sc, stream);
+  else if (measure_chunks) rc = chunk_order_finish(cx, nchunks, okey, stream);
+  if (rc != MIRT_OK) return rc;
   ++cx.uses;
   ++sc->frame_no;
   MIRT_HIP(hipEventRecord(cx.ev3, stream));

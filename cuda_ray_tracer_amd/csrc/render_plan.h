@@ -1,0 +1,191 @@
+// What one render call decides before it touches the device: a pure function from (scene facts, options, call shape) to a
+// CallPlan.  No HIP in here -- this header compiles with a plain host compiler, and tests/plan_probe.cpp runs it against
+// the tests' Python mirror of the same decisions (product_flags) without a GPU.  render.hip's render_impl carries the plan
+// out step by step.
+#ifndef MIRT_RENDER_PLAN_H
+#define MIRT_RENDER_PLAN_H
+
+#include <cstdint>
+
+// The trace kernel's waves never talk to each other, so a workgroup is one wave: a finished wave frees its slot (and its
+// 10 KB of LDS) at once instead of waiting for the slowest of four, which is what lets the next frame's waves move in
+// while this frame drains.
+#ifndef MIRT_TRACE_BLOCK
+#define MIRT_TRACE_BLOCK 64
+#endif
+#ifndef MIRT_STACK_LDS
+#define MIRT_STACK_LDS 24
+#endif
+
+namespace mirt {
+
+constexpr int TRACE_BLOCK = MIRT_TRACE_BLOCK;
+constexpr int STACK_LDS = MIRT_STACK_LDS;
+constexpr int MAX_CHUNK_SHIFT = 8, MIN_CHUNK_SHIFT = 6;   // a wave takes 64..256 consecutive samples from the frame per atomic
+// node record word 14 (after the two child references): which descent orders the node allows
+constexpr uint32_t NODE_SWAP_PURE = 1u;       // both subtrees hold spheres only: near-child-first cannot change the closest hit
+constexpr uint32_t NODE_SWAP_ANY = 2u;        // always set (the mask of MIRT_TRAVERSAL_ORDERED_ALL)
+
+// Mode switches and tuning values of a scene.  The defaults are the measured optima.  MIRT_<NAME> environment variables
+// override them ONCE, when the scene is created (tools/ sweeps); mirt_scene_set_option changes them afterwards.  Nothing
+// reads the environment during a render.
+struct Options {
+  int bounds_as_shipped = 0;   // build: 1 = scene bounds never stored, every Morton code 0 -- the tree of the shipped reference (parse.cpp:28)
+  int traversal = 1;           // MIRT_TRAVERSAL_*: 0 reference (left first), 1 ordered where pixels cannot change, 2 ordered everywhere
+  int wavefront = 0;           // 1: the trace / shade kernel pair instead of the single kernel
+  int stack_lds_depth = -1;    // traversal-stack entries kept in LDS (-1: the compiled size); tests force the spill path with it
+  int refill_k = 0;            // leave the traversal loop when this many lanes wait to shade; 0 = by kind of kernel (plan_call)
+  int batch_k = 8, drain_lanes = 16;
+  int leaf_k = 0;              // primitive tests are held back until this many lanes have one pending; 0 = by kind of kernel (8; exact records 4)
+  int reps = 0;                // traversal steps per pass through the loop header; 0 = by kind of kernel (4; wide records 5)
+  int init_k = 0;              // lanes without a sample are refilled once this many wait (1: at every shade phase); 0 = by kind of kernel (plan_call)
+  int chunk_shift = 0;         // 0: by frame size
+  int trace_waves = 0;         // 0: fill the device
+  int shadow_anyhit = 1;       // 0: shadow rays are nearest-hit queries, as in diffuseLight (draw.cu:347-352, 365-370): the reference's walk, more node visits
+  int skip_unlit = 1;          // 0: shadow rays towards lights the shading normal faces away from are traced as well (draw.cu:342-374 traces them all)
+  int qnodes = 1;              // quantised node records in the single-kernel path: 0 never; 1 sphere-only scenes (traversal >= 1) and scenes with
+                               // triangles of 65536 primitives or more (wide records, traversal = 1); 2 every scene
+  int specialise = 1;          // kernels compiled without what the scene does not have: point lights; transparency and gi (SPEC_*, shade_common.h)
+  int sched = 2;               // longest-first hand-out measured on the first call of a shape: 2 by sample (stable within a cost class), 1 by chunk (one-slab calls), 0 off
+  int slab_log2 = 28;          // a call is rendered in slabs of at most 2^slab_log2 samples (4 GiB of per-sample workspace; 2^26: +1.8 % on config 5)
+  int wf_pool = 1 << 21, wf_refill_k = 16;
+};
+
+// the facts of a built scene that the decisions read
+struct SceneFacts {
+  int N = 0, Nt = 0;                       // primitives, triangles among them
+  bool grid_ok = false;                    // the grid of the quantised records resolves the scene's coordinates (lbvh_build.hip)
+  bool has_quantised = false, has_wide = false;   // the build made 32-byte quantised / 64-byte wide records
+  bool colors_finite = true, any_trans = false, any_rough = false;
+  int gi = 0, bounces = 0;
+  int num_suns = 0, num_bulbs = 0;
+};
+
+struct CallShape {
+  long long npix = 0;                      // pixels of the part (> 0)
+  int sample_first = 0, sample_count = 1;  // each pixel's samples [sample_first, sample_first + sample_count)
+  int spp = 0;                             // MirtRenderParams::spp
+  bool accumulate = false;                 // sums are added to an accumulation buffer (else pixels are written)
+  long long num_listed = -1;               // length of the pixel list; < 0: no list, every pixel
+  bool counters = false;                   // MIRT_RENDER_COUNTERS
+};
+
+// who decides the order in which a launch's samples are handed to the waves
+enum HandOut {
+  HAND_FRAME = 0,     // frame order
+  HAND_LIST,          // the listed pixels' samples, in list order (adaptive.hip)
+  HAND_BY_CHUNK,      // sched = 1: chunks, longest first, per context
+  HAND_BY_SAMPLE,     // sched = 2: samples by decreasing cost class, one table per scene
+};
+
+struct CallPlan {
+  // slabs: whole pixels, at most 2^slab_log2 samples each
+  long long slab_pixels = 0; int nslabs = 0;
+  long long slab_samples_max = 0;          // per-sample workspace of a launch
+  long long listed_max = 0;                // a sparse launch hands out at most this many pixels: the listed pixels of one slab
+  long long launch_samples_max = 0;        // ... and any launch at most this many samples
+  long long total_samples = 0;
+  bool per_pixel_seed = false;             // curand_init(1234 + pixel, sample, 0) (draw.cu:74,162) vs curand_init(1234, pixel, 0) (draw.cu:105)
+  int args_spp = 0;                        // RenderArgs::spp
+  int rng_sample_tables = 0;               // ensure_rng_tables: tables of this many sample indices, 0 = the per-pixel tables
+  bool shading_rng = false;                // rough normals or GI draw random numbers whatever the camera does
+  // node records and walk order
+  bool notri = false, qn = false;          // sphere-only scene; a quantised walk (notri: the 32-byte records, else the wide ones)
+  uint32_t swap_mask = 0;
+  int reach_check = 0;
+  int node_bytes = 64;
+  // specialisation, shading switches
+  bool nobulb = false, nopend = false;
+  bool need_pending = false; int pending_slots = 0;
+  int skip_unlit = 0, shadow_anyhit = 0;
+  // thresholds by kind of kernel
+  int refill_k = 0, init_k = 0, leaf_k = 0, reps = 0, lds_depth = 0;
+  HandOut hand_out = HAND_FRAME;
+};
+
+inline CallPlan plan_call(const SceneFacts& s, const Options& opt, const CallShape& c)
+{
+  CallPlan pl;
+  const bool sparse = c.num_listed >= 0;
+  const bool wavefront = opt.wavefront != 0;
+  pl.slab_pixels = (1ll << opt.slab_log2) / c.sample_count;
+  if (pl.slab_pixels < 1) pl.slab_pixels = 1;
+  if (pl.slab_pixels > c.npix) pl.slab_pixels = c.npix;
+  pl.nslabs = (int)((c.npix + pl.slab_pixels - 1) / pl.slab_pixels);
+  pl.slab_samples_max = pl.slab_pixels * c.sample_count;
+  pl.listed_max = sparse ? (c.num_listed < pl.slab_pixels ? c.num_listed : pl.slab_pixels) : 0;
+  pl.launch_samples_max = sparse ? pl.listed_max * c.sample_count : pl.slab_samples_max;
+  pl.total_samples = c.npix * c.sample_count;
+  pl.per_pixel_seed = c.accumulate || c.spp > 1;
+  pl.args_spp = c.accumulate ? (c.spp > 1 ? c.spp : 2) : c.spp;      // only "is it >= 1" matters to the kernel: jittered samples (draw.cu:78-84,110-118,165-171)
+  pl.rng_sample_tables = pl.per_pixel_seed ? c.sample_first + c.sample_count : 0;
+  pl.shading_rng = s.any_rough || s.gi != 0;
+
+  // Quantised node records: single-kernel path, any order but the reference's own.  A sphere-only scene: the 32-byte records,
+  // always.  A scene with triangles: the wide records -- the reference's order at every node, so traversal = 1 only -- when the
+  // scene is large enough for memory to matter (qnodes = 1: N >= 65536, the exact records no longer fit an L2; redchair.txt's
+  // 1.7 k primitives are 12 % faster on the exact records, the 2 M-primitive scene 25 % faster on the wide ones) or always (2).
+  pl.notri = s.Nt == 0;
+  const bool qwant = opt.qnodes != 0 && !wavefront;
+  // (and only if the grid of the quantised records resolves the scene's coordinates: grid_ok, lbvh_build.hip -- a scene that
+  // sits hundreds of its own extents away from the world origin walks the exact records, in the reference's order)
+  pl.qn = s.grid_ok && (pl.notri ? (qwant && opt.traversal >= 1 && s.has_quantised)
+                                 : (qwant && opt.traversal == 1 && s.has_wide && (opt.qnodes >= 2 || s.N >= 65536)));
+  // traversal = 1: near child first on the quantised records of a sphere-only scene, nowhere else.  Over the exact boxes the
+  // reordered walk can cull a box over a sphere whose hit distance rounds below that box's entry distance (one ulp is enough; the
+  // reference, in its order, gets there first): 13 of 4 000 far-camera fuzz scenes differed by a pixel or a ray.  The quantised
+  // boxes are rounded outwards by more than that rounding as long as the grid resolves it (grid_ok, a condition of qn) -- no differing byte
+  // in 10 000 sphere scenes, 3 000 of them far-camera ones.  Everything else walks in the reference's order.
+  pl.swap_mask = opt.traversal == 1 ? ((pl.qn && pl.notri) ? NODE_SWAP_PURE : 0u) : (opt.traversal == 2 ? NODE_SWAP_ANY : 0u);
+  // (the quantised walks; the exact records are walked in the reference's own order, or -- traversal = 2 -- in one that promises nothing)
+  pl.reach_check = (pl.qn && s.N > 1) ? 1 : 0;
+  pl.node_bytes = (pl.qn && pl.notri) ? 32 : 64;
+
+  pl.need_pending = s.any_trans || s.gi != 0;
+  pl.pending_slots = pl.need_pending ? 2 * (s.bounces + (s.gi > 0 ? s.gi : 0) + 2) : 0;
+  // kernels specialised for what the scene does not have (SPEC_*, shade_common.h)
+  // (a scene with a non-finite colour gets the general kernels: only they carry the colour * 0 terms, gi_zero_term)
+  const bool specialise = opt.specialise != 0 && s.colors_finite;
+  pl.nobulb = specialise && s.num_bulbs == 0;
+  pl.nopend = specialise && !pl.need_pending;
+  pl.skip_unlit = (opt.skip_unlit != 0 && s.colors_finite && s.num_suns + s.num_bulbs <= 32) ? 1 : 0;
+  pl.shadow_anyhit = opt.shadow_anyhit != 0 ? 1 : 0;
+
+  pl.lds_depth = (opt.stack_lds_depth >= 0 && opt.stack_lds_depth <= STACK_LDS) ? opt.stack_lds_depth : STACK_LDS;   // tests force the spill path
+  // Thresholds of the two expensive divergent pieces of work, measured per kind of kernel (round 3, tools/r03_i.sh, r03_x.sh): lanes
+  // wait to shade until refill_k of them do, lanes without a sample until init_k of them do.  Sphere-only scenes 32 / 10; wide
+  // records (2 M-primitive scene) 24 / 8; exact records (redchair.txt) 64 / 64 -- with the samples handed out by cost class
+  // (sched = 2) the lanes of a wave run samples of one kind, and redchair.txt's short ray trees are fastest in lock step: the whole
+  // wave traverses, the whole wave shades, the whole wave takes 64 new samples (1080p16: 20.6 ms at 52 / 48, 18.1 at 64 / 64;
+  // tenthousand.txt's deep reflection chains want the opposite: 28.0 ms at 64 / 64 against 21.7).  Refilling finished lanes at
+  // every shade phase (init_k = 1, rounds 1-2) cost redchair.txt 14 % of its frame, the sphere scenes 1.5 %.
+  pl.refill_k = opt.refill_k > 0 ? opt.refill_k : (pl.qn ? (pl.notri ? 32 : 24) : 64);
+  const int init_k = opt.init_k > 0 ? opt.init_k : (pl.qn ? (pl.notri ? 10 : 8) : 64);
+  pl.init_k = init_k < pl.refill_k ? init_k : pl.refill_k;      // (<= refill_k: lanes waiting for a sample count as waiting in the loop header)
+  pl.leaf_k = opt.leaf_k > 0 ? opt.leaf_k : (pl.qn ? 8 : 4);      // (exact records, redchair.txt: 4 is 1.3 % better than 8)
+  pl.reps = opt.reps > 0 ? opt.reps : ((pl.qn && !pl.notri) ? 5 : 4);      // (wide records: 5 is 1 % better on the 2 M-primitive scene, worse elsewhere)
+
+  // A sparse call is handed out in list order: it neither measures an order nor uses one, and leaves the chunk orders and the
+  // scene's by-sample table -- which belong to the dense shape rendered last -- as they are.
+  // sched = 1 (by chunk): one-slab calls only.
+  // sched = 2 (default, by sample): any call whose launches fit a 32-bit sample index and whose table (4 B per sample of the
+  // call) stays within 12 GiB; beyond that the call is rendered in frame order.
+  if (sparse) pl.hand_out = HAND_LIST;
+  else if (wavefront) pl.hand_out = HAND_FRAME;
+  else if (opt.sched == 1 && pl.nslabs == 1) pl.hand_out = HAND_BY_CHUNK;
+  else if (opt.sched == 2 && pl.slab_samples_max < 0x7fffffffll && pl.total_samples <= (3ll << 30)) pl.hand_out = HAND_BY_SAMPLE;
+  return pl;
+}
+
+// Chunk size of the work counter: 256 samples, smaller for a small (part of a) frame so that every wave still gets a dozen
+// chunks or more -- with four chunks per wave (1/8 of a 1080p frame) the waves finished up to a chunk apart.  `blocks` is
+// the launch's grid, which depends on the device and on the frames in flight.
+inline int plan_chunk_shift(long long launch_samples_max, int blocks, int option)
+{
+  int chunk_shift = MAX_CHUNK_SHIFT;
+  while (chunk_shift > MIN_CHUNK_SHIFT && (launch_samples_max >> chunk_shift) < 16ll * blocks * (TRACE_BLOCK / 64)) --chunk_shift;
+  return option >= 4 ? option : chunk_shift;
+}
+
+} // namespace mirt
+#endif

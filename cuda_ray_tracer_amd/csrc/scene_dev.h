@@ -8,6 +8,7 @@
 
 #include "../../include/mirt.h"
 #include "device_common.h"
+#include "render_plan.h"
 #include "xorwow_tables.h"
 
 namespace mirt {
@@ -43,9 +44,7 @@ constexpr uint32_t REF_QPURE = 0x20000000u;
 constexpr uint32_t QBOX_NONE = 0x0000ffffu;   // lo = 65535, hi = 0
 constexpr int STACK_TOTAL_WIDE = 88;          // up to three pushes per two levels of a tree at most 58 levels deep
 constexpr float QINV_STEPS = 1152921504606846976.0f;   // 2^60: |1 / d| is clamped to this many grid steps per unit of t (quantised_axis)
-// node record word 14 (after the two child references): which descent orders the node allows
-constexpr uint32_t NODE_SWAP_PURE = 1u;       // both subtrees hold spheres only: near-child-first cannot change the closest hit
-constexpr uint32_t NODE_SWAP_ANY = 2u;        // always set (the mask of MIRT_TRAVERSAL_ORDERED_ALL)
+// (NODE_SWAP_*, the descent orders a node record allows: render_plan.h)
 
 struct PlaneDev { float nx, ny, nz, px, py, pz; float mat[11]; float pad; };   // 72 B
 // suns: direction; bulbs: position.  n* = normalize(direction) and i* = 1 / n* for suns, computed on the host with the same
@@ -146,30 +145,7 @@ struct RngCache {
   uint4* A = nullptr; uint32_t* B = nullptr; uint32_t* K = nullptr; uint32_t* R2 = nullptr;
 };
 
-// Mode switches and tuning values of a scene.  The defaults are the measured optima.  MIRT_<NAME> environment variables
-// override them ONCE, when the scene is created (tools/ sweeps); mirt_scene_set_option changes them afterwards.  Nothing
-// reads the environment during a render.
-struct Options {
-  int bounds_as_shipped = 0;   // build: 1 = scene bounds never stored, every Morton code 0 -- the tree of the shipped reference (parse.cpp:28)
-  int traversal = 1;           // MIRT_TRAVERSAL_*: 0 reference (left first), 1 ordered where pixels cannot change, 2 ordered everywhere
-  int wavefront = 0;           // 1: the trace / shade kernel pair instead of the single kernel
-  int stack_lds_depth = -1;    // traversal-stack entries kept in LDS (-1: the compiled size); tests force the spill path with it
-  int refill_k = 0;            // leave the traversal loop when this many lanes wait to shade; 0 = by kind of kernel (render.hip)
-  int batch_k = 8, drain_lanes = 16;
-  int leaf_k = 0;              // primitive tests are held back until this many lanes have one pending; 0 = by kind of kernel (8; exact records 4)
-  int reps = 0;                // traversal steps per pass through the loop header; 0 = by kind of kernel (4; wide records 5)
-  int init_k = 0;              // lanes without a sample are refilled once this many wait (1: at every shade phase); 0 = by kind of kernel (render.hip)
-  int chunk_shift = 0;         // 0: by frame size
-  int trace_waves = 0;         // 0: fill the device
-  int shadow_anyhit = 1;       // 0: shadow rays are nearest-hit queries, as in diffuseLight (draw.cu:347-352, 365-370): the reference's walk, more node visits
-  int skip_unlit = 1;          // 0: shadow rays towards lights the shading normal faces away from are traced as well (draw.cu:342-374 traces them all)
-  int qnodes = 1;              // quantised node records in the single-kernel path: 0 never; 1 sphere-only scenes (traversal >= 1) and scenes with
-                               // triangles of 65536 primitives or more (wide records, traversal = 1); 2 every scene
-  int specialise = 1;          // kernels compiled without what the scene does not have: point lights; transparency and gi (SPEC_*, shade_common.h)
-  int sched = 2;               // longest-first hand-out measured on the first call of a shape: 2 by sample (stable within a cost class), 1 by chunk (one-slab calls), 0 off
-  int slab_log2 = 28;          // a call is rendered in slabs of at most 2^slab_log2 samples (4 GiB of per-sample workspace; 2^26: +1.8 % on config 5)
-  int wf_pool = 1 << 21, wf_refill_k = 16;
-};
+// (Options, the mode switches and tuning values of a scene: render_plan.h)
 
 constexpr int MIRT_MAX_FRAMES = 4;
 // everything one frame in flight owns
@@ -305,6 +281,7 @@ int scatter_part(const MirtRenderParams* p, const void* d_part, void* d_frame, h
 int64_t render_num_pixels(const MirtRenderParams* p);
 int part_pixel(const MirtRenderParams* p, int64_t local, int32_t* x, int32_t* y);
 int trace_ms_of(RenderCtx& cx, float* ms);
+int fold_trace_time(MirtScene* sc, RenderCtx& cx);
 int probe_math(int device, int which, int n, const float* in, float* out);
 int probe_xorwow(int device, int spp, int nstreams, int draws, uint32_t* out);
 int ensure_rng_tables(RngCache* rc, int sample_tables, long long frame_pixels, hipStream_t stream, RngTablesDev* out, bool allow_larger);
@@ -344,5 +321,50 @@ int temporal_accumulate(const MirtRenderParams* p, const MirtCamera* prev_camera
 int wavefront_trace(MirtScene* sc, RenderCtx& cx, RenderArgs& a, bool count, hipStream_t stream, float* trace_ms);
 }
 #define MIRT_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return mirt::hip_fail(e_, #call, __FILE__, __LINE__); } while (0)
+
+namespace mirt {
+
+// A device buffer that only grows, used by the work on one stream.  When its capacity `cap` (in the caller's unit) is below
+// `need`: wait for that stream -- an earlier call on it may still be using the smaller buffer -- free it, allocate `bytes`.
+// (Buffers that frames on OTHER streams read -- the chunk orders, the rng tables -- wait for the device instead, at their sites.)
+template <class T>
+int grow(T*& ptr, size_t& cap, size_t need, size_t bytes, hipStream_t stream)
+{
+  if (cap >= need) return MIRT_OK;
+  MIRT_HIP(hipStreamSynchronize(stream));
+  hipFree(ptr); ptr = nullptr; cap = 0;
+  MIRT_HIP(hipMalloc(&ptr, bytes));
+  cap = need;
+  return MIRT_OK;
+}
+
+// Blocks of a persistent grid that fills the device: compute units x resident blocks of `kernel` per unit (per_cu_fallback
+// if the occupancy query fails).  An error only if the device's properties cannot be read.
+template <class K>
+hipError_t persistent_grid_blocks(int device, K kernel, int block, int per_cu_fallback, int* blocks)
+{
+  hipDeviceProp_t prop;
+  const hipError_t e = hipGetDeviceProperties(&prop, device);
+  if (e != hipSuccess) return e;
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0) != hipSuccess || per_cu < 1) per_cu = per_cu_fallback;
+  *blocks = prop.multiProcessorCount * per_cu;
+  return hipSuccess;
+}
+
+// the frame, camera and partition block of RenderArgs (what a primary ray is made from, apart from spp and the rng tables)
+inline void fill_camera(RenderArgs& a, const MirtScene* sc, const MirtRenderParams* p)
+{
+  a.width = p->width; a.height = p->height; a.bounces = sc->d.bounces;
+  a.fisheye = sc->d.fisheye; a.panorama = sc->d.panorama;
+  a.dof_focus = sc->d.dof_focus; a.dof_lens = sc->d.dof_lens;
+  a.forward.x = sc->d.forward.x; a.forward.y = sc->d.forward.y; a.forward.z = sc->d.forward.z;
+  a.right.x = sc->d.right.x; a.right.y = sc->d.right.y; a.right.z = sc->d.right.z;
+  a.up.x = sc->d.up.x; a.up.y = sc->d.up.y; a.up.z = sc->d.up.z;
+  a.eye.x = sc->d.eye.x; a.eye.y = sc->d.eye.y; a.eye.z = sc->d.eye.z;
+  a.stripe_rows = p->stripe_rows; a.num_parts = p->num_parts; a.part = p->part;
+}
+
+} // namespace mirt
 
 #endif

@@ -473,18 +473,9 @@ int wavefront_trace(MirtScene* sc, RenderCtx& cx, RenderArgs& a, bool count, hip
   // workspace
   const size_t state_bytes = sizeof(uint32_t) * (size_t)W_COUNT * pool;
   const size_t rays_bytes = sizeof(float4) * 2 * max_rays;
-  if (sc->wf_state_cap < state_bytes) {
-    MIRT_HIP(hipStreamSynchronize(stream));
-    hipFree(sc->wf_state); sc->wf_state = nullptr; sc->wf_state_cap = 0;
-    MIRT_HIP(hipMalloc(&sc->wf_state, state_bytes));
-    sc->wf_state_cap = state_bytes;
-  }
-  if (sc->wf_rays_cap < rays_bytes) {
-    MIRT_HIP(hipStreamSynchronize(stream));
-    hipFree(sc->wf_rays); sc->wf_rays = nullptr; sc->wf_rays_cap = 0;
-    MIRT_HIP(hipMalloc(&sc->wf_rays, rays_bytes));
-    sc->wf_rays_cap = rays_bytes;
-  }
+  int rc = grow(sc->wf_state, sc->wf_state_cap, state_bytes, state_bytes, stream);
+  if (rc == MIRT_OK) rc = grow(sc->wf_rays, sc->wf_rays_cap, rays_bytes, rays_bytes, stream);
+  if (rc != MIRT_OK) return rc;
   if (!sc->wf_ctr) {
     MIRT_HIP(hipMalloc(&sc->wf_ctr, 8 * sizeof(unsigned long long)));
     MIRT_HIP(hipHostMalloc(&sc->wf_ctr_host, 8 * sizeof(unsigned long long)));
@@ -493,30 +484,16 @@ int wavefront_trace(MirtScene* sc, RenderCtx& cx, RenderArgs& a, bool count, hip
   const bool need_pending = sc->any_trans || sc->d.gi != 0;
   const int pending_slots = need_pending ? 2 * (sc->d.bounces + (sc->d.gi > 0 ? sc->d.gi : 0) + 2) : 0;
   const size_t pending_need = (size_t)pending_slots * PENDING_WORDS * pool;
-  if (cx.pending_cap < pending_need) {
-    MIRT_HIP(hipStreamSynchronize(stream));
-    hipFree(cx.pending); cx.pending = nullptr; cx.pending_cap = 0;
-    MIRT_HIP(hipMalloc(&cx.pending, sizeof(float) * pending_need));
-    cx.pending_cap = pending_need;
-  }
+  rc = grow(cx.pending, cx.pending_cap, pending_need, sizeof(float) * pending_need, stream);
+  if (rc != MIRT_OK) return rc;
   a.pending = cx.pending; a.pending_slots = pending_slots;
 
-  if (!sc->wf_trace_blocks) {
-    hipDeviceProp_t prop;
-    MIRT_HIP(hipGetDeviceProperties(&prop, sc->device));
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, wf_trace_kernel<false>, WBLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 4;
-    sc->wf_trace_blocks = prop.multiProcessorCount * per_cu;
-  }
+  if (!sc->wf_trace_blocks) MIRT_HIP(persistent_grid_blocks(sc->device, wf_trace_kernel<false>, WBLOCK, 4, &sc->wf_trace_blocks));
   const int trace_blocks = sc->wf_trace_blocks;
   const size_t gthreads = (size_t)trace_blocks * WBLOCK;
   const size_t spill_need = (size_t)STACK_TOTAL * gthreads;
-  if (cx.spill_cap < spill_need) {
-    MIRT_HIP(hipStreamSynchronize(stream));
-    hipFree(cx.stack_spill); cx.stack_spill = nullptr; cx.spill_cap = 0;
-    MIRT_HIP(hipMalloc(&cx.stack_spill, sizeof(uint32_t) * spill_need));
-    cx.spill_cap = spill_need;
-  }
+  rc = grow(cx.stack_spill, cx.spill_cap, spill_need, sizeof(uint32_t) * spill_need, stream);
+  if (rc != MIRT_OK) return rc;
   a.stack_spill = cx.stack_spill;
 
   WfArgs w;
@@ -541,7 +518,7 @@ int wavefront_trace(MirtScene* sc, RenderCtx& cx, RenderArgs& a, bool count, hip
       if (count) hipLaunchKernelGGL(wf_shade_kernel<true>, dim3(shade_blocks), dim3(SBLOCK), 0, stream, w);
       else hipLaunchKernelGGL(wf_shade_kernel<false>, dim3(shade_blocks), dim3(SBLOCK), 0, stream, w);
       hipEvent_t e0, e1;
-      int rc = next_event(&e0); if (rc) return rc;
+      rc = next_event(&e0); if (rc) return rc;
       rc = next_event(&e1); if (rc) return rc;
       MIRT_HIP(hipEventRecord(e0, stream));
       if (count) hipLaunchKernelGGL(wf_trace_kernel<true>, dim3(trace_blocks), dim3(WBLOCK), 0, stream, w);

@@ -1,10 +1,10 @@
 """The shading-branch scene matrix (test data, generated not stored): small scenes, each aimed at named branches of the shading
 state machine (shade_common.h advance_core / batch_next / unlit_mask, their second copy in wavefront.hip, the host switches of
-render_impl) that the bundled scenes, edge_scenes.py and the fuzzer do not reach.
+plan_call, render_plan.h) that the bundled scenes, edge_scenes.py and the fuzzer do not reach.
 
 Every entry of ALL is a Case: the scene text, the frame size, the oracle branch counters (oracle_lib.BRANCH_FIELDS) the scene was
 built to reach -- tests/test_shade_matrix.py requires each to be >= 10 at spp 0 -- and what the product's host switches make of it
-(`skip_unlit`: False where render_impl turns the unlit-light shortcut off: more than 32 lights, a non-finite colour or exposure).
+(`skip_unlit`: False where plan_call turns the unlit-light shortcut off: more than 32 lights, a non-finite colour or exposure).
 `rng_free`: at spp 0 the scene draws no random number (no roughness, depth of field or gi)."""
 import math
 from collections import namedtuple

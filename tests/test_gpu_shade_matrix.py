@@ -25,7 +25,7 @@ FORMS = {"default": {}, "general": dict(specialise=0), "wavefront": dict(wavefro
 @pytest.mark.parametrize("spp", [0, 1, 5, 16])
 @pytest.mark.parametrize("name", list(shade_scenes.ALL))
 def test_matrix_scene_matches_the_oracle_in_every_kernel_form(name, spp):
-    """spp 5: a resolve that is not a power of two.  The oracle flags mirror the host switches of render_impl: skip_unlit off for
+    """spp 5: a resolve that is not a power of two.  The oracle flags mirror the host switches of plan_call (render_plan.h): skip_unlit off for
     more than 32 lights and for non-finite colours (Case.skip_unlit).  Default options against the reference-walk mode: both
     images byte for byte, float image included, and the same number of rays."""
     case = shade_scenes.ALL[name]

@@ -8,11 +8,14 @@ from .api import (MirtError, StlConfig, RawConfig, parseInput, parseText, synthe
                   camera_rays, pack_rays, unpack_hits, Camera, update_spheres, update_triangles, render_accumulate_pixels,
                   select_pixels, finalize_counts, render_adaptive, hit_features, denoise,
                   denoise_work_bytes, denoise_frame, get_spheres, get_triangles, prev_features, temporal_accumulate,
-                  TemporalAccumulator)
+                  TemporalAccumulator, Shading, make_plane, update_sphere_materials, update_triangle_materials,
+                  get_sphere_materials, get_triangle_materials)
 
 __all__ = ["MirtError", "StlConfig", "RawConfig", "parseInput", "parseText", "syntheticScene", "initRawConfigFromStl",
            "copyConfigDataToDevice", "freeRawConfigDeviceMemory", "build_lbvh_karas", "render", "render_params",
            "num_pixels", "scatter_part", "write_png", "lib", "render_accumulate", "finalize", "Ray", "Hit", "trace_rays",
            "camera_rays", "pack_rays", "unpack_hits", "Camera", "update_spheres", "update_triangles", "render_accumulate_pixels",
            "select_pixels", "finalize_counts", "render_adaptive", "hit_features", "denoise", "denoise_work_bytes", "denoise_frame",
-           "get_spheres", "get_triangles", "prev_features", "temporal_accumulate", "TemporalAccumulator"]
+           "get_spheres", "get_triangles", "prev_features", "temporal_accumulate", "TemporalAccumulator",
+           "Shading", "make_plane", "update_sphere_materials", "update_triangle_materials", "get_sphere_materials",
+           "get_triangle_materials"]

@@ -56,6 +56,11 @@ class Camera(C.Structure):
                 ("dof_focus", C.c_float), ("dof_lens", C.c_float), ("fisheye", C.c_int32), ("panorama", C.c_int32)]
 
 
+class Shading(C.Structure):
+    """MirtShading: bounces, gi and expose of a scene (RawConfig.shading / set_shading); expose +inf = exposure off."""
+    _fields_ = [("bounces", C.c_int32), ("gi", C.c_int32), ("expose", C.c_float)]
+
+
 def _camera_with(cam, fields):
     """A copy of `cam` with the keyword fields replaced (a Vec3 field takes a Vec3 or three numbers)."""
     out = Camera.from_buffer_copy(bytes(cam))
@@ -125,6 +130,10 @@ EXPORTS = [
     "mirt_render_accumulate_pixels", "mirt_select_pixels", "mirt_finalize_counts",
     "mirt_hit_features", "mirt_denoise", "mirt_denoise_work_bytes",
     "mirt_scene_get_spheres", "mirt_scene_get_triangles", "mirt_prev_features", "mirt_temporal_accumulate",
+    "mirt_scene_get_lights", "mirt_scene_set_lights", "mirt_scene_get_planes", "mirt_scene_set_planes", "mirt_make_plane",
+    "mirt_scene_get_shading", "mirt_scene_set_shading", "mirt_scene_update_sphere_materials", "mirt_scene_update_triangle_materials",
+    "mirt_scene_get_sphere_materials", "mirt_scene_get_triangle_materials", "mirt_multi_set_lights", "mirt_multi_set_planes",
+    "mirt_multi_set_shading",
 ]
 
 _lib = None
@@ -207,6 +216,21 @@ def lib():
         L.mirt_prev_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mirt_temporal_accumulate.argtypes = [C.POINTER(RenderParams), C.POINTER(Camera)] + [C.c_void_p] * 8 + [C.c_int, C.c_float, C.c_float] + \
                                               [C.c_void_p] * 4
+    if hasattr(L, "mirt_scene_set_lights"):      # (shading values in place: likewise)
+        L.mirt_scene_get_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mirt_scene_set_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mirt_scene_get_planes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.mirt_scene_set_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.mirt_make_plane.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mirt_scene_get_shading.argtypes = [C.c_void_p, C.POINTER(Shading)]
+        L.mirt_scene_set_shading.argtypes = [C.c_void_p, C.POINTER(Shading)]
+        for f in (L.mirt_scene_update_sphere_materials, L.mirt_scene_update_triangle_materials):
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        for f in (L.mirt_scene_get_sphere_materials, L.mirt_scene_get_triangle_materials):
+            f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.mirt_multi_set_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mirt_multi_set_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.mirt_multi_set_shading.argtypes = [C.c_void_p, C.POINTER(Shading)]
     _lib = L
     return L
 
@@ -334,6 +358,53 @@ class RawConfig:
         _check(lib().mirt_scene_set_camera(self._h, C.byref(new)))
         return new
 
+    def lights(self):
+        """mirt_scene_get_lights: (suns, bulbs) as numpy layouts.LIGHT arrays -- v is a sun's direction or a bulb's position --
+        as the scene was created or as set_lights left them."""
+        import numpy as np
+        from . import layouts
+        suns = np.zeros(self.desc.num_suns, dtype=layouts.LIGHT)
+        bulbs = np.zeros(self.desc.num_bulbs, dtype=layouts.LIGHT)
+        _check(lib().mirt_scene_get_lights(self._h, suns.ctypes.data if len(suns) else None, bulbs.ctypes.data if len(bulbs) else None))
+        return suns, bulbs
+
+    def set_lights(self, suns=None, bulbs=None, stream=None):
+        """mirt_scene_set_lights: new suns and / or bulbs (numpy layouts.LIGHT arrays of the scene's num_suns / num_bulbs
+        records; None leaves that kind as it is).  The counts are fixed: a zero colour switches a light off.  The scene stays
+        built; a frame in flight keeps its lights.  Asynchronous on `stream` (default: torch's current stream)."""
+        arrays = [_records(a, name, _light_dtype(), n) for a, name, n in ((suns, "suns", self.desc.num_suns), (bulbs, "bulbs", self.desc.num_bulbs))]
+        _check(lib().mirt_scene_set_lights(self._h, _host_ptr(arrays[0]), _host_ptr(arrays[1]), _stream_ptr(stream)))
+
+    def planes(self):
+        """mirt_scene_get_planes: every plane as a numpy layouts.PLANE array."""
+        import numpy as np
+        from . import layouts
+        out = np.zeros(self.desc.num_planes, dtype=layouts.PLANE)
+        _check(lib().mirt_scene_get_planes(self._h, 0, len(out), _host_ptr(out)))
+        return out
+
+    def set_planes(self, planes, first=0, stream=None):
+        """mirt_scene_set_planes: planes first .. first+n-1 take the records of `planes` (numpy layouts.PLANE [n]; make_plane
+        makes one the way the parser does), taken as given.  The scene stays built; a frame in flight keeps its planes.
+        Asynchronous on `stream` (default: torch's current stream)."""
+        from . import layouts
+        a = _records(planes, "planes", layouts.PLANE, None)
+        _check(lib().mirt_scene_set_planes(self._h, _host_ptr(a), int(first), len(a), _stream_ptr(stream)))
+
+    def shading(self):
+        """mirt_scene_get_shading: the scene's bounces, gi and expose as a Shading."""
+        sh = Shading()
+        _check(lib().mirt_scene_get_shading(self._h, C.byref(sh)))
+        return sh
+
+    def set_shading(self, sh=None, **fields):
+        """mirt_scene_set_shading: `sh` (default: the current settings) with the keyword fields replaced, e.g.
+        set_shading(expose=2.0) or set_shading(bounces=2, gi=1).  Applies to the calls issued afterwards; a frame in flight keeps
+        its settings.  Returns the Shading that was set."""
+        new = _shading_with(sh if sh is not None else self.shading(), fields)
+        _check(lib().mirt_scene_set_shading(self._h, C.byref(new)))
+        return new
+
     def tree(self):
         """(nodes, codes, refs, bounds) in the reference's numbering -- for parity tests."""
         import numpy as np
@@ -346,6 +417,58 @@ class RawConfig:
         _check(lib().mirt_get_tree(self._h, nodes.ctypes.data if n else None, codes.ctypes.data if n else None,
                                    refs.ctypes.data if n else None, bounds.ctypes.data))
         return nodes, codes, refs, bounds
+
+
+def _light_dtype():
+    from . import layouts
+    return layouts.LIGHT
+
+
+def _records(a, name, dtype, count):
+    """ValueError unless `a` is None or a C-contiguous one-dimensional numpy array of `dtype` (of `count` records, if given);
+    returns it (None stays None)."""
+    import numpy as np
+    if a is None:
+        return None
+    if not isinstance(a, np.ndarray):
+        raise ValueError(f"{name} must be a numpy array")
+    if a.dtype != dtype:
+        raise ValueError(f"{name} has dtype {a.dtype}; expected {dtype}")
+    if a.ndim != 1 or (count is not None and a.shape[0] != count):
+        raise ValueError(f"{name} has shape {list(a.shape)}; expected [{'n' if count is None else count}]")
+    if not a.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"{name} must be contiguous")
+    return a
+
+
+def _host_ptr(a):
+    return C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+
+
+def _shading_with(sh, fields):
+    """A copy of `sh` with the keyword fields replaced."""
+    out = Shading.from_buffer_copy(bytes(sh))
+    names = dict(Shading._fields_)
+    for k, v in fields.items():
+        if k not in names:
+            raise ValueError(f"{k} is not a shading field; expected one of {sorted(names)}")
+        setattr(out, k, v)
+    return out
+
+
+def make_plane(abcd, mat):
+    """mirt_make_plane: the record (numpy layouts.PLANE, one element) the parser makes of a `plane a b c d` line under material
+    `mat` (a layouts.MAT record): nor and point by the parser's own arithmetic.  Host only."""
+    import numpy as np
+    from . import layouts
+    c = np.ascontiguousarray(abcd, dtype=np.float32)
+    if c.shape != (4,):
+        raise ValueError(f"abcd has shape {list(c.shape)}; expected [4]")
+    mm = np.zeros(1, dtype=layouts.MAT)
+    mm[0] = mat
+    out = np.zeros(1, dtype=layouts.PLANE)
+    _check(lib().mirt_make_plane(c.ctypes.data, mm.ctypes.data, out.ctypes.data))
+    return out
 
 
 def initRawConfigFromStl(stl, device=0):
@@ -386,6 +509,25 @@ class MultiGpu:
         afterwards."""
         new = _camera_with(cam, fields)
         _check(lib().mirt_multi_set_camera(self._h, C.byref(new)))
+        return new
+
+    def set_lights(self, suns=None, bulbs=None):
+        """mirt_multi_set_lights: RawConfig.set_lights on every device's scene, for the frames submitted afterwards."""
+        d = self._keep.desc
+        arrays = [_records(a, name, _light_dtype(), n) for a, name, n in ((suns, "suns", d.num_suns), (bulbs, "bulbs", d.num_bulbs))]
+        _check(lib().mirt_multi_set_lights(self._h, _host_ptr(arrays[0]), _host_ptr(arrays[1])))
+
+    def set_planes(self, planes, first=0):
+        """mirt_multi_set_planes: RawConfig.set_planes on every device's scene, for the frames submitted afterwards."""
+        from . import layouts
+        a = _records(planes, "planes", layouts.PLANE, None)
+        _check(lib().mirt_multi_set_planes(self._h, _host_ptr(a), int(first), len(a)))
+
+    def set_shading(self, sh, **fields):
+        """mirt_multi_set_shading: `sh` (with the keyword fields replaced) on every device's scene, for the frames submitted
+        afterwards."""
+        new = _shading_with(sh, fields)
+        _check(lib().mirt_multi_set_shading(self._h, C.byref(new)))
         return new
 
     def render_frame(self, width, height, spp, stripe_rows=4):
@@ -595,6 +737,38 @@ def update_triangles(raw, d_verts, first=0, stream=None):
     _tensor(d_verts, "d_verts", _f32(), [None, 9])
     _on_device(((d_verts, "d_verts"),), raw.device)
     _check(lib().mirt_scene_update_triangles(raw._h, _ptr(d_verts), int(first), d_verts.shape[0], _stream_ptr(stream)))
+
+
+def update_sphere_materials(raw, d_mats, first=0, stream=None):
+    """mirt_scene_update_sphere_materials: spheres first .. first+n-1 (file order) take their material from d_mats (float32
+    [n, 11]: colour rgb, shininess rgb, trans rgb, ior, roughness -- layouts.MAT's order; contiguous, on the scene's device).
+    Asynchronous on `stream` (default: torch's current stream); the scene stays built (n = 0 changes nothing).  The next render
+    waits once, on the host, for the update's kernels."""
+    _tensor(d_mats, "d_mats", _f32(), [None, 11])
+    _on_device(((d_mats, "d_mats"),), raw.device)
+    _check(lib().mirt_scene_update_sphere_materials(raw._h, _ptr(d_mats), int(first), d_mats.shape[0], _stream_ptr(stream)))
+
+
+def update_triangle_materials(raw, d_mats, first=0, stream=None):
+    """mirt_scene_update_triangle_materials: update_sphere_materials for triangles first .. first+n-1 (file order)."""
+    _tensor(d_mats, "d_mats", _f32(), [None, 11])
+    _on_device(((d_mats, "d_mats"),), raw.device)
+    _check(lib().mirt_scene_update_triangle_materials(raw._h, _ptr(d_mats), int(first), d_mats.shape[0], _stream_ptr(stream)))
+
+
+def get_sphere_materials(raw, d_mats, first=0, stream=None):
+    """mirt_scene_get_sphere_materials: the materials of spheres first .. first+n-1 into d_mats (float32 [n, 11], contiguous, on
+    the scene's device): what update_sphere_materials was given, or the file's values.  Asynchronous on `stream`."""
+    _tensor(d_mats, "d_mats", _f32(), [None, 11])
+    _on_device(((d_mats, "d_mats"),), raw.device)
+    _check(lib().mirt_scene_get_sphere_materials(raw._h, int(first), d_mats.shape[0], _ptr(d_mats), _stream_ptr(stream)))
+
+
+def get_triangle_materials(raw, d_mats, first=0, stream=None):
+    """mirt_scene_get_triangle_materials: get_sphere_materials for triangles first .. first+n-1."""
+    _tensor(d_mats, "d_mats", _f32(), [None, 11])
+    _on_device(((d_mats, "d_mats"),), raw.device)
+    _check(lib().mirt_scene_get_triangle_materials(raw._h, int(first), d_mats.shape[0], _ptr(d_mats), _stream_ptr(stream)))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -863,7 +1037,9 @@ def temporal_accumulate(d_out_accum, d_out_accum_sq, d_out_counts, d_accum, d_ac
 
 
 class TemporalAccumulator:
-    """Frames of an animated scene that reuse the previous frame's samples.  Allocates once: this frame's moments and two history
+    """Frames of an animated scene that reuse the previous frame's samples.  (A history gathered under other lights, planes,
+    materials or shading settings is stale -- reprojection follows surface points, not what they looked like: after set_lights,
+    set_planes, set_shading or a material update call reset(), or keep max_history low.)  Allocates once: this frame's moments and two history
     sets used in turn, two feature buffers, the reprojected features, rays, hits, the snapshots of the spheres and triangles as
     the previous frame saw them, the denoiser's workspace and the image.  The caller moves the camera (raw.set_camera), moves
     geometry (update_spheres / update_triangles) and rebuilds (build_lbvh_karas) between frame() calls.  The scene's camera must

@@ -1,6 +1,7 @@
 // C ABI glue for the device side of libmirt.so (include/mirt.h): scene upload, build, render, stats.
 #include "scene_dev.h"
 #include "host_scene.h"
+#include "material_flags.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -23,14 +24,14 @@ int upload(T** dst, const std::vector<T>& src)
   return MIRT_OK;
 }
 
-bool nonzero(const MirtRGB& c) { return !(fabsf(c.r) < 1e-6f && fabsf(c.g) < 1e-6f && fabsf(c.b) < 1e-6f); }
-bool finite_rgb(const MirtRGB& c) { return std::isfinite(c.r) && std::isfinite(c.g) && std::isfinite(c.b); }
-
-void pack_mat(const MirtMaterials& m, float4* out)
+// a primitive's material: its three float4 on the device, its facts (material_flags.h) into the scene's
+void take_mat(MirtScene* sc, const MirtMaterials& mat, float4* out)
 {
-  out[0] = make_float4(m.color.r, m.color.g, m.color.b, m.shininess.r);
-  out[1] = make_float4(m.shininess.g, m.shininess.b, m.trans.r, m.trans.g);
-  out[2] = make_float4(m.trans.b, m.ior, m.roughness, 0.0f);
+  float m[11];
+  static_assert(sizeof(MirtMaterials) == sizeof(m), "MirtMaterials is 11 floats");
+  memcpy(m, &mat, sizeof(m));
+  pack_mat(m, out);
+  sc->prim_flags |= material_flags(m);
 }
 
 // mode: the option selects what is computed or visited (another tree, another walk, another render path) -- as opposed to a
@@ -145,10 +146,7 @@ int scene_create(const MirtSceneDesc* d, int device, MirtScene** out)
   for (int i = 0; i < sc->Ns; ++i) {
     const MirtSphere& s = d->spheres[i];
     spheres[i] = make_float4(s.c.x, s.c.y, s.c.z, s.r);
-    pack_mat(s.mat, &mats[3 * (size_t)i]);
-    if (nonzero(s.mat.trans)) sc->any_trans = true;
-    if (s.mat.roughness > 0.0f) sc->any_rough = true;
-    if (!finite_rgb(s.mat.color)) sc->colors_finite = false;
+    take_mat(sc, s.mat, &mats[3 * (size_t)i]);
   }
   for (int i = 0; i < sc->Nt; ++i) {
     const MirtTriangle& t = d->triangles[i];
@@ -158,10 +156,7 @@ int scene_create(const MirtSceneDesc* d, int device, MirtScene** out)
     verts[3 * (size_t)i + 0] = make_float4(t.p0.x, t.p0.y, t.p0.z, 0.0f);
     verts[3 * (size_t)i + 1] = make_float4(t.p1.x, t.p1.y, t.p1.z, 0.0f);
     verts[3 * (size_t)i + 2] = make_float4(t.p2.x, t.p2.y, t.p2.z, 0.0f);
-    pack_mat(t.mat, &mats[3 * ((size_t)sc->Ns + i)]);
-    if (nonzero(t.mat.trans)) sc->any_trans = true;
-    if (t.mat.roughness > 0.0f) sc->any_rough = true;
-    if (!finite_rgb(t.mat.color)) sc->colors_finite = false;
+    take_mat(sc, t.mat, &mats[3 * ((size_t)sc->Ns + i)]);
   }
   std::vector<MirtPrimRef> refs(d->prim_refs, d->prim_refs + N);
   for (int i = 0; i < N; ++i) {
@@ -170,33 +165,17 @@ int scene_create(const MirtSceneDesc* d, int device, MirtScene** out)
       delete sc; set_error("mirt_scene_create: primitive reference out of range"); return MIRT_ERR_ARG;
     }
   }
+  // planes and lights: the host keeps what it was given (mirt_scene_get_planes / _get_lights, and the facts they contribute)
+  sc->planes_host.assign(d->planes, d->planes + d->num_planes);
+  sc->suns_host.resize((size_t)d->num_suns); sc->bulbs_host.resize((size_t)d->num_bulbs);
+  for (int i = 0; i < d->num_suns; ++i) sc->suns_host[i] = {d->suns[i].dir, d->suns[i].color};
+  for (int i = 0; i < d->num_bulbs; ++i) sc->bulbs_host[i] = {d->bulbs[i].point, d->bulbs[i].color};
   std::vector<PlaneDev> planes((size_t)d->num_planes);
-  for (int i = 0; i < d->num_planes; ++i) {
-    const MirtPlane& p = d->planes[i];
-    PlaneDev& q = planes[i];
-    q.nx = p.nor.x; q.ny = p.nor.y; q.nz = p.nor.z; q.px = p.point.x; q.py = p.point.y; q.pz = p.point.z;
-    const float m[11] = {p.mat.color.r, p.mat.color.g, p.mat.color.b, p.mat.shininess.r, p.mat.shininess.g, p.mat.shininess.b,
-                         p.mat.trans.r, p.mat.trans.g, p.mat.trans.b, p.mat.ior, p.mat.roughness};
-    memcpy(q.mat, m, sizeof(m)); q.pad = 0.0f;
-    if (nonzero(p.mat.trans)) sc->any_trans = true;
-    if (p.mat.roughness > 0.0f) sc->any_rough = true;
-    if (!finite_rgb(p.mat.color)) sc->colors_finite = false;
-  }
-  for (int i = 0; i < d->num_suns; ++i) if (!finite_rgb(d->suns[i].color)) sc->colors_finite = false;
-  for (int i = 0; i < d->num_bulbs; ++i) if (!finite_rgb(d->bulbs[i].color)) sc->colors_finite = false;
-  if (!std::isfinite(d->expose) && d->expose != INFINITY) sc->colors_finite = false;
+  for (int i = 0; i < d->num_planes; ++i) planes[i] = plane_dev(d->planes[i]);
   std::vector<LightDev> suns((size_t)d->num_suns), bulbs((size_t)d->num_bulbs);
-  for (int i = 0; i < d->num_suns; ++i) {
-    const MirtVec3& v = d->suns[i].dir;
-    // vec3::normalize (vec3.cuh:72-82) -- this translation unit is built with -ffp-contract=off
-    const float mag = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z);
-    float nx = 0.0f, ny = 0.0f, nz = 0.0f;
-    const float diff = fabsf(mag - 0.0f), largest = fmaxf(fabsf(mag), fabsf(0.0f));
-    const bool zero = (largest < 1e-6f) ? (diff < 1e-6f) : (diff / largest < 1e-6f);
-    if (!zero) { const float inv = 1.0f / mag; nx = v.x * inv; ny = v.y * inv; nz = v.z * inv; }
-    suns[i] = {v.x, v.y, v.z, d->suns[i].color.r, d->suns[i].color.g, d->suns[i].color.b, nx, ny, nz, 1.0f / nx, 1.0f / ny, 1.0f / nz};
-  }
-  for (int i = 0; i < d->num_bulbs; ++i) bulbs[i] = {d->bulbs[i].point.x, d->bulbs[i].point.y, d->bulbs[i].point.z, d->bulbs[i].color.r, d->bulbs[i].color.g, d->bulbs[i].color.b, 0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < d->num_suns; ++i) suns[i] = sun_dev(sc->suns_host[i]);
+  for (int i = 0; i < d->num_bulbs; ++i) bulbs[i] = bulb_dev(sc->bulbs_host[i]);
+  refresh_host_facts(sc);
   sc->d.spheres = nullptr; sc->d.triangles = nullptr; sc->d.prim_refs = nullptr; sc->d.planes = nullptr; sc->d.suns = nullptr; sc->d.bulbs = nullptr;
 
   int rc = MIRT_OK;
@@ -289,6 +268,7 @@ void mirt_scene_destroy(MirtScene* sc)
   if (sc->ev1) hipEventDestroy(sc->ev1);
   if (sc->so_ev) hipEventDestroy(sc->so_ev);
   hipFree(sc->so_order); hipFree(sc->so_keys); hipFree(sc->so_keys2); hipFree(sc->so_ws);
+  free_shading_state(sc);
   delete sc;
 }
 
@@ -439,6 +419,82 @@ int mirt_scene_get_triangles(MirtScene* sc, int first, int count, void* d_verts_
   if (!sc) { set_error("mirt_scene_get_triangles: null scene"); return MIRT_ERR_ARG; }
   MIRT_HIP(hipSetDevice(sc->device));
   return get_triangles(sc, first, count, d_verts_out, (hipStream_t)stream);
+}
+
+int mirt_scene_get_lights(const MirtScene* sc, MirtLight* suns_out, MirtLight* bulbs_out)
+{
+  if (!sc) { set_error("mirt_scene_get_lights: null scene"); return MIRT_ERR_ARG; }
+  if (suns_out && !sc->suns_host.empty()) memcpy(suns_out, sc->suns_host.data(), sizeof(MirtLight) * sc->suns_host.size());
+  if (bulbs_out && !sc->bulbs_host.empty()) memcpy(bulbs_out, sc->bulbs_host.data(), sizeof(MirtLight) * sc->bulbs_host.size());
+  return MIRT_OK;
+}
+
+int mirt_scene_set_lights(MirtScene* sc, const MirtLight* suns, const MirtLight* bulbs, void* stream)
+{
+  if (!sc) { set_error("mirt_scene_set_lights: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return set_lights(sc, suns, bulbs, (hipStream_t)stream);
+}
+
+int mirt_scene_get_planes(const MirtScene* sc, int first, int count, MirtPlane* out)
+{
+  if (!sc) { set_error("mirt_scene_get_planes: null scene"); return MIRT_ERR_ARG; }
+  bool go = false;
+  const int rc = check_range("mirt_scene_get_planes", out, first, count, sc->d.num_planes, alignof(MirtPlane), &go);
+  if (rc != MIRT_OK || !go) return rc;
+  memcpy(out, sc->planes_host.data() + first, sizeof(MirtPlane) * (size_t)count);
+  return MIRT_OK;
+}
+
+int mirt_scene_set_planes(MirtScene* sc, const MirtPlane* planes, int first, int count, void* stream)
+{
+  if (!sc) { set_error("mirt_scene_set_planes: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return set_planes(sc, planes, first, count, (hipStream_t)stream);
+}
+
+int mirt_scene_get_shading(const MirtScene* sc, MirtShading* out)
+{
+  if (!sc || !out) { set_error(sc ? "mirt_scene_get_shading: null argument" : "mirt_scene_get_shading: null scene"); return MIRT_ERR_ARG; }
+  out->bounces = sc->d.bounces; out->gi = sc->d.gi; out->expose = sc->d.expose;
+  return MIRT_OK;
+}
+
+// Host state only, like the camera: render.hip copies these fields into the RenderArgs of every call it issues.
+int mirt_scene_set_shading(MirtScene* sc, const MirtShading* sh)
+{
+  if (!sc || !sh) { set_error(sc ? "mirt_scene_set_shading: null argument" : "mirt_scene_set_shading: null scene"); return MIRT_ERR_ARG; }
+  sc->d.bounces = sh->bounces; sc->d.gi = sh->gi; sc->d.expose = sh->expose;
+  refresh_host_facts(sc);
+  return MIRT_OK;
+}
+
+int mirt_scene_update_sphere_materials(MirtScene* sc, const void* d_mats, int first, int count, void* stream)
+{
+  if (!sc) { set_error("mirt_scene_update_sphere_materials: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return update_materials(sc, "mirt_scene_update_sphere_materials", d_mats, 0, sc->Ns, first, count, (hipStream_t)stream);
+}
+
+int mirt_scene_update_triangle_materials(MirtScene* sc, const void* d_mats, int first, int count, void* stream)
+{
+  if (!sc) { set_error("mirt_scene_update_triangle_materials: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return update_materials(sc, "mirt_scene_update_triangle_materials", d_mats, sc->Ns, sc->Nt, first, count, (hipStream_t)stream);
+}
+
+int mirt_scene_get_sphere_materials(MirtScene* sc, int first, int count, void* d_mats_out, void* stream)
+{
+  if (!sc) { set_error("mirt_scene_get_sphere_materials: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return get_materials(sc, "mirt_scene_get_sphere_materials", 0, sc->Ns, first, count, d_mats_out, (hipStream_t)stream);
+}
+
+int mirt_scene_get_triangle_materials(MirtScene* sc, int first, int count, void* d_mats_out, void* stream)
+{
+  if (!sc) { set_error("mirt_scene_get_triangle_materials: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return get_materials(sc, "mirt_scene_get_triangle_materials", sc->Ns, sc->Nt, first, count, d_mats_out, (hipStream_t)stream);
 }
 
 int mirt_prev_features(MirtScene* sc, const void* d_rays, const void* d_hits, int64_t n, const void* d_prev_xyzr, const void* d_prev_verts,

@@ -314,6 +314,13 @@ int mirt_synthetic_scene(uint64_t seed, int num_spheres, int num_triangles, Mirt
 
 void mirt_host_scene_destroy(MirtHostScene* hs) { delete hs; }
 
+int mirt_make_plane(const float abcd[4], const MirtMaterials* mat, MirtPlane* out)
+{
+  if (!abcd || !mat || !out) { mirt::set_error("mirt_make_plane: null argument"); return MIRT_ERR_ARG; }
+  *out = mirt::make_plane(abcd[0], abcd[1], abcd[2], abcd[3], *mat);
+  return MIRT_OK;
+}
+
 int mirt_host_scene_desc(const MirtHostScene* hs, MirtSceneDesc* out)
 {
   if (!hs || !out) { mirt::set_error("null argument"); return MIRT_ERR_ARG; }

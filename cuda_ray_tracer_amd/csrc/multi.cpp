@@ -242,6 +242,37 @@ int mirt_multi_set_camera(MirtMulti* mm, const MirtCamera* cam)
   return MIRT_OK;
 }
 
+// The scene's setter on every device, on that device's default stream, and the records in place before the call returns: the
+// frames submitted afterwards run on the slots' own (non-blocking) streams, which no stream order ties to this one.
+int mirt_multi_set_lights(MirtMulti* mm, const MirtLight* suns, const MirtLight* bulbs)
+{
+  if (!mm) { mirt::set_error("mirt_multi_set_lights: null argument"); return MIRT_ERR_ARG; }
+  for (MirtScene* sc : mm->scene) {
+    int rc = mirt_scene_set_lights(sc, suns, bulbs, nullptr);
+    if (rc != MIRT_OK) return rc;
+    MM_HIP(hipStreamSynchronize(nullptr));
+  }
+  return MIRT_OK;
+}
+
+int mirt_multi_set_planes(MirtMulti* mm, const MirtPlane* planes, int first, int count)
+{
+  if (!mm) { mirt::set_error("mirt_multi_set_planes: null argument"); return MIRT_ERR_ARG; }
+  for (MirtScene* sc : mm->scene) {
+    int rc = mirt_scene_set_planes(sc, planes, first, count, nullptr);
+    if (rc != MIRT_OK) return rc;
+    MM_HIP(hipStreamSynchronize(nullptr));
+  }
+  return MIRT_OK;
+}
+
+int mirt_multi_set_shading(MirtMulti* mm, const MirtShading* sh)
+{
+  if (!mm || !sh) { mirt::set_error("mirt_multi_set_shading: null argument"); return MIRT_ERR_ARG; }
+  for (MirtScene* sc : mm->scene) { int rc = mirt_scene_set_shading(sc, sh); if (rc != MIRT_OK) return rc; }
+  return MIRT_OK;
+}
+
 int mirt_multi_get_stats(MirtMulti* mm, int part, MirtStats* out)
 {
   if (!mm || part < 0 || part >= mm->n || !out) { mirt::set_error("mirt_multi_get_stats: bad argument"); return MIRT_ERR_ARG; }

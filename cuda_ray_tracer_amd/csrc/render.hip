@@ -604,14 +604,20 @@ struct RenderCall {
   bool count() const { return (p->flags & MIRT_RENDER_COUNTERS) != 0; }
 };
 
-static SceneFacts scene_facts(const MirtScene* sc)
+// The first thing that plans a call: it settles the facts -- after a material update in place the primitives' share of
+// any_trans / any_rough / colors_finite is known only to the device, and this waits, once, for the update's reduction
+// (update_shading.hip) -- and recombines them with the host's share (planes, lights, exposure).
+static int scene_facts(MirtScene* sc, SceneFacts* out)
 {
+  const int rc = settle_facts(sc);
+  if (rc != MIRT_OK) return rc;
   SceneFacts f;
   f.N = sc->N; f.Nt = sc->Nt; f.grid_ok = sc->grid_ok;
   f.has_quantised = sc->root_ref_q != REF_NONE; f.has_wide = sc->root_ref_w != REF_NONE;
   f.colors_finite = sc->colors_finite; f.any_trans = sc->any_trans; f.any_rough = sc->any_rough;
   f.gi = sc->d.gi; f.bounces = sc->d.bounces; f.num_suns = sc->d.num_suns; f.num_bulbs = sc->d.num_bulbs;
-  return f;
+  *out = f;
+  return MIRT_OK;
 }
 
 // step 1: the call's arguments.  MIRT_OK with *npix = 0: an empty part, nothing to do.
@@ -918,7 +924,10 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
   CallShape shape;
   shape.npix = npix; shape.sample_first = sample_first; shape.sample_count = sample_count; shape.spp = p->spp;
   shape.accumulate = d_accum != nullptr; shape.num_listed = c.sparse() ? ax->num_listed : -1; shape.counters = count;
-  const CallPlan pl = plan_call(scene_facts(sc), sc->opt, shape);
+  SceneFacts facts;
+  rc = scene_facts(sc, &facts);
+  if (rc != MIRT_OK) return rc;
+  const CallPlan pl = plan_call(facts, sc->opt, shape);
   const int blocks = size_grid(sc, pl, count, stream);
   const int chunk_shift = plan_chunk_shift(pl.launch_samples_max, blocks, sc->opt.chunk_shift);
   const size_t nchunks = (size_t)((pl.slab_samples_max + (1ll << chunk_shift) - 1) >> chunk_shift);

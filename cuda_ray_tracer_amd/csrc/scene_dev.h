@@ -266,6 +266,20 @@ struct MirtScene {
   bool any_rough = false;
   int query_blocks = 0;                    // grid size of the ray-query kernel on this scene's device (query.hip; filled on first use)
   bool updated = false;                    // geometry updated in place since the last build (update.hip): mirt_camera_rays waits for the build like every other call
+  // Shading values updated in place (update_shading.hip).  The three facts above are prim_flags | host_flags (MAT_* bits,
+  // material_flags.h), by source: the primitives' materials -- after a material update known only to the device, until
+  // settle_facts has read the reduction's word -- and what the host holds: planes, lights, exposure.
+  unsigned prim_flags = 0, host_flags = 0;
+  std::vector<MirtLight> suns_host, bulbs_host;      // what mirt_scene_create / mirt_scene_set_lights were given
+  std::vector<MirtPlane> planes_host;
+  unsigned char* mat_flags = nullptr;      // device: material_flags of every primitive (spheres, then triangles), padded with zeros to whole words; made by the first material update
+  unsigned* flags_or = nullptr;            // device: the OR over mat_flags, written by the reduction that ends a material update
+  unsigned* flags_or_host = nullptr;       // pinned: its copy, valid once facts_ev has passed
+  hipEvent_t facts_ev = nullptr;           // end of the last material update's reduction and copy
+  bool facts_pending = false;              // a material update was issued since prim_flags was read
+  hipStream_t facts_stream = nullptr;      // ... on this stream
+  unsigned char* stage = nullptr; size_t stage_cap = 0;   // pinned staging of the light and plane records on their way to the device
+  hipEvent_t stage_ev = nullptr; bool stage_used = false; // ... and the end of the last copy out of it
 };
 
 namespace mirt {
@@ -308,6 +322,19 @@ int denoise(const MirtRenderParams* p, const void* d_accum, const void* d_accum_
 // update.hip
 int update_spheres(MirtScene* sc, const void* d_spheres, int first, int count, hipStream_t stream);
 int update_triangles(MirtScene* sc, const void* d_verts, int first, int count, hipStream_t stream);
+int wait_for_frames(MirtScene* sc);
+// update_shading.hip
+LightDev sun_dev(const MirtLight& l);
+LightDev bulb_dev(const MirtLight& l);
+PlaneDev plane_dev(const MirtPlane& p);
+void pack_mat(const float m[11], float4* out);
+void refresh_host_facts(MirtScene* sc);
+int settle_facts(MirtScene* sc);
+void free_shading_state(MirtScene* sc);
+int set_lights(MirtScene* sc, const MirtLight* suns, const MirtLight* bulbs, hipStream_t stream);
+int set_planes(MirtScene* sc, const MirtPlane* planes, int first, int count, hipStream_t stream);
+int update_materials(MirtScene* sc, const char* who, const void* d_mats, int base, int total, int first, int count, hipStream_t stream);
+int get_materials(MirtScene* sc, const char* who, int base, int total, int first, int count, void* d_mats_out, hipStream_t stream);
 // temporal.hip
 int get_spheres(MirtScene* sc, int first, int count, void* d_xyzr_out, hipStream_t stream);
 int get_triangles(MirtScene* sc, int first, int count, void* d_verts_out, hipStream_t stream);

@@ -51,14 +51,22 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void update_triangles_kernel(const fl
 // frame before anything is enqueued.  From here on the scene is not built.
 int begin_update(MirtScene* sc)
 {
-  for (int i = 0; i < MIRT_MAX_FRAMES; ++i)
-    if (sc->ctx[i].used) MIRT_HIP(hipEventSynchronize(sc->ctx[i].ev3));
+  const int rc = wait_for_frames(sc);
+  if (rc != MIRT_OK) return rc;
   sc->built = false;
   sc->updated = true;
   return MIRT_OK;
 }
 
 } // namespace
+
+// the last frame of every render context has finished (what an update in place waits for before it enqueues anything)
+int wait_for_frames(MirtScene* sc)
+{
+  for (int i = 0; i < MIRT_MAX_FRAMES; ++i)
+    if (sc->ctx[i].used) MIRT_HIP(hipEventSynchronize(sc->ctx[i].ev3));
+  return MIRT_OK;
+}
 
 int update_spheres(MirtScene* sc, const void* d_spheres, int first, int count, hipStream_t stream)
 {

@@ -332,7 +332,8 @@ int mirt_denoise(const MirtRenderParams* p, const void* d_accum_f32, const void*
  * filled once, config_utils.cu:18-199).  Callers detect the feature by these symbols (MIRT_VERSION stays 3).
  *
  * MirtCamera: the camera fields of MirtSceneDesc, taken as given (the forward / up keyword rule of parse.cpp:60-72 is the
- * parser's business and is not applied); 64 B.  expose, bounces, gi, lights and planes are not part of it and stay fixed. */
+ * parser's business and is not applied); 64 B.  expose, bounces and gi are MirtShading's, lights and planes have setters of their
+ * own (below: "shading values of a built scene in place"). */
 typedef struct MirtCamera { MirtVec3 eye, forward, right, up; float dof_focus, dof_lens; int32_t fisheye, panorama; } MirtCamera;
 int mirt_scene_get_camera(const MirtScene* sc, MirtCamera* out);
 /* The new camera applies to every mirt_render, mirt_render_accumulate, mirt_camera_rays (and mirt_multi_submit) issued after
@@ -347,7 +348,8 @@ int mirt_scene_set_camera(MirtScene* sc, const MirtCamera* cam);
  *              are computed as Triangle(Vertex, Vertex, Vertex, RGB) computes them (object.cuh:177-191): normalize(cross(p1 - p0,
  *              p2 - p0)), the two crosses with nor, 1 / dot, three multiplies -- one rounding per operation, the bits the parser
  *              produces on the host for the same vertices (a zero-area triangle gives NaN in both places)
- * Materials, primitive counts, the order of the primitives, planes and lights do not change.
+ * Primitive counts and the order of the primitives do not change; materials, planes and lights are not touched (they have
+ * update calls of their own, below, which need no build).
  * State: an update marks the scene NOT BUILT: until the next mirt_build_lbvh (issued on the same stream, or after the caller
  * has ordered it behind the update), mirt_render*, mirt_trace_rays, mirt_camera_rays and mirt_get_tree return MIRT_ERR_STATE.
  * Several updates may precede one build.  The build is the full one: the result is exactly the scene that mirt_scene_create +
@@ -369,6 +371,58 @@ int mirt_scene_update_triangles(MirtScene* sc, const void* d_verts, int first, i
  * count > 0. */
 int mirt_scene_get_spheres(MirtScene* sc, int first, int count, void* d_xyzr_out, void* stream);
 int mirt_scene_get_triangles(MirtScene* sc, int first, int count, void* d_verts_out, void* stream);
+
+/* ---- shading values of a built scene in place: lights, planes, materials, bounces / gi / expose ------------- */
+/* Every field of a scene file that the calls above leave fixed.  None of these values is in the record heap the tree is built
+ * from, so no call here needs a mirt_build_lbvh: the scene STAYS BUILT (mirt_render*, mirt_trace_rays, mirt_camera_rays and
+ * mirt_get_tree keep working, the tree keeps its bits), and the render workspaces, the random-number tables and the measured
+ * hand-out order ("sched") stay, as across a camera change -- an order learned under other values can cost time, never a byte.
+ * A scene changed in place renders, bit for bit and counter for counter, what a scene created afresh with the new values renders:
+ * the facts the call plan is made from (is any material transparent or rough, is every colour finite) follow every call.
+ * Not in the reference.  Callers detect the feature by these symbols (MIRT_VERSION stays 3).
+ *
+ * Common to mirt_scene_set_lights, mirt_scene_set_planes and the two material updates:
+ *   Frames in flight read these device arrays: before it enqueues anything the call waits on the host for the last frame of
+ *   every render context, so a frame issued before the call finishes with the old values.  (Ray queries read none of them.)
+ *   The device writes are asynchronous on `stream`; host arrays passed in may be reused as soon as the call returns.  A render
+ *   issued on ANOTHER stream must be ordered behind `stream` by the caller (a material update orders itself: see below).
+ *   MIRT_ERR_ARG: null scene; negative first or count, or a range beyond the array; a null or misaligned pointer with count > 0.
+ *
+ * Lights.  MirtLight is MirtSun / MirtBulb under one name: v is a sun's direction or a bulb's position.  The COUNTS are those the
+ * scene was created with and do not change; a light is switched off by a zero colour.  set: suns / bulbs are arrays of num_suns /
+ * num_bulbs records, NULL = leave that kind as it is.  A sun's device record carries vec3::normalize of its direction and the
+ * reciprocals, computed by the code mirt_scene_create uses.  get: what was set (or created), either pointer may be NULL. */
+typedef struct MirtLight { MirtVec3 v; MirtRGB color; } MirtLight;         /* 24 B */
+int mirt_scene_get_lights(const MirtScene* sc, MirtLight* suns_out, MirtLight* bulbs_out);
+int mirt_scene_set_lights(MirtScene* sc, const MirtLight* suns, const MirtLight* bulbs, void* stream);
+/* Planes first .. first+count-1, records taken as given, as mirt_scene_create takes them: nor and point are what is rendered (a, b,
+ * c, d are carried along).  count 0: MIRT_OK, nothing done.  The number of planes does not change. */
+int mirt_scene_get_planes(const MirtScene* sc, int first, int count, MirtPlane* out);
+int mirt_scene_set_planes(MirtScene* sc, const MirtPlane* planes, int first, int count, void* stream);
+/* The record the parser makes of a `plane a b c d` line (Plane(a, b, c, d, rgb), object.cuh:136-141) with material *mat: nor and
+ * point by the parser's own routine, the same bits.  Host arithmetic, no device.  MIRT_ERR_ARG: a null pointer. */
+int mirt_make_plane(const float abcd[4], const MirtMaterials* mat, MirtPlane* out);
+/* bounces, gi, expose (+inf = exposure off), taken as given.  Exactly like the camera pair: host state only, no device work, no
+ * synchronisation; applies to the calls issued afterwards, a frame already issued keeps the settings it was issued with.
+ * MIRT_ERR_ARG: null scene or struct. */
+typedef struct MirtShading { int32_t bounces, gi; float expose; } MirtShading;
+int mirt_scene_get_shading(const MirtScene* sc, MirtShading* out);
+int mirt_scene_set_shading(MirtScene* sc, const MirtShading* sh);
+/* New materials from device memory (hipMalloc, or a torch data_ptr(), on the scene's device), like the geometry updates -- a scene
+ * can hold millions.  d_mats: float [count][11] = colour rgb, shininess rgb, trans rgb, ior, roughness of spheres / triangles
+ * first .. first+count-1 (file order): MirtMaterials' field order; 4-byte aligned; values taken as they are.  One kernel, one lane
+ * per primitive, writes the three float4 the renderer reads (triangle i sits behind the spheres, at num_spheres + i) and one
+ * byte of facts; a second kernel ORs the bytes of ALL primitives -- a partial update forgets no glass sphere outside its range,
+ * and glass turned opaque takes the pending-children list away again -- into a word the host reads.  count 0: MIRT_OK, nothing
+ * launched.  The first material update of a scene also allocates that byte per primitive and fills it from the device arrays.
+ * ONE HOST WAIT per material update: the next mirt_render* on the scene (on any stream) waits, before it plans anything, for the
+ * update's kernels to finish and reads the word; calls that do not render never wait.
+ * The get calls are the device-to-device inverses (d_mats_out: float [count][11]); asynchronous on `stream`, they wait for
+ * nothing. */
+int mirt_scene_update_sphere_materials(MirtScene* sc, const void* d_mats, int first, int count, void* stream);
+int mirt_scene_update_triangle_materials(MirtScene* sc, const void* d_mats, int first, int count, void* stream);
+int mirt_scene_get_sphere_materials(MirtScene* sc, int first, int count, void* d_mats_out, void* stream);
+int mirt_scene_get_triangle_materials(MirtScene* sc, int first, int count, void* d_mats_out, void* stream);
 
 /* ---- temporal accumulation: the previous frame's samples, reused by reprojection --------------------- */
 /* Not in the reference (every frame starts from nothing).  Callers detect the feature by these symbols (MIRT_VERSION stays 3).
@@ -466,6 +520,12 @@ void mirt_multi_destroy(MirtMulti* mm);
 int mirt_multi_num_parts(const MirtMulti* mm);
 int mirt_multi_set_option(MirtMulti* mm, const char* name, int value);      /* mirt_scene_set_option on every device's scene */
 int mirt_multi_set_camera(MirtMulti* mm, const MirtCamera* cam);            /* mirt_scene_set_camera on every device's scene: frames submitted afterwards */
+/* mirt_scene_set_lights / set_planes / set_shading on every device's scene, for the frames submitted afterwards (frames in
+ * flight keep their values; the call returns once every device holds the new records).  Material updates take device memory on
+ * every device and are not offered for a MirtMulti. */
+int mirt_multi_set_lights(MirtMulti* mm, const MirtLight* suns, const MirtLight* bulbs);
+int mirt_multi_set_planes(MirtMulti* mm, const MirtPlane* planes, int first, int count);
+int mirt_multi_set_shading(MirtMulti* mm, const MirtShading* sh);
 /* Frames in flight: mirt_multi_submit issues one width x height frame at spp samples per pixel on every device and returns at
  * once with a ticket; mirt_multi_wait blocks until that frame is gathered (and copied to host_rgba, nullable, which must stay
  * valid until then).  Up to MIRT_MULTI_MAX_IN_FLIGHT frames may be in flight: consecutive frames overlap on every device (the

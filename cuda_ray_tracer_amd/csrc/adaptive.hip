@@ -243,9 +243,10 @@ int launch_finalize(const void* d_accum, const uint32_t* d_counts, void* d_rgba8
 
 // mirt_select_pixels has no scene to keep its block counts in: one buffer per (device, stream), grown on demand and kept, so
 // that calls on different streams never share one
-struct SelectWs { uint32_t* blocks = nullptr; size_t cap = 0; };
+// (the map is made on first use and never destroyed: an owning buffer must not outlive the HIP runtime, dev_mem.h)
 std::mutex select_mu;
-std::map<std::pair<int, hipStream_t>, SelectWs> select_ws;
+using SelectWs = std::map<std::pair<int, hipStream_t>, DevBuf<uint32_t>>;
+SelectWs& select_ws() { static SelectWs* const ws = new SelectWs(); return *ws; }
 
 } // namespace
 
@@ -310,10 +311,9 @@ int select_pixels(const MirtRenderParams* p, const void* d_accum, const void* d_
   uint32_t* blocks = nullptr;
   {
     std::lock_guard<std::mutex> lock(select_mu);
-    SelectWs& ws = select_ws[std::make_pair(device, stream)];
-    const int rc = grow(ws.blocks, ws.cap, need, 4 * need, stream);
-    if (rc != MIRT_OK) return rc;
-    blocks = ws.blocks;
+    DevBuf<uint32_t>& ws = select_ws()[std::make_pair(device, stream)];
+    MIRT_TRY(ws.grow(need, stream, "select blocks"));
+    blocks = ws;
   }
   SelectPred pr;
   pr.sum = (const float4*)d_accum; pr.sq = (const float4*)d_accum_sq; pr.counts = d_counts;

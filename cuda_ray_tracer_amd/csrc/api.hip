@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -15,12 +16,12 @@ using namespace mirt;
 namespace {
 
 template <typename T>
-int upload(T** dst, const std::vector<T>& src)
+int upload(DevBuf<T>& dst, const std::vector<T>& src)
 {
-  *dst = nullptr;
   if (src.empty()) return MIRT_OK;
-  MIRT_HIP(hipMalloc(dst, sizeof(T) * src.size()));
-  MIRT_HIP(hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
+  const int rc = dst.alloc(src.size(), "upload");
+  if (rc != MIRT_OK) return rc;
+  MIRT_HIP(hipMemcpy(dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
   return MIRT_OK;
 }
 
@@ -134,7 +135,8 @@ int scene_create(const MirtSceneDesc* d, int device, MirtScene** out)
   if (device < 0 || device >= ndev) { set_error("mirt_scene_create: bad device index"); return MIRT_ERR_ARG; }
   MIRT_HIP(hipSetDevice(device));
 
-  MirtScene* sc = new MirtScene();
+  std::unique_ptr<MirtScene> owner(new MirtScene());      // until the scene is handed out, a return gives back whatever it holds by then
+  MirtScene* const sc = owner.get();
   sc->device = device;
   options_from_env(sc->opt);
   sc->d = *d;
@@ -162,7 +164,7 @@ int scene_create(const MirtSceneDesc* d, int device, MirtScene** out)
   for (int i = 0; i < N; ++i) {
     const MirtPrimRef& r = refs[i];
     if (r.type > 1 || (r.type == 0 && (int)r.id >= sc->Ns) || (r.type == 1 && (int)r.id >= sc->Nt)) {
-      delete sc; set_error("mirt_scene_create: primitive reference out of range"); return MIRT_ERR_ARG;
+      set_error("mirt_scene_create: primitive reference out of range"); return MIRT_ERR_ARG;
     }
   }
   // planes and lights: the host keeps what it was given (mirt_scene_get_planes / _get_lights, and the facts they contribute)
@@ -178,8 +180,6 @@ int scene_create(const MirtSceneDesc* d, int device, MirtScene** out)
   refresh_host_facts(sc);
   sc->d.spheres = nullptr; sc->d.triangles = nullptr; sc->d.prim_refs = nullptr; sc->d.planes = nullptr; sc->d.suns = nullptr; sc->d.bulbs = nullptr;
 
-  int rc = MIRT_OK;
-  auto chk = [&](int r) { if (rc == MIRT_OK) rc = r; };
   // record heap: [internal nodes 64 B each | primitive records in sorted order: sphere 16 B, triangle 48 B | 64 B pad] -- the
   // traversal kernel addresses any record with one 32-bit byte offset.  The build fills it (lbvh_build.hip).
   {
@@ -189,48 +189,38 @@ int scene_create(const MirtSceneDesc* d, int device, MirtScene** out)
     const size_t qnode_bytes = (sc->Nt == 0 && N > 1) ? 32 * (size_t)(N - 1) : 0;
     const size_t wnode_bytes = (sc->Nt > 0 && N > 1) ? 64 * (size_t)(N - 1) + 128 : 0;      // wide records (scene_dev.h), line-aligned
     const size_t total = nodes_bytes + sph_bytes + tri_bytes + 64 + qnode_bytes + wnode_bytes;
-    if (total > 0xfffffff0ull) { delete sc; set_error("mirt_scene_create: scene too large for 32-bit record offsets"); return MIRT_ERR_ARG; }
-    hipError_t e = hipMalloc(&sc->heap, total);
-    if (e == hipSuccess) e = hipMemset(sc->heap, 0, total);
-    if (e != hipSuccess) { delete sc; return hip_fail(e, "hipMalloc(heap)", __FILE__, __LINE__); }
+    if (total > 0xfffffff0ull) { set_error("mirt_scene_create: scene too large for 32-bit record offsets"); return MIRT_ERR_ARG; }
+    MIRT_TRY(sc->heap.alloc(total, "heap"));
+    MIRT_HIP(hipMemset(sc->heap, 0, total));
     sc->prim_base = (uint32_t)nodes_bytes;
     sc->qnode_base = qnode_bytes ? (uint32_t)(nodes_bytes + sph_bytes + tri_bytes + 64) : 0u;
     sc->wnode_base = wnode_bytes ? (uint32_t)((nodes_bytes + sph_bytes + tri_bytes + 64 + qnode_bytes + 127) / 128 * 128) : 0u;
-    sc->nodes = reinterpret_cast<float4*>(sc->heap);
+    sc->nodes = reinterpret_cast<float4*>(sc->heap.get());
   }
-  chk(upload(&sc->spheres, spheres)); chk(upload(&sc->tris, tris));
-  chk(upload(&sc->tri_verts, verts)); chk(upload(&sc->mats, mats));
-  chk(upload(&sc->refs_in, refs)); chk(upload(&sc->planes, planes)); chk(upload(&sc->suns, suns)); chk(upload(&sc->bulbs, bulbs));
-  auto alloc = [&](void** p, size_t bytes) { if (rc == MIRT_OK && bytes) { hipError_t e = hipMalloc(p, bytes); if (e != hipSuccess) rc = hip_fail(e, "hipMalloc", __FILE__, __LINE__); } };
+  MIRT_TRY(upload(sc->spheres, spheres)); MIRT_TRY(upload(sc->tris, tris));
+  MIRT_TRY(upload(sc->tri_verts, verts)); MIRT_TRY(upload(sc->mats, mats));
+  MIRT_TRY(upload(sc->refs_in, refs)); MIRT_TRY(upload(sc->planes, planes)); MIRT_TRY(upload(sc->suns, suns)); MIRT_TRY(upload(sc->bulbs, bulbs));
   if (N > 0) {
-    alloc((void**)&sc->codes, 4 * (size_t)N); alloc((void**)&sc->order, 4 * (size_t)N);
-    alloc((void**)&sc->parent, 4 * (2 * (size_t)N - 1)); alloc((void**)&sc->boxes, 24 * (2 * (size_t)N - 1));
-    if (N > 1) { alloc((void**)&sc->child_l, 4 * (size_t)(N - 1)); alloc((void**)&sc->child_r, 4 * (size_t)(N - 1)); alloc((void**)&sc->range, 8 * (size_t)(N - 1)); }
-    alloc((void**)&sc->unit_prim, 4 * ((size_t)sc->Ns + 3 * (size_t)sc->Nt));
-    alloc((void**)&sc->tris_before, 4 * ((size_t)N + 1));
+    const size_t n = (size_t)N;
+    MIRT_TRY(sc->codes.alloc(n, "codes")); MIRT_TRY(sc->order.alloc(n, "order"));
+    MIRT_TRY(sc->parent.alloc(2 * n - 1, "parent")); MIRT_TRY(sc->boxes.alloc(6 * (2 * n - 1), "boxes"));
+    if (N > 1) { MIRT_TRY(sc->child_l.alloc(n - 1, "child_l")); MIRT_TRY(sc->child_r.alloc(n - 1, "child_r")); MIRT_TRY(sc->range.alloc(n - 1, "range")); }
+    MIRT_TRY(sc->unit_prim.alloc((size_t)sc->Ns + 3 * (size_t)sc->Nt, "unit_prim"));
+    MIRT_TRY(sc->tris_before.alloc(n + 1, "tris_before"));
   }
-  alloc((void**)&sc->bounds_keys, 6 * 4);
-  alloc((void**)&sc->qparams, 9 * 4);
-  alloc((void**)&sc->tri_boxes, 32 * (size_t)sc->Nt);
-  for (int i = 0; i < mirt::MIRT_MAX_FRAMES; ++i) {
-    alloc((void**)&sc->ctx[i].counters, 16 * sizeof(unsigned long long));
-    if (rc == MIRT_OK && hipMemset(sc->ctx[i].counters, 0, 16 * sizeof(unsigned long long)) != hipSuccess) rc = MIRT_ERR_HIP;
+  MIRT_TRY(sc->bounds_keys.alloc(6, "bounds_keys"));
+  MIRT_TRY(sc->qparams.alloc(9, "qparams"));
+  MIRT_TRY(sc->tri_boxes.alloc(2 * (size_t)sc->Nt, "tri_boxes"));
+  for (RenderCtx& c : sc->ctx) {
+    MIRT_TRY(c.counters.alloc(16, "counters"));
+    MIRT_HIP(hipMemset(c.counters, 0, 16 * sizeof(unsigned long long)));
   }
-  if (rc == MIRT_OK) {
-    hipError_t e = hipEventCreate(&sc->ev0);
-    if (e == hipSuccess) e = hipEventCreate(&sc->ev1);
-    if (e == hipSuccess) e = hipEventCreate(&sc->so_ev);
-    for (int i = 0; i < mirt::MIRT_MAX_FRAMES && e == hipSuccess; ++i) {
-      e = hipEventCreate(&sc->ctx[i].ev0);
-      if (e == hipSuccess) e = hipEventCreate(&sc->ctx[i].ev1);
-      if (e == hipSuccess) e = hipEventCreate(&sc->ctx[i].ev2);
-      if (e == hipSuccess) e = hipEventCreate(&sc->ctx[i].ev3);
-      if (e == hipSuccess) e = hipEventCreate(&sc->ctx[i].order_ev);
-    }
-    if (e != hipSuccess) rc = hip_fail(e, "hipEventCreate", __FILE__, __LINE__);
+  // (created here, not on first use: a context that has never rendered or sorted is still asked about its events)
+  MIRT_TRY(sc->ev0.create()); MIRT_TRY(sc->ev1.create()); MIRT_TRY(sc->so_ev.create());
+  for (RenderCtx& c : sc->ctx) {
+    MIRT_TRY(c.ev0.create()); MIRT_TRY(c.ev1.create()); MIRT_TRY(c.ev2.create()); MIRT_TRY(c.ev3.create()); MIRT_TRY(c.order_ev.create());
   }
-  if (rc != MIRT_OK) { mirt_scene_destroy(sc); return rc; }
-  *out = sc;
+  *out = owner.release();
   return MIRT_OK;
 }
 
@@ -243,32 +233,6 @@ void mirt_scene_destroy(MirtScene* sc)
   if (!sc) return;
   hipSetDevice(sc->device);
   hipDeviceSynchronize();
-  hipFree(sc->heap); hipFree(sc->spheres); hipFree(sc->tris); hipFree(sc->tri_verts); hipFree(sc->mats); hipFree(sc->refs_in);
-  hipFree(sc->unit_prim); hipFree(sc->tris_before); hipFree(sc->range);
-  hipFree(sc->planes); hipFree(sc->suns); hipFree(sc->bulbs);
-  hipFree(sc->codes); hipFree(sc->order); hipFree(sc->child_l); hipFree(sc->child_r); hipFree(sc->parent); hipFree(sc->boxes); hipFree(sc->build_ws);
-  hipFree(sc->bounds_keys); hipFree(sc->qparams); hipFree(sc->tri_boxes);
-  for (int i = 0; i < mirt::MIRT_MAX_FRAMES; ++i) {
-    mirt::RenderCtx& c = sc->ctx[i];
-    hipFree(c.samples); hipFree(c.stack_spill); hipFree(c.pending); hipFree(c.counters); hipFree(c.args_dev);
-    hipFree(c.chunk_cost); for (uint32_t* o : c.order_out) hipFree(o);
-    hipFree(c.sp_list); hipFree(c.sp_table); hipFree(c.sp_blocks);
-    if (c.ev0) hipEventDestroy(c.ev0);
-    if (c.ev1) hipEventDestroy(c.ev1);
-    if (c.ev2) hipEventDestroy(c.ev2);
-    if (c.ev3) hipEventDestroy(c.ev3);
-    if (c.order_ev) hipEventDestroy(c.order_ev);
-    for (hipEvent_t e : c.slab_ev) hipEventDestroy(e);
-  }
-  rng_cache_free(&sc->rng);
-  hipFree(sc->wf_state); hipFree(sc->wf_rays); hipFree(sc->wf_ctr);
-  if (sc->wf_ctr_host) hipHostFree(sc->wf_ctr_host);
-  for (hipEvent_t e : sc->wf_events) hipEventDestroy(e);
-  if (sc->ev0) hipEventDestroy(sc->ev0);
-  if (sc->ev1) hipEventDestroy(sc->ev1);
-  if (sc->so_ev) hipEventDestroy(sc->so_ev);
-  hipFree(sc->so_order); hipFree(sc->so_keys); hipFree(sc->so_keys2); hipFree(sc->so_ws);
-  free_shading_state(sc);
   delete sc;
 }
 

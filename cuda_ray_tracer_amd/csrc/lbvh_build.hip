@@ -570,11 +570,7 @@ int build_lbvh(MirtScene* sc, hipStream_t stream)
   // sort / refit workspace: one allocation, made before the timed region and kept with the scene (a rebuild reuses it)
   const int sblocks = (n + SORT_TILE - 1) / SORT_TILE;
   const size_t wwords = 4 * (size_t)n + 256 * (size_t)sblocks + 256 + (size_t)(n > 1 ? n - 1 : 0);
-  if (sc->build_ws_words < wwords) {
-    (void)hipFree(sc->build_ws); sc->build_ws = nullptr; sc->build_ws_words = 0;
-    MIRT_HIP(hipMalloc(&sc->build_ws, sizeof(uint32_t) * wwords));
-    sc->build_ws_words = wwords;
-  }
+  if (sc->build_ws.cap() < wwords) MIRT_TRY(sc->build_ws.alloc(wwords, "build_ws"));
   MIRT_HIP(hipEventRecord(sc->ev0, stream));
   // scene bounds
   const int nblk = (n + BLOCK - 1) / BLOCK;

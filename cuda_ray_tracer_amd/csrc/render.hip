@@ -561,13 +561,14 @@ int ensure_rng_tables(RngCache* rc, int sample_tables, long long frame_pixels, h
   if (rc->key != key && !(allow_larger && spp >= 1 && rc->key >= key)) {
     if (spp >= 1) build_sample_tables(spp, rc->host);
     else build_pixel_tables(frame_pixels, 1234, rc->host);
-    MIRT_HIP(hipDeviceSynchronize());   // another stream may still be reading the old tables
+    MIRT_HIP(hipDeviceSynchronize());   // (not grow(): another stream may still be reading the old tables)
     rng_cache_free(rc);
     const RngTables& t = rc->host;
-    MIRT_HIP(hipMalloc(&rc->A, t.A.size() * 4)); MIRT_HIP(hipMemcpy(rc->A, t.A.data(), t.A.size() * 4, hipMemcpyHostToDevice));
-    MIRT_HIP(hipMalloc(&rc->B, t.B.size() * 4)); MIRT_HIP(hipMemcpy(rc->B, t.B.data(), t.B.size() * 4, hipMemcpyHostToDevice));
-    MIRT_HIP(hipMalloc(&rc->K, t.K.size() * 4)); MIRT_HIP(hipMemcpy(rc->K, t.K.data(), t.K.size() * 4, hipMemcpyHostToDevice));
-    if (!t.R2.empty()) { MIRT_HIP(hipMalloc(&rc->R2, t.R2.size() * 4)); MIRT_HIP(hipMemcpy(rc->R2, t.R2.data(), t.R2.size() * 4, hipMemcpyHostToDevice)); }
+    MIRT_TRY(rc->A.alloc(t.A.size() / 4, "rc->A")); MIRT_HIP(hipMemcpy(rc->A, t.A.data(), t.A.size() * 4, hipMemcpyHostToDevice));      // (A: whole uint4)
+    MIRT_TRY(rc->B.alloc(t.B.size(), "rc->B")); MIRT_HIP(hipMemcpy(rc->B, t.B.data(), t.B.size() * 4, hipMemcpyHostToDevice));
+    MIRT_TRY(rc->K.alloc(t.K.size(), "rc->K")); MIRT_HIP(hipMemcpy(rc->K, t.K.data(), t.K.size() * 4, hipMemcpyHostToDevice));
+    MIRT_TRY(rc->R2.alloc(t.R2.size(), "rc->R2"));
+    if (!t.R2.empty()) MIRT_HIP(hipMemcpy(rc->R2, t.R2.data(), t.R2.size() * 4, hipMemcpyHostToDevice));
     rc->key = key;
   }
   const RngTables& t = rc->host;
@@ -576,10 +577,10 @@ int ensure_rng_tables(RngCache* rc, int sample_tables, long long frame_pixels, h
   return MIRT_OK;
 }
 
+// (the tables go back with their owner; a cache without a key is made again by the next call)
 void rng_cache_free(RngCache* rc)
 {
-  hipFree(rc->A); hipFree(rc->B); hipFree(rc->K); hipFree(rc->R2);
-  rc->A = nullptr; rc->B = nullptr; rc->K = nullptr; rc->R2 = nullptr; rc->key = -1;
+  rc->key = -1;
 }
 
 // One call of mirt_render / mirt_render_accumulate.  The part's pixels are rendered in slabs of at most 2^slab_log2 samples,
@@ -691,20 +692,18 @@ static int ensure_workspace(const RenderCall& c, RenderCtx& cx, const CallPlan& 
   const size_t samples = (size_t)pl.slab_samples_max;
   const size_t spill_need = (size_t)STACK_TOTAL_WIDE * gthreads;      // (the wide walk pushes up to three entries per two levels)
   const size_t pending_need = (size_t)pl.pending_slots * PENDING_WORDS * gthreads;
-  int rc = grow(cx.samples, cx.samples_cap, samples, sizeof(float4) * samples, stream);
-  if (rc == MIRT_OK) rc = grow(cx.stack_spill, cx.spill_cap, spill_need, sizeof(uint32_t) * spill_need, stream);
-  if (rc == MIRT_OK && c.sparse()) {
-    const size_t listed = (size_t)c.ax->num_listed, table = (size_t)pl.launch_samples_max, blocks_need = sparse_blocks_words(c.ax->num_listed);
-    rc = grow(cx.sp_list, cx.sp_list_cap, listed, 4 * listed, stream);
-    if (rc == MIRT_OK) rc = grow(cx.sp_table, cx.sp_table_cap, table, 4 * table, stream);
-    if (rc == MIRT_OK) rc = grow(cx.sp_blocks, cx.sp_blocks_cap, blocks_need, 4 * blocks_need, stream);
+  MIRT_TRY(cx.samples.grow(samples, stream, "samples"));
+  MIRT_TRY(cx.stack_spill.grow(spill_need, stream, "stack_spill"));
+  if (c.sparse()) {
+    MIRT_TRY(cx.sp_list.grow((size_t)c.ax->num_listed, stream, "sp_list"));
+    MIRT_TRY(cx.sp_table.grow((size_t)pl.launch_samples_max, stream, "sp_table"));
+    MIRT_TRY(cx.sp_blocks.grow(sparse_blocks_words(c.ax->num_listed), stream, "sp_blocks"));
   }
-  if (rc == MIRT_OK) rc = grow(cx.pending, cx.pending_cap, pending_need, sizeof(float) * pending_need, stream);
-  if (rc != MIRT_OK) return rc;
-  if (c.sc->opt.wavefront == 0 && !cx.args_dev) MIRT_HIP(hipMalloc(&cx.args_dev, sizeof(RenderArgs) * MAX_SLAB_ARGS));
+  MIRT_TRY(cx.pending.grow(pending_need, stream, "pending"));
+  if (c.sc->opt.wavefront == 0 && !cx.args_dev) MIRT_TRY(cx.args_dev.alloc(MAX_SLAB_ARGS, "args_dev"));
   // one event pair per trace launch: a call of several slabs reports the SUM of its launches, not a bracket that would take in
   // the resolve kernels between them
-  while ((int)cx.slab_ev.size() < 2 * pl.nslabs) { hipEvent_t e = nullptr; MIRT_HIP(hipEventCreate(&e)); cx.slab_ev.push_back(e); }
+  while ((int)cx.slab_ev.size() < 2 * pl.nslabs) { Event e; MIRT_TRY(e.create()); cx.slab_ev.push_back(std::move(e)); }
   return MIRT_OK;
 }
 
@@ -760,13 +759,14 @@ static int fill_args(const RenderCall& c, RenderCtx& cx, const CallPlan& pl, int
 // Returns the order in *order, or null: this frame measures one (chunk_order_finish).
 static int chunk_order_find(MirtScene* sc, RenderCtx& cx, size_t nchunks, long long okey, const uint32_t** order)
 {
-  if (cx.chunk_cap < nchunks) {
+  // (the four are freed together before the first is made, and the last one made stands for all: if any fails, it is empty)
+  if (cx.order_out[RenderCtx::ORDER_BUFS - 1].cap() < nchunks) {
     MIRT_HIP(hipDeviceSynchronize());   // (not grow(): a frame on another stream may still be reading one of these orders)
-    hipFree(cx.chunk_cost); cx.chunk_cost = nullptr; cx.chunk_cap = 0; cx.order_key = -1;
-    for (uint32_t*& o : cx.order_out) { hipFree(o); o = nullptr; }
-    MIRT_HIP(hipMalloc(&cx.chunk_cost, 4 * nchunks));
-    for (uint32_t*& o : cx.order_out) MIRT_HIP(hipMalloc(&o, 4 * nchunks));
-    cx.chunk_cap = nchunks;
+    cx.order_key = -1;
+    cx.chunk_cost.reset();
+    for (DevBuf<uint32_t>& o : cx.order_out) o.reset();
+    MIRT_TRY(cx.chunk_cost.alloc(nchunks, "chunk_cost"));
+    for (DevBuf<uint32_t>& o : cx.order_out) MIRT_TRY(o.alloc(nchunks, "order_out"));
   }
   unsigned long long best = 0;
   *order = nullptr;
@@ -811,19 +811,16 @@ static int sample_table_find(MirtScene* sc, const CallPlan& pl, long long okey, 
   if (sc->so_key == okey && sc->so_total == pl.total_samples) { *ordered = true; return MIRT_OK; }
   // (no frame in flight reads the old table once every context's frame has finished: wait for them before rewriting it)
   for (int i = 0; i < MIRT_MAX_FRAMES; ++i) if (sc->ctx[i].used) MIRT_HIP(hipEventSynchronize(sc->ctx[i].ev3));
-  if (sc->so_cap < total || sc->so_slab_cap < slab) {
-    hipFree(sc->so_order); hipFree(sc->so_keys); hipFree(sc->so_keys2); hipFree(sc->so_ws);
-    sc->so_order = sc->so_keys = sc->so_keys2 = sc->so_ws = nullptr; sc->so_cap = 0; sc->so_slab_cap = 0; sc->so_key = -1;
+  if (sc->so_order.cap() < total || sc->so_keys.cap() < slab) {
+    sc->so_order.reset(); sc->so_keys.reset(); sc->so_keys2.reset(); sc->so_ws.reset(); sc->so_key = -1;
     // (the table is an optimisation: without the memory for it the call is rendered in frame order)
-    const bool got = hipMalloc(&sc->so_order, 4 * total) == hipSuccess && hipMalloc(&sc->so_keys, 4 * slab) == hipSuccess &&
-                     hipMalloc(&sc->so_keys2, 4 * slab) == hipSuccess && hipMalloc(&sc->so_ws, 4 * sort_low_byte_ws_words(pl.slab_samples_max)) == hipSuccess;
+    const bool got = sc->so_order.alloc_raw(total) == hipSuccess && sc->so_keys.alloc_raw(slab) == hipSuccess &&
+                     sc->so_keys2.alloc_raw(slab) == hipSuccess && sc->so_ws.alloc_raw(sort_low_byte_ws_words(pl.slab_samples_max)) == hipSuccess;
     if (!got) {
       (void)hipGetLastError();
-      hipFree(sc->so_order); hipFree(sc->so_keys); hipFree(sc->so_keys2); hipFree(sc->so_ws);
-      sc->so_order = sc->so_keys = sc->so_keys2 = sc->so_ws = nullptr;
+      sc->so_order.reset(); sc->so_keys.reset(); sc->so_keys2.reset(); sc->so_ws.reset();
       return MIRT_OK;
     }
-    sc->so_cap = total; sc->so_slab_cap = slab;
   }
   *measure = true;
   sc->so_key = -1;
@@ -1058,13 +1055,12 @@ int part_pixel(const MirtRenderParams* p, int64_t local, int32_t* x, int32_t* y)
 int probe_math(int device, int which, int n, const float* in, float* out)
 {
   MIRT_HIP(hipSetDevice(device));
-  float *di = nullptr, *dout = nullptr;
-  MIRT_HIP(hipMalloc(&di, 4 * (size_t)n)); MIRT_HIP(hipMalloc(&dout, 4 * (size_t)n));
+  DevBuf<float> di, dout;
+  MIRT_TRY(di.alloc((size_t)n, "di")); MIRT_TRY(dout.alloc((size_t)n, "dout"));
   MIRT_HIP(hipMemcpy(di, in, 4 * (size_t)n, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(probe_math_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, which, n, di, dout);
   MIRT_HIP(hipGetLastError());
   MIRT_HIP(hipMemcpy(out, dout, 4 * (size_t)n, hipMemcpyDeviceToHost));
-  hipFree(di); hipFree(dout);
   return MIRT_OK;
 }
 
@@ -1075,13 +1071,11 @@ int probe_xorwow(int device, int spp, int nstreams, int draws, uint32_t* out)
   RngTablesDev t;
   int rc = ensure_rng_tables(&cache, spp > 1 ? spp : 0, nstreams, nullptr, &t, false);
   if (rc != MIRT_OK) return rc;
-  uint32_t* d = nullptr;
-  MIRT_HIP(hipMalloc(&d, 4 * (size_t)nstreams * draws));
+  DevBuf<uint32_t> d;
+  MIRT_TRY(d.alloc((size_t)nstreams * draws, "draws"));
   hipLaunchKernelGGL(probe_xorwow_kernel, dim3((nstreams + 255) / 256), dim3(256), 0, 0, t, spp, nstreams, draws, d);
   MIRT_HIP(hipGetLastError());
   MIRT_HIP(hipMemcpy(out, d, 4 * (size_t)nstreams * draws, hipMemcpyDeviceToHost));
-  hipFree(d);
-  rng_cache_free(&cache);
   return MIRT_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/mirt.h"
+#include "dev_mem.h"
 #include "device_common.h"
 #include "render_plan.h"
 #include "xorwow_tables.h"
@@ -142,7 +143,7 @@ struct ResolveArgs {
 struct RngCache {
   RngTables host;
   long long key = -1;
-  uint4* A = nullptr; uint32_t* B = nullptr; uint32_t* K = nullptr; uint32_t* R2 = nullptr;
+  DevBuf<uint4> A; DevBuf<uint32_t> B, K, R2;
 };
 
 // (Options, the mode switches and tuning values of a scene: render_plan.h)
@@ -150,41 +151,38 @@ struct RngCache {
 constexpr int MIRT_MAX_FRAMES = 4;
 // everything one frame in flight owns
 struct RenderCtx {
-  float4* samples = nullptr; size_t samples_cap = 0;
-  uint32_t* stack_spill = nullptr; size_t spill_cap = 0;
-  float* pending = nullptr; size_t pending_cap = 0;
-  unsigned long long* counters = nullptr;  // device: [0..7] MirtStats counters, [8] work counter, [9] overflow events, [10] scratch (mirt_get_stats), [11] rays traversed, [12] waves past the end of the work
+  DevBuf<float4> samples;
+  DevBuf<uint32_t> stack_spill;
+  DevBuf<float> pending;
+  DevBuf<unsigned long long> counters;     // device: [0..7] MirtStats counters, [8] work counter, [9] overflow events, [10] scratch (mirt_get_stats), [11] rays traversed, [12] waves past the end of the work
   hipStream_t stream = nullptr;            // the stream this context's latest frame was issued on
-  RenderArgs* args_dev = nullptr;          // this frame's RenderArgs in device memory (a ring of slots, one per slab in flight)
+  DevBuf<RenderArgs> args_dev;             // this frame's RenderArgs in device memory (a ring of slots, one per slab in flight)
   RenderArgs args_host[4];                 // what each slot holds
   bool args_valid[4] = {false, false, false, false};
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;   // render start / first trace start / last trace end / render end
-  std::vector<hipEvent_t> slab_ev;         // start / end of every trace launch of the last call beyond the first (ev1 / ev2 serve a one-slab call)
+  Event ev0, ev1, ev2, ev3;                // render start / first trace start / last trace end / render end
+  std::vector<Event> slab_ev;              // start / end of every trace launch of the last call beyond the first (ev1 / ev2 serve a one-slab call)
   int launches = 0;                        // trace launches of the last call
   int node_bytes = 64;                     // record size of the walk the last call used
   bool used = false, counted = false, timed = true;
   // longest-first scheduling: this frame's per-chunk cost, and the hand-out orders computed from it (two buffers used in
   // turn, so that a frame still reading an order never sees it rewritten)
-  uint32_t* chunk_cost = nullptr;
+  DevBuf<uint32_t> chunk_cost;
   // chunk orders this context produced, used round-robin.  Three of them: the one written at use u is next written at use
   // u + 3, i.e. 12 frames later, and by then the host has waited (on context reuse) for every frame that could read it --
   // so no frame ever needs a device-side wait on another frame's stream.
   static constexpr unsigned ORDER_BUFS = 3;
-  uint32_t* order_out[ORDER_BUFS] = {nullptr, nullptr, nullptr};
-  size_t chunk_cap = 0;
+  DevBuf<uint32_t> order_out[ORDER_BUFS];
   unsigned uses = 0;
   unsigned long long frame_id = 0;         // sequence number of the frame that last used this context
   long long order_key = -1;                // frame size (and chunk size) the order in order_out[(order_writes - 1) % ORDER_BUFS] was measured on
   unsigned order_writes = 0;               // orders this context has produced
   unsigned long long order_frame = 0;      // frame_id of the frame that measured it
-  hipEvent_t order_ev = nullptr;           // ... and the end of its sort
+  Event order_ev;                          // ... and the end of its sort
   float wf_trace_ms = -1.0f;               // >= 0: the wavefront path ran; summed trace-kernel time
   // mirt_render_accumulate_pixels with a pixel list (adaptive.hip): the listed pixels of the current slab in list order, the
   // position -> launch-sample table made from them (RenderArgs::sample_order of that launch), and the per-block counts of the
   // compaction, whose last word is the number of pixels kept
-  uint32_t* sp_list = nullptr; size_t sp_list_cap = 0;
-  uint32_t* sp_table = nullptr; size_t sp_table_cap = 0;
-  uint32_t* sp_blocks = nullptr; size_t sp_blocks_cap = 0;
+  DevBuf<uint32_t> sp_list, sp_table, sp_blocks;
 };
 
 // What mirt_render_accumulate_pixels adds to mirt_render_accumulate (which renders with an empty one): the pixels to render
@@ -205,35 +203,35 @@ struct MirtScene {
   mirt::Options opt;
   int grid_blocks = 0, wf_trace_blocks = 0;   // persistent-grid sizes for this scene's device (filled on first use)
   // uploaded geometry, file order (inputs of the build)
-  float4* spheres = nullptr;            // (cx, cy, cz, r)
-  float4* tris = nullptr;               // 3 x float4 per triangle: p0.xyz nor.x | nor.yz e1.xy | e1.z e2.xyz
-  float4* mats = nullptr;
-  MirtPrimRef* refs_in = nullptr;       // file order
-  float4* tri_verts = nullptr;          // 3 x float4 per triangle (p0,p1,p2) -- build only
-  mirt::PlaneDev* planes = nullptr;
-  mirt::LightDev* suns = nullptr;
-  mirt::LightDev* bulbs = nullptr;
+  mirt::DevBuf<float4> spheres;         // (cx, cy, cz, r)
+  mirt::DevBuf<float4> tris;            // 3 x float4 per triangle: p0.xyz nor.x | nor.yz e1.xy | e1.z e2.xyz
+  mirt::DevBuf<float4> mats;
+  mirt::DevBuf<MirtPrimRef> refs_in;    // file order
+  mirt::DevBuf<float4> tri_verts;       // 3 x float4 per triangle (p0,p1,p2) -- build only
+  mirt::DevBuf<mirt::PlaneDev> planes;
+  mirt::DevBuf<mirt::LightDev> suns;
+  mirt::DevBuf<mirt::LightDev> bulbs;
   // build products
-  uint32_t* codes = nullptr;            // sorted Morton codes [N]
-  uint32_t* order = nullptr;            // sorted position -> file-order index [N]
-  uint32_t* child_l = nullptr;          // reference numbering [N-1]
-  uint32_t* child_r = nullptr;
-  int* parent = nullptr;                // [2N-1]
-  float* boxes = nullptr;               // [2N-1][6] xmin,xmax,ymin,ymax,zmin,zmax
-  float4* nodes = nullptr;              // packed [N-1][4]; start of the record heap [nodes | primitive records, sorted order | pad]
-  unsigned char* heap = nullptr;
+  mirt::DevBuf<uint32_t> codes;         // sorted Morton codes [N]
+  mirt::DevBuf<uint32_t> order;         // sorted position -> file-order index [N]
+  mirt::DevBuf<uint32_t> child_l;       // reference numbering [N-1]
+  mirt::DevBuf<uint32_t> child_r;
+  mirt::DevBuf<int> parent;             // [2N-1]
+  mirt::DevBuf<float> boxes;            // [2N-1][6] xmin,xmax,ymin,ymax,zmin,zmax
+  float4* nodes = nullptr;              // packed [N-1][4]; start of the record heap [nodes | primitive records, sorted order | pad] (not owning: points into heap)
+  mirt::DevBuf<unsigned char> heap;
   uint32_t prim_base = 0;               // byte offset of the primitive region in the heap
-  uint32_t* unit_prim = nullptr;        // [Ns + 3 Nt]: per 16-byte unit of the primitive region, type << 31 | index (first unit of a record)
-  uint32_t* tris_before = nullptr;      // [N + 1]: triangles among sorted leaves [0, j)
-  uint2* range = nullptr;               // [N - 1]: sorted-leaf range (first, last) of every internal node
+  mirt::DevBuf<uint32_t> unit_prim;     // [Ns + 3 Nt]: per 16-byte unit of the primitive region, type << 31 | index (first unit of a record)
+  mirt::DevBuf<uint32_t> tris_before;   // [N + 1]: triangles among sorted leaves [0, j)
+  mirt::DevBuf<uint2> range;            // [N - 1]: sorted-leaf range (first, last) of every internal node
   uint32_t qnode_base = 0;              // byte offset of the quantised node records in the heap (0: none built)
   uint32_t wnode_base = 0;              // byte offset of the wide quantised records (scenes with triangles; 0: none built)
   uint32_t root_ref_w = mirt::REF_NONE; // root reference into the wide records
   uint32_t root_ref_q = mirt::REF_NONE; // root reference into the quantised records
-  float* qparams = nullptr;             // [9] device: grid origin, grid step, 2^60 / grid step
-  float4* tri_boxes = nullptr;          // [2 Nt]: exact leaf box of every triangle (scene order), for the quantised walk's triangle check
-  uint32_t* build_ws = nullptr; size_t build_ws_words = 0;   // LBVH build workspace (sort buffers, histograms, arrival counters)
-  uint32_t* bounds_keys = nullptr;      // [6] ordered-uint min xyz, max xyz
+  mirt::DevBuf<float> qparams;          // [9] device: grid origin, grid step, 2^60 / grid step
+  mirt::DevBuf<float4> tri_boxes;       // [2 Nt]: exact leaf box of every triangle (scene order), for the quantised walk's triangle check
+  mirt::DevBuf<uint32_t> build_ws;      // LBVH build workspace (sort buffers, histograms, arrival counters)
+  mirt::DevBuf<uint32_t> bounds_keys;   // [6] ordered-uint min xyz, max xyz
   uint32_t root_ref = mirt::REF_NONE;
   bool built = false;
   float build_ms = 0.0f;
@@ -248,19 +246,19 @@ struct MirtScene {
   unsigned long long overflow_events = 0;  // capacity overflows seen since the last mirt_get_stats
   double trace_ms_sum = 0.0; int trace_frames = 0;   // trace-kernel time of the frames finished since the last mirt_get_stats
   // wavefront path workspace (wavefront.hip)
-  uint32_t* wf_state = nullptr; size_t wf_state_cap = 0;
-  float4* wf_rays = nullptr; size_t wf_rays_cap = 0;
-  unsigned long long* wf_ctr = nullptr;
-  unsigned long long* wf_ctr_host = nullptr;
-  std::vector<hipEvent_t> wf_events;
+  mirt::DevBuf<uint32_t> wf_state;
+  mirt::DevBuf<float4> wf_rays;
+  mirt::DevBuf<unsigned long long> wf_ctr;
+  mirt::PinnedBuf<unsigned long long> wf_ctr_host;
+  std::vector<mirt::Event> wf_events;
   int wf_rounds = 0;
   // sched = 2: the frame's samples in order of decreasing cost class, measured once per frame size (shared by the contexts)
-  uint32_t* so_order = nullptr; uint32_t* so_keys = nullptr; uint32_t* so_keys2 = nullptr; uint32_t* so_ws = nullptr;
-  size_t so_cap = 0, so_slab_cap = 0; long long so_key = -1, so_pending_key = -1, so_total = -1; hipEvent_t so_ev = nullptr; bool so_busy = false;
+  mirt::DevBuf<uint32_t> so_order, so_keys, so_keys2, so_ws;      // [call's samples], [slab's samples] x 2, the sort's workspace
+  long long so_key = -1, so_pending_key = -1, so_total = -1; mirt::Event so_ev; bool so_busy = false;
   // rng tables cache
   mirt::RngCache rng;
   // LBVH build timing
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  mirt::Event ev0, ev1;
   bool colors_finite = true;               // every material colour and light colour is finite (0 * colour == 0)
   bool any_trans = false;                  // some material has transparency != 0
   bool any_rough = false;
@@ -272,18 +270,18 @@ struct MirtScene {
   unsigned prim_flags = 0, host_flags = 0;
   std::vector<MirtLight> suns_host, bulbs_host;      // what mirt_scene_create / mirt_scene_set_lights were given
   std::vector<MirtPlane> planes_host;
-  unsigned char* mat_flags = nullptr;      // device: material_flags of every primitive (spheres, then triangles), padded with zeros to whole words; made by the first material update
-  unsigned* flags_or = nullptr;            // device: the OR over mat_flags, written by the reduction that ends a material update
-  unsigned* flags_or_host = nullptr;       // pinned: its copy, valid once facts_ev has passed
-  hipEvent_t facts_ev = nullptr;           // end of the last material update's reduction and copy
+  mirt::DevBuf<unsigned char> mat_flags;   // device: material_flags of every primitive (spheres, then triangles), padded with zeros to whole words; made by the first material update
+  mirt::DevBuf<unsigned> flags_or;         // device: the OR over mat_flags, written by the reduction that ends a material update
+  mirt::PinnedBuf<unsigned> flags_or_host; // pinned: its copy, valid once facts_ev has passed
+  mirt::Event facts_ev;                    // end of the last material update's reduction and copy
   bool facts_pending = false;              // a material update was issued since prim_flags was read
   hipStream_t facts_stream = nullptr;      // ... on this stream
-  unsigned char* stage = nullptr; size_t stage_cap = 0;   // pinned staging of the light and plane records on their way to the device
-  hipEvent_t stage_ev = nullptr; bool stage_used = false; // ... and the end of the last copy out of it
+  mirt::PinnedBuf<unsigned char> stage;    // pinned staging of the light and plane records on their way to the device
+  mirt::Event stage_ev; bool stage_used = false;          // ... and the end of the last copy out of it
 };
 
 namespace mirt {
-int hip_fail(hipError_t e, const char* what, const char* file, int line);
+// (hip_fail, lbvh_build.hip: dev_mem.h declares it)
 // lbvh_build.hip
 int build_lbvh(MirtScene* sc, hipStream_t stream);
 size_t sort_low_byte_ws_words(long long n);
@@ -330,7 +328,6 @@ PlaneDev plane_dev(const MirtPlane& p);
 void pack_mat(const float m[11], float4* out);
 void refresh_host_facts(MirtScene* sc);
 int settle_facts(MirtScene* sc);
-void free_shading_state(MirtScene* sc);
 int set_lights(MirtScene* sc, const MirtLight* suns, const MirtLight* bulbs, hipStream_t stream);
 int set_planes(MirtScene* sc, const MirtPlane* planes, int first, int count, hipStream_t stream);
 int update_materials(MirtScene* sc, const char* who, const void* d_mats, int base, int total, int first, int count, hipStream_t stream);
@@ -348,22 +345,10 @@ int temporal_accumulate(const MirtRenderParams* p, const MirtCamera* prev_camera
 int wavefront_trace(MirtScene* sc, RenderCtx& cx, RenderArgs& a, bool count, hipStream_t stream, float* trace_ms);
 }
 #define MIRT_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return mirt::hip_fail(e_, #call, __FILE__, __LINE__); } while (0)
+// the same for a call that has reported its own failure and returns a MIRT_* status
+#define MIRT_TRY(call) do { const int rc_ = (call); if (rc_ != MIRT_OK) return rc_; } while (0)
 
 namespace mirt {
-
-// A device buffer that only grows, used by the work on one stream.  When its capacity `cap` (in the caller's unit) is below
-// `need`: wait for that stream -- an earlier call on it may still be using the smaller buffer -- free it, allocate `bytes`.
-// (Buffers that frames on OTHER streams read -- the chunk orders, the rng tables -- wait for the device instead, at their sites.)
-template <class T>
-int grow(T*& ptr, size_t& cap, size_t need, size_t bytes, hipStream_t stream)
-{
-  if (cap >= need) return MIRT_OK;
-  MIRT_HIP(hipStreamSynchronize(stream));
-  hipFree(ptr); ptr = nullptr; cap = 0;
-  MIRT_HIP(hipMalloc(&ptr, bytes));
-  cap = need;
-  return MIRT_OK;
-}
 
 // Blocks of a persistent grid that fills the device: compute units x resident blocks of `kernel` per unit (per_cu_fallback
 // if the occupancy query fails).  An error only if the device's properties cannot be read.

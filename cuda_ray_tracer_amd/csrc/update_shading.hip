@@ -94,12 +94,8 @@ void recombine(MirtScene* sc)
 int take_stage(MirtScene* sc, size_t bytes)
 {
   if (sc->stage_used) { MIRT_HIP(hipEventSynchronize(sc->stage_ev)); sc->stage_used = false; }
-  if (!sc->stage_ev) MIRT_HIP(hipEventCreateWithFlags(&sc->stage_ev, hipEventDisableTiming));
-  if (sc->stage_cap < bytes) {
-    if (sc->stage) { MIRT_HIP(hipHostFree(sc->stage)); sc->stage = nullptr; sc->stage_cap = 0; }
-    MIRT_HIP(hipHostMalloc((void**)&sc->stage, bytes, hipHostMallocDefault));
-    sc->stage_cap = bytes;
-  }
+  MIRT_TRY(sc->stage_ev.create(hipEventDisableTiming));
+  if (sc->stage.cap() < bytes) MIRT_TRY(sc->stage.alloc(bytes, "stage"));
   return MIRT_OK;
 }
 
@@ -108,18 +104,15 @@ int ensure_flags(MirtScene* sc, hipStream_t stream)
 {
   if (sc->mat_flags) return MIRT_OK;
   const size_t bytes = ((size_t)sc->N + 3) / 4 * 4;
-  if (!sc->flags_or) MIRT_HIP(hipMalloc(&sc->flags_or, sizeof(unsigned)));
-  if (!sc->flags_or_host) MIRT_HIP(hipHostMalloc((void**)&sc->flags_or_host, sizeof(unsigned), hipHostMallocDefault));
-  if (!sc->facts_ev) MIRT_HIP(hipEventCreateWithFlags(&sc->facts_ev, hipEventDisableTiming));
-  unsigned char* flags = nullptr;
-  MIRT_HIP(hipMalloc(&flags, bytes));
-  hipError_t e = hipMemsetAsync(flags, 0, bytes, stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(material_flags_kernel, dim3(grid_of(sc->N)), dim3(SBLOCK), 0, stream, sc->mats, flags, sc->N);
-    e = hipGetLastError();
-  }
-  if (e != hipSuccess) { hipFree(flags); return hip_fail(e, "material flags", __FILE__, __LINE__); }
-  sc->mat_flags = flags;
+  if (!sc->flags_or) MIRT_TRY(sc->flags_or.alloc(1, "flags_or"));
+  if (!sc->flags_or_host) MIRT_TRY(sc->flags_or_host.alloc(1, "flags_or_host"));
+  MIRT_TRY(sc->facts_ev.create(hipEventDisableTiming));
+  DevBuf<unsigned char> flags;      // (the scene's only once they are filled: mat_flags set means made)
+  MIRT_TRY(flags.alloc(bytes, "mat_flags"));
+  MIRT_HIP(hipMemsetAsync(flags, 0, bytes, stream));
+  hipLaunchKernelGGL(material_flags_kernel, dim3(grid_of(sc->N)), dim3(SBLOCK), 0, stream, sc->mats, flags, sc->N);
+  MIRT_HIP(hipGetLastError());
+  sc->mat_flags = std::move(flags);
   return MIRT_OK;
 }
 
@@ -182,15 +175,6 @@ int settle_facts(MirtScene* sc)
   return MIRT_OK;
 }
 
-void free_shading_state(MirtScene* sc)
-{
-  hipFree(sc->mat_flags); hipFree(sc->flags_or);
-  if (sc->flags_or_host) hipHostFree(sc->flags_or_host);
-  if (sc->stage) hipHostFree(sc->stage);
-  if (sc->facts_ev) hipEventDestroy(sc->facts_ev);
-  if (sc->stage_ev) hipEventDestroy(sc->stage_ev);
-}
-
 int set_lights(MirtScene* sc, const MirtLight* suns, const MirtLight* bulbs, hipStream_t stream)
 {
   const size_t ns = suns ? (size_t)sc->d.num_suns : 0, nb = bulbs ? (size_t)sc->d.num_bulbs : 0;
@@ -198,7 +182,7 @@ int set_lights(MirtScene* sc, const MirtLight* suns, const MirtLight* bulbs, hip
   int rc = wait_for_frames(sc);
   if (rc == MIRT_OK) rc = take_stage(sc, sizeof(LightDev) * (ns + nb));
   if (rc != MIRT_OK) return rc;
-  LightDev* st = reinterpret_cast<LightDev*>(sc->stage);
+  LightDev* st = reinterpret_cast<LightDev*>(sc->stage.get());
   for (size_t i = 0; i < ns; ++i) st[i] = sun_dev(suns[i]);
   for (size_t i = 0; i < nb; ++i) st[ns + i] = bulb_dev(bulbs[i]);
   sc->stage_used = true;      // (from here on the buffer may be in use, whatever fails below)
@@ -219,7 +203,7 @@ int set_planes(MirtScene* sc, const MirtPlane* planes, int first, int count, hip
   rc = wait_for_frames(sc);
   if (rc == MIRT_OK) rc = take_stage(sc, sizeof(PlaneDev) * (size_t)count);
   if (rc != MIRT_OK) return rc;
-  PlaneDev* st = reinterpret_cast<PlaneDev*>(sc->stage);
+  PlaneDev* st = reinterpret_cast<PlaneDev*>(sc->stage.get());
   for (int i = 0; i < count; ++i) st[i] = plane_dev(planes[i]);
   sc->stage_used = true;
   MIRT_HIP(hipMemcpyAsync(sc->planes + first, st, sizeof(PlaneDev) * (size_t)count, hipMemcpyHostToDevice, stream));
@@ -248,7 +232,7 @@ int update_materials(MirtScene* sc, const char* who, const void* d_mats, int bas
   const long long words = ((long long)sc->N + 3) / 4;
   const unsigned blocks = grid_of(words) < (unsigned)REDUCE_BLOCKS_MAX ? grid_of(words) : (unsigned)REDUCE_BLOCKS_MAX;
   MIRT_HIP(hipMemsetAsync(sc->flags_or, 0, sizeof(unsigned), stream));
-  hipLaunchKernelGGL(reduce_flags_kernel, dim3(blocks), dim3(SBLOCK), 0, stream, reinterpret_cast<const uint32_t*>(sc->mat_flags), words, sc->flags_or);
+  hipLaunchKernelGGL(reduce_flags_kernel, dim3(blocks), dim3(SBLOCK), 0, stream, reinterpret_cast<const uint32_t*>(sc->mat_flags.get()), words, sc->flags_or);
   MIRT_HIP(hipGetLastError());
   MIRT_HIP(hipMemcpyAsync(sc->flags_or_host, sc->flags_or, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
   MIRT_HIP(hipEventRecord(sc->facts_ev, stream));

@@ -471,29 +471,22 @@ int wavefront_trace(MirtScene* sc, RenderCtx& cx, RenderArgs& a, bool count, hip
   if (max_rays >= 0xffffffffull) { set_error("wavefront: ray queue too large"); return MIRT_ERR_ARG; }
 
   // workspace
-  const size_t state_bytes = sizeof(uint32_t) * (size_t)W_COUNT * pool;
-  const size_t rays_bytes = sizeof(float4) * 2 * max_rays;
-  int rc = grow(sc->wf_state, sc->wf_state_cap, state_bytes, state_bytes, stream);
-  if (rc == MIRT_OK) rc = grow(sc->wf_rays, sc->wf_rays_cap, rays_bytes, rays_bytes, stream);
-  if (rc != MIRT_OK) return rc;
-  if (!sc->wf_ctr) {
-    MIRT_HIP(hipMalloc(&sc->wf_ctr, 8 * sizeof(unsigned long long)));
-    MIRT_HIP(hipHostMalloc(&sc->wf_ctr_host, 8 * sizeof(unsigned long long)));
-  }
+  MIRT_TRY(sc->wf_state.grow((size_t)W_COUNT * pool, stream, "wf_state"));
+  MIRT_TRY(sc->wf_rays.grow(2 * max_rays, stream, "wf_rays"));
+  if (!sc->wf_ctr) MIRT_TRY(sc->wf_ctr.alloc(8, "wf_ctr"));
+  if (!sc->wf_ctr_host) MIRT_TRY(sc->wf_ctr_host.alloc(8, "wf_ctr_host"));
   // pending-children LIFO is indexed by slot here
   const bool need_pending = sc->any_trans || sc->d.gi != 0;
   const int pending_slots = need_pending ? 2 * (sc->d.bounces + (sc->d.gi > 0 ? sc->d.gi : 0) + 2) : 0;
   const size_t pending_need = (size_t)pending_slots * PENDING_WORDS * pool;
-  rc = grow(cx.pending, cx.pending_cap, pending_need, sizeof(float) * pending_need, stream);
-  if (rc != MIRT_OK) return rc;
+  MIRT_TRY(cx.pending.grow(pending_need, stream, "pending"));
   a.pending = cx.pending; a.pending_slots = pending_slots;
 
   if (!sc->wf_trace_blocks) MIRT_HIP(persistent_grid_blocks(sc->device, wf_trace_kernel<false>, WBLOCK, 4, &sc->wf_trace_blocks));
   const int trace_blocks = sc->wf_trace_blocks;
   const size_t gthreads = (size_t)trace_blocks * WBLOCK;
   const size_t spill_need = (size_t)STACK_TOTAL * gthreads;
-  rc = grow(cx.stack_spill, cx.spill_cap, spill_need, sizeof(uint32_t) * spill_need, stream);
-  if (rc != MIRT_OK) return rc;
+  MIRT_TRY(cx.stack_spill.grow(spill_need, stream, "stack_spill"));
   a.stack_spill = cx.stack_spill;
 
   WfArgs w;
@@ -503,10 +496,10 @@ int wavefront_trace(MirtScene* sc, RenderCtx& cx, RenderArgs& a, bool count, hip
   hipLaunchKernelGGL(wf_reset_kernel, dim3((pool + 255) / 256), dim3(256), 0, stream, sc->wf_state, pool);
 
   const int shade_blocks = pool / SBLOCK;
-  std::vector<hipEvent_t>& evs = sc->wf_events;
+  std::vector<Event>& evs = sc->wf_events;
   size_t ev_used = 0;
   auto next_event = [&](hipEvent_t* out) -> int {
-    if (ev_used == evs.size()) { hipEvent_t e; MIRT_HIP(hipEventCreate(&e)); evs.push_back(e); }
+    if (ev_used == evs.size()) { Event e; MIRT_TRY(e.create()); evs.push_back(std::move(e)); }
     *out = evs[ev_used++];
     return MIRT_OK;
   };
@@ -518,8 +511,8 @@ int wavefront_trace(MirtScene* sc, RenderCtx& cx, RenderArgs& a, bool count, hip
       if (count) hipLaunchKernelGGL(wf_shade_kernel<true>, dim3(shade_blocks), dim3(SBLOCK), 0, stream, w);
       else hipLaunchKernelGGL(wf_shade_kernel<false>, dim3(shade_blocks), dim3(SBLOCK), 0, stream, w);
       hipEvent_t e0, e1;
-      rc = next_event(&e0); if (rc) return rc;
-      rc = next_event(&e1); if (rc) return rc;
+      MIRT_TRY(next_event(&e0));
+      MIRT_TRY(next_event(&e1));
       MIRT_HIP(hipEventRecord(e0, stream));
       if (count) hipLaunchKernelGGL(wf_trace_kernel<true>, dim3(trace_blocks), dim3(WBLOCK), 0, stream, w);
       else hipLaunchKernelGGL(wf_trace_kernel<false>, dim3(trace_blocks), dim3(WBLOCK), 0, stream, w);

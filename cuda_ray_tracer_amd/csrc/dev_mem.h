@@ -1,5 +1,5 @@
-// What the library allocates through the HIP runtime, owned by type: device buffers, pinned host buffers, events.  Each is
-// freed by its destructor, so a scene, a context or a local gives back what it holds wherever it ends -- no list to extend.
+// What the library allocates through the HIP runtime, owned by type: device buffers, pinned host buffers, events, streams.  Each
+// is freed by its destructor, so a scene, a context or a local gives back what it holds wherever it ends -- no list to extend.
 // Non-copyable, movable.  Host only.
 // NO OBJECT OF THESE TYPES MAY HAVE STATIC STORAGE DURATION: its destructor would run after the HIP runtime has shut down and
 // must not call into it.  They live in scenes, contexts and locals ("Ownership").
@@ -127,6 +127,43 @@ private:
   hipEvent_t e_ = nullptr;
 };
 
+class Stream {
+public:
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  Stream(Stream&& o) noexcept : s_(o.s_) { o.s_ = nullptr; }
+  Stream& operator=(Stream&& o) noexcept
+  {
+    if (this != &o) { reset(); s_ = o.s_; o.s_ = nullptr; }
+    return *this;
+  }
+  ~Stream() { reset(); }
+
+  operator hipStream_t() const { return s_; }
+  void reset()
+  {
+    if (s_) (void)hipStreamDestroy(s_);
+    s_ = nullptr;
+  }
+  // creates the stream if there is none (a failure names the caller's file and line)
+  int create(unsigned flags, const char* file = __builtin_FILE(), int line = __builtin_LINE())
+  {
+    if (s_) return MIRT_OK;
+    const hipError_t e = hipStreamCreateWithFlags(&s_, flags);
+    if (e == hipSuccess) return MIRT_OK;
+    s_ = nullptr;
+    return hip_fail(e, "hipStreamCreateWithFlags", file, line);
+  }
+
+private:
+  hipStream_t s_ = nullptr;
+};
+
 } // namespace mirt
+
+#define MIRT_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return mirt::hip_fail(e_, #call, __FILE__, __LINE__); } while (0)
+// the same for a call that has reported its own failure and returns a MIRT_* status
+#define MIRT_TRY(call) do { const int rc_ = (call); if (rc_ != MIRT_OK) return rc_; } while (0)
 
 #endif

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/mirt.h"
+#include "dev_mem.h"
 #include "host_scene.h"
 
 namespace {
@@ -60,54 +61,69 @@ bool load_rccl(Rccl& r)
   return r.CommInitAll && r.CommDestroy && r.GroupStart && r.GroupEnd && r.Send && r.Recv && r.GetErrorString;
 }
 
-int hip_err(hipError_t e, const char* what)
-{
-  mirt::set_error(std::string("mirt_multi: HIP error in ") + what + ": " + hipGetErrorString(e));
-  return MIRT_ERR_HIP;
-}
-#define MM_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_err(e_, #call); } while (0)
+// The handles are grouped by the device they live on, in dev_mem.h's owning types; each group makes its device current in its
+// destructor's body, which runs before its members go.  What one frame in flight holds on one device:
+struct SlotDev {
+  int dev = 0;
+  mirt::Stream stream;                       // this slot's render stream
+  mirt::Event ev0, ev1;                      // part render start / end
+  mirt::Event sent;                          // its share of the gather has left (communication stream)
+  mirt::DevBuf<unsigned char> part;          // its compact part buffer
+  ~SlotDev() { hipSetDevice(dev); }
+};
+
+// ... and on device 0 alone
+struct SlotRoot {
+  int dev = 0;
+  std::vector<mirt::DevBuf<unsigned char>> gathered;      // where part r arrives (r >= 1)
+  mirt::DevBuf<unsigned char> frame;         // the row-major frame
+  mirt::Event gather_end;                    // (communication stream) frame re-interleaved
+  mirt::Event done;                          // host copy issued too
+  ~SlotRoot() { hipSetDevice(dev); }
+};
 
 // everything one frame in flight owns
 struct Slot {
-  std::vector<hipStream_t> stream;           // per device: this slot's render stream
-  std::vector<hipEvent_t> ev0, ev1;          // per device: part render start / end
-  std::vector<hipEvent_t> sent;              // per device: its share of the gather has left (communication stream)
-  hipEvent_t gather_end = nullptr;           // device 0 (communication stream): frame re-interleaved
-  hipEvent_t done = nullptr;                 // device 0: host copy issued too
-  std::vector<void*> part;                   // per device: its compact part buffer
-  std::vector<void*> gathered;               // device 0: where part r arrives (r >= 1)
-  void* frame = nullptr;                     // device 0: the row-major frame
-  size_t part_cap = 0, frame_cap = 0;
+  std::vector<SlotDev> on;                   // per device
+  SlotRoot at0;
   bool busy = false;
   unsigned long long ticket = 0;
   std::chrono::steady_clock::time_point t0;
 };
 
+// what the object holds on one device, whatever the frame
+struct PerDev {
+  int dev = 0;
+  MirtScene* scene = nullptr;                // opaque here: given back through mirt_scene_destroy (mirt_multi_destroy)
+  mirt::Stream comm_stream;                  // the gathers, in submission order
+  ~PerDev() { hipSetDevice(dev); }
+};
+
 } // namespace
 
+// All vectors of n elements are sized once, in mirt_multi_create before the build threads start; nothing resizes them later.
 struct MirtMulti {
   int n = 0;
   bool copy_gather = false;                  // peer-to-peer copies instead of RCCL (MIRT_MULTI_GATHER=copy)
   std::vector<int> dev;
-  std::vector<MirtScene*> scene;
-  std::vector<hipStream_t> comm_stream;      // per device: the gathers, in submission order
+  std::vector<PerDev> per;
   Slot slot[MIRT_MULTI_MAX_IN_FLIGHT];
   unsigned long long next_ticket = 1;
   int outstanding = 0;
   Rccl rccl;
-  std::vector<ncclComm_t> comm;
+  std::vector<ncclComm_t> comm;              // empty unless ncclCommInitAll made them; released through `rccl` (mirt_multi_destroy)
   float build_ms_max = 0.0f;
 };
 
 namespace {
 
-// wait for everything the slot has in flight (error paths, reuse, destroy)
+// wait for everything the slot has in flight (error paths, reuse, destroy; a stream never made is the device's null stream)
 void drain_slot(MirtMulti* mm, Slot& s)
 {
   for (int r = 0; r < mm->n; ++r) {
     hipSetDevice(mm->dev[r]);
-    if (r < (int)s.stream.size() && s.stream[r]) hipStreamSynchronize(s.stream[r]);
-    if (r < (int)mm->comm_stream.size() && mm->comm_stream[r]) hipStreamSynchronize(mm->comm_stream[r]);
+    hipStreamSynchronize(s.on[r].stream);
+    hipStreamSynchronize(mm->per[r].comm_stream);
   }
 }
 
@@ -118,10 +134,26 @@ int check_overflow(MirtMulti* mm)
   int rc = MIRT_OK;
   for (int r = 0; r < mm->n; ++r) {
     MirtStats st;
-    const int q = mirt_get_stats(mm->scene[r], &st);
+    const int q = mirt_get_stats(mm->per[r].scene, &st);
     if (q != MIRT_OK && rc == MIRT_OK) rc = q;      // (the message of the first failing device stays in mirt_last_error)
   }
   return rc;
+}
+
+// One device's share of mirt_multi_create, on that device's thread: its scene, streams and events, then its tree.
+int create_on_device(MirtMulti* mm, const MirtSceneDesc* desc, int r, float* build_ms)
+{
+  PerDev& d = mm->per[r];
+  MIRT_TRY(mirt_scene_create(desc, d.dev, &d.scene));
+  MIRT_HIP(hipSetDevice(d.dev));
+  MIRT_TRY(d.comm_stream.create(hipStreamNonBlocking));
+  for (Slot& s : mm->slot) {
+    SlotDev& q = s.on[r];
+    MIRT_TRY(q.stream.create(hipStreamNonBlocking));
+    MIRT_TRY(q.ev0.create()); MIRT_TRY(q.ev1.create()); MIRT_TRY(q.sent.create());
+    if (r == 0) { MIRT_TRY(s.at0.gather_end.create()); MIRT_TRY(s.at0.done.create()); }
+  }
+  return mirt_build_lbvh(d.scene, mm->slot[0].on[r].stream, build_ms);
 }
 
 } // namespace
@@ -134,26 +166,10 @@ void mirt_multi_destroy(MirtMulti* mm)
 {
   if (!mm) return;
   for (Slot& s : mm->slot) drain_slot(mm, s);
-  for (int r = 0; r < (int)mm->scene.size(); ++r) {
-    hipSetDevice(mm->dev[r]);
-    if (r < (int)mm->comm.size() && mm->comm[r]) mm->rccl.CommDestroy(mm->comm[r]);
-    if (mm->scene[r]) mirt_scene_destroy(mm->scene[r]);
-    hipSetDevice(mm->dev[r]);
-    for (Slot& s : mm->slot) {
-      if (r < (int)s.part.size()) hipFree(s.part[r]);
-      if (r < (int)s.gathered.size()) hipFree(s.gathered[r]);
-      if (r < (int)s.ev0.size() && s.ev0[r]) hipEventDestroy(s.ev0[r]);
-      if (r < (int)s.ev1.size() && s.ev1[r]) hipEventDestroy(s.ev1[r]);
-      if (r < (int)s.sent.size() && s.sent[r]) hipEventDestroy(s.sent[r]);
-      if (r < (int)s.stream.size() && s.stream[r]) hipStreamDestroy(s.stream[r]);
-    }
-    if (r < (int)mm->comm_stream.size() && mm->comm_stream[r]) hipStreamDestroy(mm->comm_stream[r]);
-  }
-  if (!mm->dev.empty()) {
-    hipSetDevice(mm->dev[0]);
-    for (Slot& s : mm->slot) { hipFree(s.frame); if (s.gather_end) hipEventDestroy(s.gather_end); if (s.done) hipEventDestroy(s.done); }
-  }
-  delete mm;
+  // the communicators go before the streams they were used on, through the run-time-loaded table
+  for (size_t r = 0; r < mm->comm.size(); ++r) { hipSetDevice(mm->dev[r]); mm->rccl.CommDestroy(mm->comm[r]); }
+  for (PerDev& d : mm->per) mirt_scene_destroy(d.scene);      // (a scene never made is null, which that call accepts; it waits for the device)
+  delete mm;                                                  // streams, events and buffers: the members' destructors
 }
 
 int mirt_multi_create(const MirtSceneDesc* desc, int ngpu, const int* devices, MirtMulti** out)
@@ -165,21 +181,21 @@ int mirt_multi_create(const MirtSceneDesc* desc, int ngpu, const int* devices, M
   const char* g = getenv("MIRT_MULTI_GATHER");
   const bool copy_gather = g && strcmp(g, "copy") == 0;
   if (ngpu > ndev && !copy_gather) { mirt::set_error("mirt_multi_create: more GPUs requested than present"); return MIRT_ERR_ARG; }
+  std::vector<int> dev;
+  for (int r = 0; r < ngpu; ++r) {
+    const int d = devices ? devices[r] : (copy_gather ? r % ndev : r);      // (rehearsal: more parts than GPUs time-share them)
+    if (d < 0 || d >= ndev) { mirt::set_error("mirt_multi_create: bad device index"); return MIRT_ERR_ARG; }
+    // (RCCL refuses a device listed twice; with peer copies several parts may time-share one GPU: a rehearsal, see above)
+    if (!copy_gather) for (int q = 0; q < r; ++q) if (dev[q] == d) { mirt::set_error("mirt_multi_create: a device is listed twice"); return MIRT_ERR_ARG; }
+    dev.push_back(d);
+  }
   MirtMulti* mm = new MirtMulti();
   mm->n = ngpu;
   mm->copy_gather = copy_gather;
-  for (int r = 0; r < ngpu; ++r) {
-    const int d = devices ? devices[r] : (copy_gather ? r % ndev : r);      // (rehearsal: more parts than GPUs time-share them)
-    if (d < 0 || d >= ndev) { mirt_multi_destroy(mm); mirt::set_error("mirt_multi_create: bad device index"); return MIRT_ERR_ARG; }
-    // (RCCL refuses a device listed twice; with peer copies several parts may time-share one GPU: a rehearsal, see above)
-    if (!copy_gather) for (int q = 0; q < r; ++q) if (mm->dev[q] == d) { mirt_multi_destroy(mm); mirt::set_error("mirt_multi_create: a device is listed twice"); return MIRT_ERR_ARG; }
-    mm->dev.push_back(d);
-  }
-  mm->scene.assign(ngpu, nullptr); mm->comm_stream.assign(ngpu, nullptr);
-  for (Slot& s : mm->slot) {
-    s.stream.assign(ngpu, nullptr); s.ev0.assign(ngpu, nullptr); s.ev1.assign(ngpu, nullptr); s.sent.assign(ngpu, nullptr);
-    s.part.assign(ngpu, nullptr); s.gathered.assign(ngpu, nullptr);
-  }
+  mm->dev = dev;
+  mm->per = std::vector<PerDev>(ngpu);
+  for (Slot& s : mm->slot) { s.on = std::vector<SlotDev>(ngpu); s.at0.gathered.resize(ngpu); s.at0.dev = dev[0]; }
+  for (int r = 0; r < ngpu; ++r) { mm->per[r].dev = dev[r]; for (Slot& s : mm->slot) s.on[r].dev = dev[r]; }
   // The BVH is replicated: every device gets the same arrays and builds the same tree -- all devices at once, one host thread
   // each (upload and build are synchronous calls, lbvh_builder.cu:475).
   std::vector<int> rcs(ngpu, MIRT_OK);
@@ -189,24 +205,8 @@ int mirt_multi_create(const MirtSceneDesc* desc, int ngpu, const int* devices, M
     std::vector<std::thread> th;
     for (int r = 0; r < ngpu; ++r) {
       th.emplace_back([&, r]() {
-        int rc = mirt_scene_create(desc, mm->dev[r], &mm->scene[r]);
-        hipError_t e = hipSuccess;
-        if (rc == MIRT_OK) {
-          e = hipSetDevice(mm->dev[r]);
-          if (e == hipSuccess) e = hipStreamCreateWithFlags(&mm->comm_stream[r], hipStreamNonBlocking);
-          for (Slot& s : mm->slot) {
-            if (e == hipSuccess) e = hipStreamCreateWithFlags(&s.stream[r], hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipEventCreate(&s.ev0[r]);
-            if (e == hipSuccess) e = hipEventCreate(&s.ev1[r]);
-            if (e == hipSuccess) e = hipEventCreate(&s.sent[r]);
-            if (e == hipSuccess && r == 0) e = hipEventCreate(&s.gather_end);
-            if (e == hipSuccess && r == 0) e = hipEventCreate(&s.done);
-          }
-          if (e != hipSuccess) rc = hip_err(e, "stream / event creation");
-        }
-        if (rc == MIRT_OK) rc = mirt_build_lbvh(mm->scene[r], mm->slot[0].stream[r], &bms[r]);
-        rcs[r] = rc;
-        if (rc != MIRT_OK) msgs[r] = mirt_last_error();      // (the error string is per thread)
+        rcs[r] = create_on_device(mm, desc, r, &bms[r]);
+        if (rcs[r] != MIRT_OK) msgs[r] = mirt_last_error();      // (the error string is per thread)
       });
     }
     for (std::thread& t : th) t.join();
@@ -217,12 +217,13 @@ int mirt_multi_create(const MirtSceneDesc* desc, int ngpu, const int* devices, M
   }
   if (ngpu > 1 && !copy_gather) {
     if (!load_rccl(mm->rccl)) { mirt_multi_destroy(mm); mirt::set_error("mirt_multi_create: librccl.so not found (needed for more than one GPU)"); return MIRT_ERR_STATE; }
-    mm->comm.assign(ngpu, nullptr);
-    ncclResult_t nr = mm->rccl.CommInitAll(mm->comm.data(), ngpu, mm->dev.data());
+    std::vector<ncclComm_t> comm(ngpu, nullptr);
+    ncclResult_t nr = mm->rccl.CommInitAll(comm.data(), ngpu, mm->dev.data());
     if (nr != ncclSuccess) {
       std::string msg = std::string("mirt_multi_create: ncclCommInitAll: ") + mm->rccl.GetErrorString(nr);
-      mm->comm.clear(); mirt_multi_destroy(mm); mirt::set_error(msg); return MIRT_ERR_HIP;
+      mirt_multi_destroy(mm); mirt::set_error(msg); return MIRT_ERR_HIP;
     }
+    mm->comm = std::move(comm);
   }
   *out = mm;
   return MIRT_OK;
@@ -231,14 +232,14 @@ int mirt_multi_create(const MirtSceneDesc* desc, int ngpu, const int* devices, M
 int mirt_multi_set_option(MirtMulti* mm, const char* name, int value)
 {
   if (!mm) { mirt::set_error("mirt_multi_set_option: null argument"); return MIRT_ERR_ARG; }
-  for (MirtScene* sc : mm->scene) { int rc = mirt_scene_set_option(sc, name, value); if (rc != MIRT_OK) return rc; }
+  for (PerDev& d : mm->per) { int rc = mirt_scene_set_option(d.scene, name, value); if (rc != MIRT_OK) return rc; }
   return MIRT_OK;
 }
 
 int mirt_multi_set_camera(MirtMulti* mm, const MirtCamera* cam)
 {
   if (!mm || !cam) { mirt::set_error("mirt_multi_set_camera: null argument"); return MIRT_ERR_ARG; }
-  for (MirtScene* sc : mm->scene) { int rc = mirt_scene_set_camera(sc, cam); if (rc != MIRT_OK) return rc; }
+  for (PerDev& d : mm->per) { int rc = mirt_scene_set_camera(d.scene, cam); if (rc != MIRT_OK) return rc; }
   return MIRT_OK;
 }
 
@@ -247,10 +248,10 @@ int mirt_multi_set_camera(MirtMulti* mm, const MirtCamera* cam)
 int mirt_multi_set_lights(MirtMulti* mm, const MirtLight* suns, const MirtLight* bulbs)
 {
   if (!mm) { mirt::set_error("mirt_multi_set_lights: null argument"); return MIRT_ERR_ARG; }
-  for (MirtScene* sc : mm->scene) {
-    int rc = mirt_scene_set_lights(sc, suns, bulbs, nullptr);
+  for (PerDev& d : mm->per) {
+    int rc = mirt_scene_set_lights(d.scene, suns, bulbs, nullptr);
     if (rc != MIRT_OK) return rc;
-    MM_HIP(hipStreamSynchronize(nullptr));
+    MIRT_HIP(hipStreamSynchronize(nullptr));
   }
   return MIRT_OK;
 }
@@ -258,10 +259,10 @@ int mirt_multi_set_lights(MirtMulti* mm, const MirtLight* suns, const MirtLight*
 int mirt_multi_set_planes(MirtMulti* mm, const MirtPlane* planes, int first, int count)
 {
   if (!mm) { mirt::set_error("mirt_multi_set_planes: null argument"); return MIRT_ERR_ARG; }
-  for (MirtScene* sc : mm->scene) {
-    int rc = mirt_scene_set_planes(sc, planes, first, count, nullptr);
+  for (PerDev& d : mm->per) {
+    int rc = mirt_scene_set_planes(d.scene, planes, first, count, nullptr);
     if (rc != MIRT_OK) return rc;
-    MM_HIP(hipStreamSynchronize(nullptr));
+    MIRT_HIP(hipStreamSynchronize(nullptr));
   }
   return MIRT_OK;
 }
@@ -269,14 +270,14 @@ int mirt_multi_set_planes(MirtMulti* mm, const MirtPlane* planes, int first, int
 int mirt_multi_set_shading(MirtMulti* mm, const MirtShading* sh)
 {
   if (!mm || !sh) { mirt::set_error("mirt_multi_set_shading: null argument"); return MIRT_ERR_ARG; }
-  for (MirtScene* sc : mm->scene) { int rc = mirt_scene_set_shading(sc, sh); if (rc != MIRT_OK) return rc; }
+  for (PerDev& d : mm->per) { int rc = mirt_scene_set_shading(d.scene, sh); if (rc != MIRT_OK) return rc; }
   return MIRT_OK;
 }
 
 int mirt_multi_get_stats(MirtMulti* mm, int part, MirtStats* out)
 {
   if (!mm || part < 0 || part >= mm->n || !out) { mirt::set_error("mirt_multi_get_stats: bad argument"); return MIRT_ERR_ARG; }
-  return mirt_get_stats(mm->scene[part], out);
+  return mirt_get_stats(mm->per[part].scene, out);
 }
 
 static int submit_impl(MirtMulti* mm, Slot& s, int width, int height, int spp, int stripe_rows, uint8_t* host_rgba)
@@ -294,67 +295,64 @@ static int submit_impl(MirtMulti* mm, Slot& s, int width, int height, int spp, i
   }
   // buffers of this slot (grown on demand, kept; the slot is idle here)
   const size_t part_bytes = (size_t)maxpix * 4, frame_bytes = (size_t)width * height * 4;
-  if (s.part_cap < part_bytes) {
-    for (int r = 0; r < n; ++r) {
-      MM_HIP(hipSetDevice(mm->dev[r]));
-      hipFree(s.part[r]); s.part[r] = nullptr;
-      MM_HIP(hipMalloc(&s.part[r], part_bytes ? part_bytes : 4));
-    }
-    MM_HIP(hipSetDevice(mm->dev[0]));
-    for (int r = 1; r < n; ++r) { hipFree(s.gathered[r]); s.gathered[r] = nullptr; MM_HIP(hipMalloc(&s.gathered[r], part_bytes ? part_bytes : 4)); }
-    s.part_cap = part_bytes;
+  // The capacity of the LAST part buffer allocated stands for all of them: all are reset before the first is allocated, so a
+  // failure midway leaves it 0 and the next submit allocates again.  (part_bytes > 0: part 0 owns row 0 of a frame with pixels.)
+  const mirt::DevBuf<unsigned char>& last = n > 1 ? s.at0.gathered[n - 1] : s.on[0].part;
+  if (last.cap() < part_bytes) {
+    for (int r = 0; r < n; ++r) { s.on[r].part.reset(); s.at0.gathered[r].reset(); }
+    for (int r = 0; r < n; ++r) { MIRT_HIP(hipSetDevice(mm->dev[r])); MIRT_TRY(s.on[r].part.alloc(part_bytes)); }
+    MIRT_HIP(hipSetDevice(mm->dev[0]));
+    for (int r = 1; r < n; ++r) MIRT_TRY(s.at0.gathered[r].alloc(part_bytes));
   }
-  if (n > 1 && s.frame_cap < frame_bytes) {
-    MM_HIP(hipSetDevice(mm->dev[0]));
-    hipFree(s.frame); s.frame = nullptr;
-    MM_HIP(hipMalloc(&s.frame, frame_bytes));
-    s.frame_cap = frame_bytes;
+  if (n > 1 && s.at0.frame.cap() < frame_bytes) {
+    MIRT_HIP(hipSetDevice(mm->dev[0]));
+    MIRT_TRY(s.at0.frame.alloc(frame_bytes));
   }
   // every device renders its stripes on this slot's stream
   for (int r = 0; r < n; ++r) {
-    MM_HIP(hipSetDevice(mm->dev[r]));
-    MM_HIP(hipEventRecord(s.ev0[r], s.stream[r]));
-    if (npix[r] > 0) { int rc = mirt_render(mm->scene[r], &prm[r], s.part[r], nullptr, s.stream[r]); if (rc != MIRT_OK) return rc; }
-    MM_HIP(hipEventRecord(s.ev1[r], s.stream[r]));
-    MM_HIP(hipStreamWaitEvent(mm->comm_stream[r], s.ev1[r], 0));      // the gather of this frame follows its part, and the gathers before it
+    MIRT_HIP(hipSetDevice(mm->dev[r]));
+    MIRT_HIP(hipEventRecord(s.on[r].ev0, s.on[r].stream));
+    if (npix[r] > 0) { int rc = mirt_render(mm->per[r].scene, &prm[r], s.on[r].part, nullptr, s.on[r].stream); if (rc != MIRT_OK) return rc; }
+    MIRT_HIP(hipEventRecord(s.on[r].ev1, s.on[r].stream));
+    MIRT_HIP(hipStreamWaitEvent(mm->per[r].comm_stream, s.on[r].ev1, 0));      // the gather of this frame follows its part, and the gathers before it
   }
-  const void* result = s.part[0];          // one device: its part is the row-major frame
+  const void* result = s.on[0].part;       // one device: its part is the row-major frame
   if (n > 1) {
     if (mm->copy_gather) {
       // peer-to-peer copies issued on the sender's communication stream; device 0 waits for each
       for (int r = 1; r < n; ++r) {
         if (npix[r] == 0) continue;
-        MM_HIP(hipSetDevice(mm->dev[r]));
-        MM_HIP(hipMemcpyPeerAsync(s.gathered[r], mm->dev[0], s.part[r], mm->dev[r], (size_t)npix[r] * 4, mm->comm_stream[r]));
-        MM_HIP(hipEventRecord(s.ev1[r], mm->comm_stream[r]));
-        MM_HIP(hipSetDevice(mm->dev[0]));
-        MM_HIP(hipStreamWaitEvent(mm->comm_stream[0], s.ev1[r], 0));
+        MIRT_HIP(hipSetDevice(mm->dev[r]));
+        MIRT_HIP(hipMemcpyPeerAsync(s.at0.gathered[r], mm->dev[0], s.on[r].part, mm->dev[r], (size_t)npix[r] * 4, mm->per[r].comm_stream));
+        MIRT_HIP(hipEventRecord(s.on[r].ev1, mm->per[r].comm_stream));
+        MIRT_HIP(hipSetDevice(mm->dev[0]));
+        MIRT_HIP(hipStreamWaitEvent(mm->per[0].comm_stream, s.on[r].ev1, 0));
       }
     } else {
       // framebuffer gather to device 0: one grouped exchange per frame, each peer on its own xGMI link
       ncclResult_t nr = mm->rccl.GroupStart();
       for (int r = 1; r < n && nr == ncclSuccess; ++r) {
         if (npix[r] == 0) continue;
-        nr = mm->rccl.Send(s.part[r], (size_t)npix[r] * 4, ncclUint8, 0, mm->comm[r], mm->comm_stream[r]);
-        if (nr == ncclSuccess) nr = mm->rccl.Recv(s.gathered[r], (size_t)npix[r] * 4, ncclUint8, r, mm->comm[0], mm->comm_stream[0]);
+        nr = mm->rccl.Send(s.on[r].part, (size_t)npix[r] * 4, ncclUint8, 0, mm->comm[r], mm->per[r].comm_stream);
+        if (nr == ncclSuccess) nr = mm->rccl.Recv(s.at0.gathered[r], (size_t)npix[r] * 4, ncclUint8, r, mm->comm[0], mm->per[0].comm_stream);
       }
       const ncclResult_t ne = mm->rccl.GroupEnd();
       if (nr == ncclSuccess) nr = ne;
       if (nr != ncclSuccess) { mirt::set_error(std::string("mirt_multi_submit: RCCL: ") + mm->rccl.GetErrorString(nr)); return MIRT_ERR_HIP; }
     }
-    for (int r = 1; r < n; ++r) { MM_HIP(hipSetDevice(mm->dev[r])); MM_HIP(hipEventRecord(s.sent[r], mm->comm_stream[r])); }
-    MM_HIP(hipSetDevice(mm->dev[0]));
+    for (int r = 1; r < n; ++r) { MIRT_HIP(hipSetDevice(mm->dev[r])); MIRT_HIP(hipEventRecord(s.on[r].sent, mm->per[r].comm_stream)); }
+    MIRT_HIP(hipSetDevice(mm->dev[0]));
     for (int r = 0; r < n; ++r) {
       if (npix[r] == 0) continue;
-      int rc = mirt_scatter_part(&prm[r], r == 0 ? s.part[0] : s.gathered[r], s.frame, mm->comm_stream[0]);
+      int rc = mirt_scatter_part(&prm[r], r == 0 ? s.on[0].part : s.at0.gathered[r], s.at0.frame, mm->per[0].comm_stream);
       if (rc != MIRT_OK) return rc;
     }
-    result = s.frame;
+    result = s.at0.frame;
   }
-  MM_HIP(hipSetDevice(mm->dev[0]));
-  MM_HIP(hipEventRecord(s.gather_end, mm->comm_stream[0]));
-  if (host_rgba) MM_HIP(hipMemcpyAsync(host_rgba, result, frame_bytes, hipMemcpyDeviceToHost, mm->comm_stream[0]));
-  MM_HIP(hipEventRecord(s.done, mm->comm_stream[0]));
+  MIRT_HIP(hipSetDevice(mm->dev[0]));
+  MIRT_HIP(hipEventRecord(s.at0.gather_end, mm->per[0].comm_stream));
+  if (host_rgba) MIRT_HIP(hipMemcpyAsync(host_rgba, result, frame_bytes, hipMemcpyDeviceToHost, mm->per[0].comm_stream));
+  MIRT_HIP(hipEventRecord(s.at0.done, mm->per[0].comm_stream));
   return MIRT_OK;
 }
 
@@ -386,12 +384,12 @@ int mirt_multi_wait(MirtMulti* mm, uint64_t ticket, MirtMultiStats* stats)
   if (!s.busy || s.ticket != ticket) { mirt::set_error("mirt_multi_wait: no such frame in flight"); return MIRT_ERR_ARG; }
   const int n = mm->n;
   for (int r = 0; r < n; ++r) {
-    MM_HIP(hipSetDevice(mm->dev[r]));
-    MM_HIP(hipEventSynchronize(s.ev1[r]));
-    if (r > 0 && n > 1) MM_HIP(hipEventSynchronize(s.sent[r]));      // its part buffer is free again
+    MIRT_HIP(hipSetDevice(mm->dev[r]));
+    MIRT_HIP(hipEventSynchronize(s.on[r].ev1));
+    if (r > 0 && n > 1) MIRT_HIP(hipEventSynchronize(s.on[r].sent));      // its part buffer is free again
   }
-  MM_HIP(hipSetDevice(mm->dev[0]));
-  MM_HIP(hipEventSynchronize(s.done));
+  MIRT_HIP(hipSetDevice(mm->dev[0]));
+  MIRT_HIP(hipEventSynchronize(s.at0.done));
   s.busy = false;
   --mm->outstanding;
   if (stats) {
@@ -400,15 +398,15 @@ int mirt_multi_wait(MirtMulti* mm, uint64_t ticket, MirtMultiStats* stats)
     stats->build_ms = mm->build_ms_max;
     if (!mm->copy_gather || n == 1) {      // (with peer copies ev1[r >= 1] was re-recorded after the copy)
       for (int r = 0; r < n && r < MIRT_MULTI_MAX_GPUS; ++r) {
-        MM_HIP(hipSetDevice(mm->dev[r]));
-        MM_HIP(hipEventElapsedTime(&stats->render_ms[r], s.ev0[r], s.ev1[r]));
+        MIRT_HIP(hipSetDevice(mm->dev[r]));
+        MIRT_HIP(hipEventElapsedTime(&stats->render_ms[r], s.on[r].ev0, s.on[r].ev1));
       }
     } else {
-      MM_HIP(hipSetDevice(mm->dev[0]));
-      MM_HIP(hipEventElapsedTime(&stats->render_ms[0], s.ev0[0], s.ev1[0]));
+      MIRT_HIP(hipSetDevice(mm->dev[0]));
+      MIRT_HIP(hipEventElapsedTime(&stats->render_ms[0], s.on[0].ev0, s.on[0].ev1));
     }
-    MM_HIP(hipSetDevice(mm->dev[0]));
-    MM_HIP(hipEventElapsedTime(&stats->gather_ms, s.ev1[0], s.gather_end));
+    MIRT_HIP(hipSetDevice(mm->dev[0]));
+    MIRT_HIP(hipEventElapsedTime(&stats->gather_ms, s.on[0].ev1, s.at0.gather_end));
     stats->frame_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - s.t0).count();
   }
   // a capacity overflow on any device makes the frame untrustworthy: checked whenever the pipeline is empty

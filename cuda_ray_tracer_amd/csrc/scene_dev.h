@@ -344,9 +344,7 @@ int temporal_accumulate(const MirtRenderParams* p, const MirtCamera* prev_camera
 // wavefront.hip
 int wavefront_trace(MirtScene* sc, RenderCtx& cx, RenderArgs& a, bool count, hipStream_t stream, float* trace_ms);
 }
-#define MIRT_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return mirt::hip_fail(e_, #call, __FILE__, __LINE__); } while (0)
-// the same for a call that has reported its own failure and returns a MIRT_* status
-#define MIRT_TRY(call) do { const int rc_ = (call); if (rc_ != MIRT_OK) return rc_; } while (0)
+// (MIRT_HIP, MIRT_TRY: dev_mem.h)
 
 namespace mirt {
 

@@ -15,7 +15,7 @@
 
 namespace {
 
-enum Kind { DEVICE, PINNED, EVENT, KINDS };
+enum Kind { DEVICE, PINNED, EVENT, STREAM, KINDS };
 std::set<void*> live[KINDS];
 int allocations = 0, fail_at = 0;      // fail_at = k > 0: the k-th allocation from now fails
 int stream_waits = 0, frees = 0;
@@ -42,7 +42,7 @@ hipError_t give(Kind k, void* p)
   return hipSuccess;
 }
 
-size_t live_total() { return live[DEVICE].size() + live[PINNED].size() + live[EVENT].size(); }
+size_t live_total() { return live[DEVICE].size() + live[PINNED].size() + live[EVENT].size() + live[STREAM].size(); }
 
 } // namespace
 
@@ -53,6 +53,8 @@ hipError_t hipHostMalloc(void** p, size_t bytes, unsigned int) { return take(PIN
 hipError_t hipHostFree(void* p) { return give(PINNED, p); }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return take(EVENT, (void**)e, 1, hipErrorInvalidValue); }
 hipError_t hipEventDestroy(hipEvent_t e) { return give(EVENT, (void*)e); }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { return take(STREAM, (void**)s, 1, hipErrorInvalidValue); }
+hipError_t hipStreamDestroy(hipStream_t s) { return give(STREAM, (void*)s); }
 hipError_t hipStreamSynchronize(hipStream_t) { ++stream_waits; return hipSuccess; }
 const char* hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory" : "error"; }
 }
@@ -221,6 +223,55 @@ void event_case()
   CHECK(live[EVENT].empty() && frees == freed + 100);
 }
 
+bool names(int line, const char* what);
+
+void stream_case()
+{
+  {
+    Stream s;
+    CHECK((hipStream_t)s == nullptr && !s);
+    CHECK(s.create(hipStreamNonBlocking) == MIRT_OK && s && live[STREAM].size() == 1);
+    const hipStream_t h = s;
+    CHECK(s.create(hipStreamDefault) == MIRT_OK && (hipStream_t)s == h && live[STREAM].size() == 1);      // twice: one stream
+    Stream f(std::move(s));
+    CHECK(!s && (hipStream_t)f == h && live[STREAM].size() == 1);
+    Stream g;
+    CHECK(g.create(hipStreamNonBlocking) == MIRT_OK && live[STREAM].size() == 2);
+    const hipStream_t old = g;
+    g = std::move(f);                                       // move assignment: the target's old stream is destroyed
+    CHECK(!f && (hipStream_t)g == h && live[STREAM].count((void*)old) == 0 && live[STREAM].size() == 1);
+    g.reset();
+    CHECK(!g && live[STREAM].empty());
+    g.reset();                                              // twice
+    { Stream never; CHECK(!never); }                        // destruction of an empty object
+    CHECK(live[STREAM].empty());
+    fail_at = 1; last_error.clear();
+    Stream bad;
+    const int line = __LINE__ + 1;
+    CHECK(bad.create(hipStreamNonBlocking) == MIRT_ERR_HIP && !bad);
+    CHECK(names(line, "hipStreamCreateWithFlags"));
+    CHECK(bad.create(hipStreamNonBlocking) == MIRT_OK && bad);
+  }
+  CHECK(live[STREAM].empty());
+  // a vector sized once (as a slot's are) and one grown past several reallocations: each stream is destroyed exactly once
+  const int freed = frees;
+  {
+    std::vector<Stream> sized(7), v;
+    for (Stream& s : sized) CHECK(s.create(hipStreamNonBlocking) == MIRT_OK);
+    for (int i = 0; i < 100; ++i) {
+      Stream s;
+      CHECK(s.create(hipStreamNonBlocking) == MIRT_OK);
+      v.push_back(std::move(s));
+    }
+    CHECK(live[STREAM].size() == 107 && frees == freed);
+    std::set<void*> distinct;
+    for (const Stream& s : sized) distinct.insert((void*)(hipStream_t)s);
+    for (const Stream& s : v) distinct.insert((void*)(hipStream_t)s);
+    CHECK(distinct == live[STREAM]);
+  }
+  CHECK(live[STREAM].empty() && frees == freed + 107);
+}
+
 // Four buffers of one length whose LAST capacity stands for all four, as the chunk orders and their cost buffer are kept
 // (chunk_order_find, render.hip): all are reset before the first is allocated, so whichever allocation fails, that capacity is 0.
 int four_together(DevBuf<int>& cost, DevBuf<int> (&out)[3], size_t n)
@@ -283,7 +334,7 @@ const Case CASES[] = {
   {"failure_device", [] { failure_case<DevBuf<double>>(DEVICE); }}, {"failure_pinned", [] { failure_case<PinnedBuf<double>>(PINNED); }},
   {"move_device", [] { move_case<DevBuf<char>>(DEVICE); }}, {"move_pinned", [] { move_case<PinnedBuf<char>>(PINNED); }},
   {"reset_device", [] { reset_case<DevBuf<int>>(DEVICE); }}, {"reset_pinned", [] { reset_case<PinnedBuf<int>>(PINNED); }},
-  {"conversion", conversion_case}, {"event", event_case}, {"together", together_case}, {"message", message_case},
+  {"conversion", conversion_case}, {"event", event_case}, {"stream", stream_case}, {"together", together_case}, {"message", message_case},
 };
 
 } // namespace

@@ -1,4 +1,4 @@
-"""The owning types of csrc/dev_mem.h (DevBuf, PinnedBuf, Event) need no GPU: a stand-alone probe, tests/dev_mem_probe.cpp, defines
+"""The owning types of csrc/dev_mem.h (DevBuf, PinnedBuf, Event, Stream) need no GPU: a stand-alone probe, tests/dev_mem_probe.cpp, defines
 the few runtime entry points the header calls over malloc -- a set of live handles, an abort on a free of something not live, a
 k-th allocation that can be told to fail -- and is compiled with the host compiler (address + undefined sanitizers where they
 link).  Each case checks itself and that nothing is live when it ends.  The same file holds the source check that keeps the
@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "cuda_ray_tracer_amd", "csrc")
 
-CASES = ["grow_device", "grow_pinned", "failure_device", "failure_pinned", "move_device", "move_pinned", "reset_device", "reset_pinned", "conversion", "event", "together", "message"]
+CASES = ["grow_device", "grow_pinned", "failure_device", "failure_pinned", "move_device", "move_pinned", "reset_device", "reset_pinned", "conversion", "event", "stream", "together", "message"]
 
 
 def rocm_include():
@@ -61,6 +61,8 @@ def test_owning_types(probe, case):
     returns the error status, the raw form the runtime's error with no message set.  move_*: construction and assignment empty the
     source, assignment frees the target's old block.  reset_*: reset twice, destruction of an empty object, zero-length alloc.
     event: create twice makes one event; a std::vector<Event> grown past several reallocations destroys each event exactly once.
+    stream: the same of Stream, with reset twice, destruction of an empty object and a failing creation that leaves it empty and
+    names the call's file and line.
     together: four buffers whose last capacity stands for all (the chunk orders), the k-th allocation failing, then a smaller
     request: it allocates again.  message: a failure names the file and line of the call and the caller's label.
     Every case: the live set is empty at exit (a free of something not live aborts in the probe)."""
@@ -69,8 +71,8 @@ def test_owning_types(probe, case):
     assert r.stdout.startswith(case + ":") and r.stdout.rstrip().endswith(" 0 failures"), r.stdout
 
 
-FORBIDDEN = ("hipFree", "hipHostFree", "hipEventDestroy", "hipMalloc(", "hipHostMalloc(", "hipEventCreate")
-EXEMPT = ("dev_mem.h", "multi.cpp", "raytracer_main.cpp")      # the types themselves; several devices and RCCL; a client of the C ABI
+FORBIDDEN = ("hipFree", "hipHostFree", "hipEventDestroy", "hipMalloc(", "hipHostMalloc(", "hipEventCreate", "hipStreamCreate", "hipStreamDestroy")
+EXEMPT = ("dev_mem.h", "raytracer_main.cpp")      # the types themselves; a client of the C ABI
 
 
 def test_only_the_owning_types_allocate_and_release():

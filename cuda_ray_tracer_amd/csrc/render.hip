@@ -142,9 +142,17 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
       S.wD = mk3(__uint_as_float(p1.x), __uint_as_float(p1.y), __uint_as_float(p1.z)); S.Hior = __uint_as_float(p1.w);
     }
     // (once the frame's queue is empty the first ray of a new batch is started by the traversal loop's header instead)
-    while (!S.trav && S.g >= 0 && !(exhausted && S.batch_pending && !MIRT_HELD)) {
-      if (S.batch_pending) batch_next<COUNT, QN, RenderArgs, SPEC>(a, S, cn);
-      else advance<COUNT, QN, SPEC>(a, S, cn, gid, gthreads);
+    // One pass serves the whole wave in the common case (1.03 passes per shade phase on the headline frame): a lane whose batch
+    // ended with the ray that just finished -- its reflection ray, or the last shadow ray of a node without one -- learns so from
+    // batch_next and is shaded by the SAME pass's advance(), next to the lanes that arrived without a batch.  (With the second arm
+    // an `else` those two or three lanes came back for a pass of their own: 1.59 executions of the whole advance() stream per shade
+    // phase.)  Every lane still goes through the same calls in the same order.  The loop is written wave-uniform, the lanes'
+    // conditions inside it: as a per-lane `while` around the two `if`s the same code spilled 180 registers in two of the kernels.
+    for (;;) {
+      const bool live = !S.trav && S.g >= 0 && !(exhausted && S.batch_pending && !MIRT_HELD);
+      if (__ballot(live) == 0) break;
+      if (live && S.batch_pending) batch_next<COUNT, QN, RenderArgs, SPEC>(a, S, cn);
+      if (live && !S.trav && !S.batch_pending) advance<COUNT, QN, SPEC>(a, S, cn, gid, gthreads);
     }
     if (!exhausted) {
       // lanes without a sample take new ones -- once init_k of them wait, or when the wave has nothing else to do: starting a

@@ -14,236 +14,64 @@ Device memory, streams and torch.distributed come from PyTorch (plumbing only); 
 hand-written HIP kernels of libmirt.so.  There is no CPU fallback: if the library is missing or no GPU is present
 the calls raise.
 """
+import contextlib
 import ctypes as C
 import os
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-# MIRT_LIB: load another build of the same library (tools/ab.py builds A/B variants next to the default one)
-LIB_PATH = os.environ.get("MIRT_LIB") or os.path.join(HERE, "_build", "libmirt.so")
+from .binding import (LIB_PATH, EXPORTS, MIRT_ERR_ARG, MIRT_RENDER_COUNTERS, MIRT_HIT_NONE, MIRT_HIT_SPHERE, MIRT_HIT_TRIANGLE,      # noqa: F401
+                      MIRT_HIT_PLANE, MIRT_QUERY_ANY_HIT, MIRT_DENOISE_SIGMA_C, MIRT_DENOISE_SIGMA_N, MIRT_DENOISE_SIGMA_P, MirtError, Vec3, Ray,
+                      Hit, Camera, Shading, SceneDesc, RenderParams, Stats, MultiStats, TreeNode, lib, _check)
 
-MIRT_RENDER_COUNTERS = 1
-MIRT_HIT_NONE, MIRT_HIT_SPHERE, MIRT_HIT_TRIANGLE, MIRT_HIT_PLANE = 0, 1, 2, 3
-MIRT_QUERY_ANY_HIT = 1
-
-
-class MirtError(RuntimeError):
-    def __init__(self, status, message):
-        super().__init__(f"libmirt status {status}: {message}")
-        self.status = status
-        self.message = message
+# The dtypes a tensor argument may have, by name: torch is imported when a call needs it (uint32 only where torch has it)
+_F32, _U8, _INT, _HIT = ("float32",), ("uint8",), ("int32", "uint32"), ("float32", "int32", "uint32")
 
 
-class Vec3(C.Structure):
-    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float)]
-
-    def tolist(self):
-        return [self.x, self.y, self.z]
-
-
-class Ray(C.Structure):
-    """MirtRay: one row of a float32 [n, 8] ray tensor (pack_rays)."""
-    _fields_ = [("o", Vec3), ("tmax", C.c_float), ("d", Vec3), ("pad", C.c_float)]
-
-
-class Hit(C.Structure):
-    """MirtHit: one row of a 4-byte [n, 6] hit tensor (unpack_hits)."""
-    _fields_ = [("t", C.c_float), ("kind", C.c_uint32), ("id", C.c_uint32), ("n", Vec3)]
-
-
-class Camera(C.Structure):
-    """MirtCamera: the camera fields of a scene (RawConfig.camera / set_camera)."""
-    _fields_ = [("eye", Vec3), ("forward", Vec3), ("right", Vec3), ("up", Vec3),
-                ("dof_focus", C.c_float), ("dof_lens", C.c_float), ("fisheye", C.c_int32), ("panorama", C.c_int32)]
-
-
-class Shading(C.Structure):
-    """MirtShading: bounces, gi and expose of a scene (RawConfig.shading / set_shading); expose +inf = exposure off."""
-    _fields_ = [("bounces", C.c_int32), ("gi", C.c_int32), ("expose", C.c_float)]
-
-
-def _camera_with(cam, fields):
-    """A copy of `cam` with the keyword fields replaced (a Vec3 field takes a Vec3 or three numbers)."""
-    out = Camera.from_buffer_copy(bytes(cam))
-    names = dict(Camera._fields_)
+def _struct_with(cls, s, fields, what):
+    """A `cls` copy of `s` with the keyword fields replaced (a Vec3 field takes a Vec3 or three numbers)."""
+    out = cls.from_buffer_copy(bytes(s))
+    names = dict(cls._fields_)
     for k, v in fields.items():
         if k not in names:
-            raise ValueError(f"{k} is not a camera field; expected one of {sorted(names)}")
+            raise ValueError(f"{k} is not a {what} field; expected one of {sorted(names)}")
         if names[k] is Vec3 and not isinstance(v, Vec3):
             v = Vec3(*(float(c) for c in v))
         setattr(out, k, v)
     return out
 
 
-class SceneDesc(C.Structure):
-    _fields_ = [
-        ("width", C.c_int32), ("height", C.c_int32), ("bounces", C.c_int32), ("aa", C.c_int32),
-        ("dof_focus", C.c_float), ("dof_lens", C.c_float),
-        ("forward", Vec3), ("right", Vec3), ("up", Vec3), ("eye", Vec3),
-        ("expose", C.c_float),
-        ("fisheye", C.c_int32), ("panorama", C.c_int32), ("gi", C.c_int32),
-        ("num_spheres", C.c_int32), ("num_triangles", C.c_int32), ("num_prims", C.c_int32),
-        ("num_planes", C.c_int32), ("num_suns", C.c_int32), ("num_bulbs", C.c_int32),
-        ("spheres", C.c_void_p), ("triangles", C.c_void_p), ("prim_refs", C.c_void_p),
-        ("planes", C.c_void_p), ("suns", C.c_void_p), ("bulbs", C.c_void_p),
-    ]
+def _camera_with(cam, fields):
+    """A copy of `cam` with the keyword fields replaced (a Vec3 field takes a Vec3 or three numbers)."""
+    return _struct_with(Camera, cam, fields, "camera")
 
 
-class RenderParams(C.Structure):
-    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32),
-                ("stripe_rows", C.c_int32), ("num_parts", C.c_int32), ("part", C.c_int32), ("flags", C.c_uint32)]
+def _shading_with(sh, fields):
+    """A copy of `sh` with the keyword fields replaced."""
+    return _struct_with(Shading, sh, fields, "shading")
 
 
-class Stats(C.Structure):
-    _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "shadow_rays", "internal_visits", "sphere_tests",
-                                          "tri_tests", "mat_fetches", "max_stack", "overflow_events")] + \
-               [("trace_kernel_ms", C.c_float), ("render_ms", C.c_float), ("build_ms", C.c_float), ("num_nodes", C.c_int32),
-                ("trace_kernel_ms_mean", C.c_float), ("frames_timed", C.c_int32), ("trace_launches", C.c_int32), ("node_record_bytes", C.c_int32),
-                ("rays_traversed", C.c_uint64)]
+class _Handle:
+    """Owner of one library handle, self._h, which the entry point named by _destroy frees: close() frees it once, and __del__
+    closes without raising (the interpreter may be half gone)."""
+    _destroy = None
 
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
 
-
-MULTI_MAX_GPUS = 16
-
-
-class MultiStats(C.Structure):
-    _fields_ = [("num_gpus", C.c_int32), ("build_ms", C.c_float), ("render_ms", C.c_float * MULTI_MAX_GPUS),
-                ("gather_ms", C.c_float), ("frame_ms", C.c_float)]
-
-
-class TreeNode(C.Structure):
-    _fields_ = [("xmin", C.c_float), ("xmax", C.c_float), ("ymin", C.c_float), ("ymax", C.c_float),
-                ("zmin", C.c_float), ("zmax", C.c_float),
-                ("left", C.c_uint32), ("right", C.c_uint32), ("prim_offset", C.c_uint32), ("count", C.c_uint32)]
-
-
-EXPORTS = [
-    "mirt_last_error", "mirt_version", "mirt_parse_scene_file", "mirt_parse_scene_text", "mirt_synthetic_scene",
-    "mirt_host_scene_destroy", "mirt_host_scene_desc", "mirt_host_scene_filename", "mirt_scene_create",
-    "mirt_scene_destroy", "mirt_scene_set_option", "mirt_scene_get_option", "mirt_build_lbvh", "mirt_render_num_pixels", "mirt_render", "mirt_render_accumulate", "mirt_finalize", "mirt_scatter_part",
-    "mirt_get_stats", "mirt_get_tree", "mirt_probe_math", "mirt_probe_xorwow", "mirt_write_png",
-    "mirt_multi_create", "mirt_multi_destroy", "mirt_multi_num_parts", "mirt_multi_set_option", "mirt_render_frame_multi",
-    "mirt_multi_submit", "mirt_multi_wait", "mirt_render_frames_multi", "mirt_multi_get_stats", "mirt_part_pixel_xy",
-    "mirt_trace_rays", "mirt_camera_rays",
-    "mirt_scene_get_camera", "mirt_scene_set_camera", "mirt_multi_set_camera", "mirt_scene_update_spheres", "mirt_scene_update_triangles",
-    "mirt_render_accumulate_pixels", "mirt_select_pixels", "mirt_finalize_counts",
-    "mirt_hit_features", "mirt_denoise", "mirt_denoise_work_bytes",
-    "mirt_scene_get_spheres", "mirt_scene_get_triangles", "mirt_prev_features", "mirt_temporal_accumulate",
-    "mirt_scene_get_lights", "mirt_scene_set_lights", "mirt_scene_get_planes", "mirt_scene_set_planes", "mirt_make_plane",
-    "mirt_scene_get_shading", "mirt_scene_set_shading", "mirt_scene_update_sphere_materials", "mirt_scene_update_triangle_materials",
-    "mirt_scene_get_sphere_materials", "mirt_scene_get_triangle_materials", "mirt_multi_set_lights", "mirt_multi_set_planes",
-    "mirt_multi_set_shading",
-]
-
-_lib = None
-
-
-def lib():
-    """Load libmirt.so (fails loudly if it has not been built: `python -m cuda_ray_tracer_amd.build`)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise MirtError(-1, f"{LIB_PATH} not found: build it with `python -m cuda_ray_tracer_amd.build` "
-                            "(there is no fallback implementation)")
-    try:
-        import torch  # noqa: F401  (loads the process-wide HIP runtime first so both share one instance)
-    except Exception:
-        pass
-    L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    L.mirt_last_error.restype = C.c_char_p
-    L.mirt_parse_scene_file.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
-    L.mirt_parse_scene_text.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
-    L.mirt_synthetic_scene.argtypes = [C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-    L.mirt_host_scene_destroy.argtypes = [C.c_void_p]
-    L.mirt_host_scene_destroy.restype = None
-    L.mirt_host_scene_desc.argtypes = [C.c_void_p, C.POINTER(SceneDesc)]
-    L.mirt_host_scene_filename.argtypes = [C.c_void_p]
-    L.mirt_host_scene_filename.restype = C.c_char_p
-    L.mirt_scene_create.argtypes = [C.POINTER(SceneDesc), C.c_int, C.POINTER(C.c_void_p)]
-    L.mirt_scene_destroy.argtypes = [C.c_void_p]
-    L.mirt_scene_destroy.restype = None
-    L.mirt_scene_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    L.mirt_scene_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]
-    L.mirt_build_lbvh.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
-    L.mirt_render_num_pixels.argtypes = [C.POINTER(RenderParams)]
-    L.mirt_render_num_pixels.restype = C.c_int64
-    L.mirt_render.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.mirt_render_accumulate.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.mirt_finalize.argtypes = [C.POINTER(RenderParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.mirt_scatter_part.argtypes = [C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.mirt_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
-    L.mirt_get_tree.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.mirt_probe_math.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.mirt_probe_xorwow.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    L.mirt_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int]
-    L.mirt_multi_create.argtypes = [C.POINTER(SceneDesc), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p)]
-    L.mirt_multi_destroy.argtypes = [C.c_void_p]
-    L.mirt_multi_destroy.restype = None
-    L.mirt_multi_num_parts.argtypes = [C.c_void_p]
-    L.mirt_multi_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    L.mirt_render_frame_multi.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(MultiStats)]
-    L.mirt_multi_submit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
-    L.mirt_multi_wait.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(MultiStats)]
-    L.mirt_render_frames_multi.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(MultiStats), C.POINTER(C.c_float)]
-    L.mirt_multi_get_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(Stats)]
-    L.mirt_part_pixel_xy.argtypes = [C.POINTER(RenderParams), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    if hasattr(L, "mirt_trace_rays"):      # (ray queries: a build that predates them -- MIRT_LIB A/B runs -- still loads)
-        L.mirt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p]
-        L.mirt_camera_rays.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_void_p]
-    if hasattr(L, "mirt_scene_set_camera"):      # (updates in place: likewise)
-        L.mirt_scene_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
-        L.mirt_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
-        L.mirt_multi_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
-        L.mirt_scene_update_spheres.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.mirt_scene_update_triangles.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    if hasattr(L, "mirt_render_accumulate_pixels"):      # (adaptive sampling: likewise)
-        L.mirt_render_accumulate_pixels.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                    C.c_int, C.c_int, C.c_void_p]
-        L.mirt_select_pixels.argtypes = [C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
-                                         C.c_void_p]
-        L.mirt_finalize_counts.argtypes = [C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    if hasattr(L, "mirt_denoise"):      # (denoising: likewise)
-        L.mirt_hit_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        L.mirt_denoise_work_bytes.argtypes = [C.POINTER(RenderParams)]
-        L.mirt_denoise_work_bytes.restype = C.c_size_t
-        L.mirt_denoise.argtypes = [C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float,
-                                   C.c_void_p, C.c_void_p, C.c_void_p]
-    if hasattr(L, "mirt_temporal_accumulate"):      # (temporal accumulation: likewise)
-        L.mirt_scene_get_spheres.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.mirt_scene_get_triangles.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.mirt_prev_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mirt_temporal_accumulate.argtypes = [C.POINTER(RenderParams), C.POINTER(Camera)] + [C.c_void_p] * 8 + [C.c_int, C.c_float, C.c_float] + \
-                                              [C.c_void_p] * 4
-    if hasattr(L, "mirt_scene_set_lights"):      # (shading values in place: likewise)
-        L.mirt_scene_get_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mirt_scene_set_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mirt_scene_get_planes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.mirt_scene_set_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.mirt_make_plane.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mirt_scene_get_shading.argtypes = [C.c_void_p, C.POINTER(Shading)]
-        L.mirt_scene_set_shading.argtypes = [C.c_void_p, C.POINTER(Shading)]
-        for f in (L.mirt_scene_update_sphere_materials, L.mirt_scene_update_triangle_materials):
-            f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        for f in (L.mirt_scene_get_sphere_materials, L.mirt_scene_get_triangle_materials):
-            f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.mirt_multi_set_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mirt_multi_set_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-        L.mirt_multi_set_shading.argtypes = [C.c_void_p, C.POINTER(Shading)]
-    _lib = L
-    return L
-
-
-def _check(rc):
-    if rc != 0:
-        raise MirtError(rc, lib().mirt_last_error().decode("utf-8", "replace"))
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ------------------------------------------------------------------------------------------------------
 # StlConfig: the parsed scene on the host (config.hpp:24-73)
 # ------------------------------------------------------------------------------------------------------
-class StlConfig:
+class StlConfig(_Handle):
+    _destroy = "mirt_host_scene_destroy"
+
     def __init__(self, handle):
         self._h = C.c_void_p(handle)
         self.desc = SceneDesc()
@@ -252,17 +80,6 @@ class StlConfig:
         for name in ("width", "height", "bounces", "aa", "dof_focus", "dof_lens", "expose", "fisheye", "panorama", "gi",
                      "num_spheres", "num_triangles", "num_prims", "num_planes", "num_suns", "num_bulbs"):
             setattr(self, name, getattr(self.desc, name))
-
-    def close(self):
-        if self._h:
-            lib().mirt_host_scene_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def array(self, which):
         """Host arrays as numpy structured views (spheres, triangles, prim_refs, planes, suns, bulbs)."""
@@ -307,7 +124,9 @@ def syntheticScene(num_spheres=1_000_000, num_triangles=1_000_000, seed=1234):
 # ------------------------------------------------------------------------------------------------------
 # RawConfig: the device-resident scene (config.hpp:75-126)
 # ------------------------------------------------------------------------------------------------------
-class RawConfig:
+class RawConfig(_Handle):
+    _destroy = "mirt_scene_destroy"
+
     def __init__(self, stl_or_desc, device=0):
         desc = stl_or_desc.desc if hasattr(stl_or_desc, "desc") else stl_or_desc
         self._keep = stl_or_desc
@@ -317,17 +136,6 @@ class RawConfig:
         _check(lib().mirt_scene_create(C.byref(desc), device, C.byref(h)))
         self._h = h
         self.build_ms = None
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().mirt_scene_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def stats(self):
         """MirtStats as a dict.  Raises MirtError (status 6) when a capacity overflow was recorded during a render."""
@@ -372,8 +180,8 @@ class RawConfig:
         """mirt_scene_set_lights: new suns and / or bulbs (numpy layouts.LIGHT arrays of the scene's num_suns / num_bulbs
         records; None leaves that kind as it is).  The counts are fixed: a zero colour switches a light off.  The scene stays
         built; a frame in flight keeps its lights.  Asynchronous on `stream` (default: torch's current stream)."""
-        arrays = [_records(a, name, _light_dtype(), n) for a, name, n in ((suns, "suns", self.desc.num_suns), (bulbs, "bulbs", self.desc.num_bulbs))]
-        _check(lib().mirt_scene_set_lights(self._h, _host_ptr(arrays[0]), _host_ptr(arrays[1]), _stream_ptr(stream)))
+        ptrs = _light_ptrs(self.desc, suns, bulbs)
+        _check(lib().mirt_scene_set_lights(self._h, *ptrs, _stream_ptr(stream)))
 
     def planes(self):
         """mirt_scene_get_planes: every plane as a numpy layouts.PLANE array."""
@@ -419,9 +227,11 @@ class RawConfig:
         return nodes, codes, refs, bounds
 
 
-def _light_dtype():
+def _light_ptrs(desc, suns, bulbs):
+    """The two host pointers of a set_lights call: each array None, or layouts.LIGHT records, as many as the scene has."""
     from . import layouts
-    return layouts.LIGHT
+    arrays = [_records(a, name, layouts.LIGHT, n) for a, name, n in ((suns, "suns", desc.num_suns), (bulbs, "bulbs", desc.num_bulbs))]
+    return [_host_ptr(a) for a in arrays]
 
 
 def _records(a, name, dtype, count):
@@ -443,17 +253,6 @@ def _records(a, name, dtype, count):
 
 def _host_ptr(a):
     return C.c_void_p(a.ctypes.data) if a is not None and a.size else None
-
-
-def _shading_with(sh, fields):
-    """A copy of `sh` with the keyword fields replaced."""
-    out = Shading.from_buffer_copy(bytes(sh))
-    names = dict(Shading._fields_)
-    for k, v in fields.items():
-        if k not in names:
-            raise ValueError(f"{k} is not a shading field; expected one of {sorted(names)}")
-        setattr(out, k, v)
-    return out
 
 
 def make_plane(abcd, mat):
@@ -490,8 +289,9 @@ def part_pixel_xy(params, local):
     return x.value, y.value
 
 
-class MultiGpu:
+class MultiGpu(_Handle):
     """mirt_multi_*: one process, several GPUs, RCCL framebuffer gather (include/mirt.h)."""
+    _destroy = "mirt_multi_destroy"
 
     def __init__(self, stl, ngpu=1, devices=None):
         self._keep = stl
@@ -513,9 +313,8 @@ class MultiGpu:
 
     def set_lights(self, suns=None, bulbs=None):
         """mirt_multi_set_lights: RawConfig.set_lights on every device's scene, for the frames submitted afterwards."""
-        d = self._keep.desc
-        arrays = [_records(a, name, _light_dtype(), n) for a, name, n in ((suns, "suns", d.num_suns), (bulbs, "bulbs", d.num_bulbs))]
-        _check(lib().mirt_multi_set_lights(self._h, _host_ptr(arrays[0]), _host_ptr(arrays[1])))
+        ptrs = _light_ptrs(self._keep.desc, suns, bulbs)
+        _check(lib().mirt_multi_set_lights(self._h, *ptrs))
 
     def set_planes(self, planes, first=0):
         """mirt_multi_set_planes: RawConfig.set_planes on every device's scene, for the frames submitted afterwards."""
@@ -568,17 +367,6 @@ class MultiGpu:
         _check(lib().mirt_multi_get_stats(self._h, part, C.byref(st)))
         return st.as_dict()
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().mirt_multi_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _stream_ptr(stream):
     if stream is None:
@@ -601,27 +389,32 @@ def _ptr(x):
     return C.c_void_p(x.data_ptr()) if x.numel() else None
 
 
-def _tensor(x, name, dtypes, shape=None, numel=None):
-    """ValueError unless x is a contiguous torch tensor of one of the dtypes, of `shape` (a list; None stands for any size, as in
-    [None, 8]) or, without a shape, of `numel` elements in any shape."""
+def _tensors(*specs):
+    """ValueError unless every (x, name, dtypes, want) in turn is a contiguous torch tensor of one of the dtypes (names: _F32, _INT, ...)
+    and, `want` a list, of that shape (None stands for any size, as in [None, 8]) or, `want` a number, of that many elements in any
+    shape.  Returns the (x, name) pairs, which is what _on_device takes."""
     import torch
-    if not isinstance(x, torch.Tensor):
-        raise ValueError(f"{name} must be a torch tensor")
-    if x.dtype not in dtypes:
-        raise ValueError(f"{name} has dtype {x.dtype}; expected one of {[str(d) for d in dtypes]}")
-    if shape is not None:
-        if x.dim() != len(shape) or any(want is not None and have != want for have, want in zip(x.shape, shape)):
-            raise ValueError(f"{name} has shape {list(x.shape)}; expected [{', '.join('n' if k is None else str(k) for k in shape)}]")
-    elif x.numel() != numel:
-        raise ValueError(f"{name} has shape {list(x.shape)}; expected {numel} elements")
-    if not x.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
+    for x, name, dtypes, want in specs:
+        dtypes = [getattr(torch, d) for d in dtypes if hasattr(torch, d)]
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+        if x.dtype not in dtypes:
+            raise ValueError(f"{name} has dtype {x.dtype}; expected one of {[str(d) for d in dtypes]}")
+        if isinstance(want, list):
+            if x.dim() != len(want) or any(k is not None and have != k for have, k in zip(x.shape, want)):
+                raise ValueError(f"{name} has shape {list(x.shape)}; expected [{', '.join('n' if k is None else str(k) for k in want)}]")
+        elif x.numel() != want:
+            raise ValueError(f"{name} has shape {list(x.shape)}; expected {want} elements")
+        if not x.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    return [(x, name) for x, name, _, _ in specs]
 
 
-def _on_device(tensors, device=None):
-    """ValueError unless every (tensor, name) is on cuda device `device` (None: on the device of the first).  Returns its index."""
+def _on_device(tensors, device=None, first=None):
+    """ValueError unless every (tensor, name), the one named `first` ahead of the others, is on cuda device `device` (None: on the
+    device of the first).  Returns its index."""
     import torch
-    for x, name in tensors:
+    for x, name in sorted(tensors, key=lambda t: t[1] != first):
         index = None
         if x.device.type == "cuda":
             index = x.device.index if x.device.index is not None else torch.cuda.current_device()
@@ -631,11 +424,24 @@ def _on_device(tensors, device=None):
     return device
 
 
-def _f32():
+@contextlib.contextmanager
+def _device_and_stream(device, stream):
+    """cuda device `device` current and `stream` (None: the stream current on that device) torch's current stream: what a driver
+    allocates and issues its calls under.  Gives (torch device, stream)."""
     import torch
-    return (torch.float32,)
+    dev = torch.device("cuda", device)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        yield dev, s
 
 
+def _frame(params, width, height, spp):
+    """`params`, or without them the whole width x height frame at `spp`."""
+    return params if params is not None else render_params(width, height, spp)
+
+
+# build_lbvh_karas, render, render_accumulate, finalize and scatter_part check nothing in Python (the library checks what it is
+# given): a frame loop calls them once per frame, and they stay this thin.
 def build_lbvh_karas(raw, morton_bits=30, stream=None):
     """build_lbvh_karas(RawConfig&, int morton_bits = 30), lbvh_builder.cu:401-521.  morton_bits is accepted and
     ignored exactly as in the reference (10 bits per axis are hard-coded there, lbvh_utils.cu:84)."""
@@ -657,7 +463,7 @@ def render_params(width, height, aa, stripe_rows=None, num_parts=1, part=0, coun
 def num_pixels(params):
     n = lib().mirt_render_num_pixels(C.byref(params))
     if n < 0:
-        raise MirtError(3, "bad render parameters")
+        raise MirtError(MIRT_ERR_ARG, "bad render parameters")
     return n
 
 
@@ -668,20 +474,20 @@ def render(d_image, img_width, img_height, aa, raw, d_float=None, params=None, s
     d_float: optional float32 tensor of num_pixels*4 -- the linear sample mean before sRGB/quantisation.
     params : optional RenderParams selecting one part of a striped frame (multi-GPU); default = whole frame.
     Asynchronous on `stream` (default: torch's current stream)."""
-    p = params if params is not None else render_params(img_width, img_height, aa)
+    p = _frame(params, img_width, img_height, aa)
     _check(lib().mirt_render(raw._h, C.byref(p), _ptr(d_image), _ptr(d_float), _stream_ptr(stream)))
 
 
 def render_accumulate(d_accum, img_width, img_height, sample_first, sample_count, raw, params=None, stream=None):
     """render_kernel_atomic_aa, draw.cu:49-92: adds samples [sample_first, sample_first + sample_count) of every pixel to the
     float32 accumulation buffer d_accum (num_pixels * 4, zeroed by the caller before the first call)."""
-    p = params if params is not None else render_params(img_width, img_height, max(sample_first + sample_count, 2))
+    p = _frame(params, img_width, img_height, max(sample_first + sample_count, 2))
     _check(lib().mirt_render_accumulate(raw._h, C.byref(p), _ptr(d_accum), int(sample_first), int(sample_count), _stream_ptr(stream)))
 
 
 def finalize(d_image, d_accum, img_width, img_height, total_samples, params=None, stream=None):
     """finalize_kernel, draw.cu:13-47: mean over total_samples, sRGB, 8-bit with rounding."""
-    p = params if params is not None else render_params(img_width, img_height, max(total_samples, 2))
+    p = _frame(params, img_width, img_height, max(total_samples, 2))
     _check(lib().mirt_finalize(C.byref(p), _ptr(d_accum), int(total_samples), _ptr(d_image), _stream_ptr(stream)))
 
 
@@ -692,19 +498,20 @@ def scatter_part(params, d_part, d_frame, stream=None):
 # ------------------------------------------------------------------------------------------------------
 # Ray queries (mirt_trace_rays / mirt_camera_rays): rays are float32 [n, 8] tensors (MirtRay), hits 4-byte [n, 6] tensors (MirtHit)
 # ------------------------------------------------------------------------------------------------------
-def _hit_dtypes():
-    import torch
-    return tuple(d for d in (torch.float32, torch.int32, getattr(torch, "uint32", None)) if d is not None)
+def _ray_tensors(d_rays, d_hits, *features):
+    """_tensors for a ray tensor, the hit tensor of as many rows and every (tensor, name) of `features`, float32 [n, 8] rows for
+    the same rays.  Returns the number of rays and the (tensor, name) pairs."""
+    tensors = _tensors((d_rays, "d_rays", _F32, [None, 8]))
+    n = d_rays.shape[0]
+    return n, tensors + _tensors((d_hits, "d_hits", _HIT, [n, 6]), *((x, name, _F32, [n, 8]) for x, name in features))
 
 
 def trace_rays(raw, d_rays, d_hits, any_hit=False, stream=None):
     """mirt_trace_rays: closest hit (hitNearest, draw.cu:292-318) or, with any_hit, occlusion of every ray of d_rays (float32
     [n, 8], MirtRay rows: pack_rays) into d_hits (a 4-byte dtype, [n, 6], MirtHit rows: unpack_hits).  Both contiguous and on
     the scene's device.  Asynchronous on `stream` (default: torch's current stream)."""
-    _tensor(d_rays, "d_rays", _f32(), [None, 8])
-    n = d_rays.shape[0]
-    _tensor(d_hits, "d_hits", _hit_dtypes(), [n, 6])
-    _on_device(((d_rays, "d_rays"), (d_hits, "d_hits")), raw.device)
+    n, tensors = _ray_tensors(d_rays, d_hits)
+    _on_device(tensors, raw.device)
     _check(lib().mirt_trace_rays(raw._h, _ptr(d_rays), n, _ptr(d_hits), MIRT_QUERY_ANY_HIT if any_hit else 0, _stream_ptr(stream)))
 
 
@@ -712,31 +519,36 @@ def camera_rays(raw, d_rays, img_width, img_height, aa, params=None, stream=None
     """mirt_camera_rays: the primary ray of sample 0 of every pixel of the frame (or of the part `params` selects), in the order
     render writes pixels, into d_rays (float32 [num_pixels, 8], contiguous, on the scene's device).  trace_rays of these rays
     gives the render's primary hits."""
-    p = params if params is not None else render_params(img_width, img_height, aa)
-    _tensor(d_rays, "d_rays", _f32(), [num_pixels(p), 8])
-    _on_device(((d_rays, "d_rays"),), raw.device)
+    p = _frame(params, img_width, img_height, aa)
+    _on_device(_tensors((d_rays, "d_rays", _F32, [num_pixels(p), 8])), raw.device)
     _check(lib().mirt_camera_rays(raw._h, C.byref(p), _ptr(d_rays), _stream_ptr(stream)))
 
 
 # ------------------------------------------------------------------------------------------------------
 # Updates in place (mirt_scene_update_spheres / mirt_scene_update_triangles): new geometry from device tensors
 # ------------------------------------------------------------------------------------------------------
+def _range_call(symbol, raw, d, name, cols, first, stream):
+    """The update and get calls of a range of spheres or triangles: `d` (float32 [n, cols], contiguous, on the scene's device)
+    holds, or receives, the values of primitives first .. first+n-1.  An update takes (pointer, first, n), a get (first, n,
+    pointer)."""
+    _on_device(_tensors((d, name, _F32, [None, cols])), raw.device)
+    f = getattr(lib(), symbol)
+    where = (int(first), d.shape[0], _ptr(d)) if "_get_" in symbol else (_ptr(d), int(first), d.shape[0])
+    _check(f(raw._h, *where, _stream_ptr(stream)))
+
+
 def update_spheres(raw, d_xyzr, first=0, stream=None):
     """mirt_scene_update_spheres: spheres first .. first+n-1 (file order) take cx, cy, cz, r from d_xyzr (float32 [n, 4],
     contiguous, on the scene's device).  Asynchronous on `stream` (default: torch's current stream); the scene is not built
     until the next build_lbvh_karas (n = 0 changes nothing)."""
-    _tensor(d_xyzr, "d_xyzr", _f32(), [None, 4])
-    _on_device(((d_xyzr, "d_xyzr"),), raw.device)
-    _check(lib().mirt_scene_update_spheres(raw._h, _ptr(d_xyzr), int(first), d_xyzr.shape[0], _stream_ptr(stream)))
+    _range_call("mirt_scene_update_spheres", raw, d_xyzr, "d_xyzr", 4, first, stream)
 
 
 def update_triangles(raw, d_verts, first=0, stream=None):
     """mirt_scene_update_triangles: triangles first .. first+n-1 (file order) take p0, p1, p2 from d_verts (float32 [n, 9],
     contiguous, on the scene's device); nor, e1 and e2 are computed on the device as the parser computes them
     (object.cuh:177-191).  Asynchronous on `stream`; the scene is not built until the next build_lbvh_karas."""
-    _tensor(d_verts, "d_verts", _f32(), [None, 9])
-    _on_device(((d_verts, "d_verts"),), raw.device)
-    _check(lib().mirt_scene_update_triangles(raw._h, _ptr(d_verts), int(first), d_verts.shape[0], _stream_ptr(stream)))
+    _range_call("mirt_scene_update_triangles", raw, d_verts, "d_verts", 9, first, stream)
 
 
 def update_sphere_materials(raw, d_mats, first=0, stream=None):
@@ -744,64 +556,43 @@ def update_sphere_materials(raw, d_mats, first=0, stream=None):
     [n, 11]: colour rgb, shininess rgb, trans rgb, ior, roughness -- layouts.MAT's order; contiguous, on the scene's device).
     Asynchronous on `stream` (default: torch's current stream); the scene stays built (n = 0 changes nothing).  The next render
     waits once, on the host, for the update's kernels."""
-    _tensor(d_mats, "d_mats", _f32(), [None, 11])
-    _on_device(((d_mats, "d_mats"),), raw.device)
-    _check(lib().mirt_scene_update_sphere_materials(raw._h, _ptr(d_mats), int(first), d_mats.shape[0], _stream_ptr(stream)))
+    _range_call("mirt_scene_update_sphere_materials", raw, d_mats, "d_mats", 11, first, stream)
 
 
 def update_triangle_materials(raw, d_mats, first=0, stream=None):
     """mirt_scene_update_triangle_materials: update_sphere_materials for triangles first .. first+n-1 (file order)."""
-    _tensor(d_mats, "d_mats", _f32(), [None, 11])
-    _on_device(((d_mats, "d_mats"),), raw.device)
-    _check(lib().mirt_scene_update_triangle_materials(raw._h, _ptr(d_mats), int(first), d_mats.shape[0], _stream_ptr(stream)))
+    _range_call("mirt_scene_update_triangle_materials", raw, d_mats, "d_mats", 11, first, stream)
 
 
 def get_sphere_materials(raw, d_mats, first=0, stream=None):
     """mirt_scene_get_sphere_materials: the materials of spheres first .. first+n-1 into d_mats (float32 [n, 11], contiguous, on
     the scene's device): what update_sphere_materials was given, or the file's values.  Asynchronous on `stream`."""
-    _tensor(d_mats, "d_mats", _f32(), [None, 11])
-    _on_device(((d_mats, "d_mats"),), raw.device)
-    _check(lib().mirt_scene_get_sphere_materials(raw._h, int(first), d_mats.shape[0], _ptr(d_mats), _stream_ptr(stream)))
+    _range_call("mirt_scene_get_sphere_materials", raw, d_mats, "d_mats", 11, first, stream)
 
 
 def get_triangle_materials(raw, d_mats, first=0, stream=None):
     """mirt_scene_get_triangle_materials: get_sphere_materials for triangles first .. first+n-1."""
-    _tensor(d_mats, "d_mats", _f32(), [None, 11])
-    _on_device(((d_mats, "d_mats"),), raw.device)
-    _check(lib().mirt_scene_get_triangle_materials(raw._h, int(first), d_mats.shape[0], _ptr(d_mats), _stream_ptr(stream)))
+    _range_call("mirt_scene_get_triangle_materials", raw, d_mats, "d_mats", 11, first, stream)
 
 
 # ------------------------------------------------------------------------------------------------------
 # Adaptive sampling (mirt_render_accumulate_pixels / mirt_select_pixels / mirt_finalize_counts): accum and accum_sq are float32
 # tensors of num_pixels * 4 elements, counts 4-byte integer tensors of num_pixels, pixel lists int32 / uint32 [n]
 # ------------------------------------------------------------------------------------------------------
-def _int_dtypes():
-    import torch
-    return tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
-
-
 def render_accumulate_pixels(raw, d_accum, img_width, img_height, sample_first, sample_count, pixels=None, d_accum_sq=None, d_counts=None,
                              params=None, stream=None):
     """mirt_render_accumulate_pixels: render_accumulate for the pixels of `pixels` (int32 / uint32 [n], distinct local pixel
     indices, any order; None: every pixel), adding as well the squared samples to d_accum_sq and sample_count to d_counts (both
     optional).  Unlisted pixels are neither traced nor written.  Asynchronous on `stream` (default: torch's current stream)."""
-    p = params if params is not None else render_params(img_width, img_height, max(sample_first + sample_count, 2))
+    p = _frame(params, img_width, img_height, max(sample_first + sample_count, 2))
     n = num_pixels(p)
-    _tensor(d_accum, "d_accum", _f32(), numel=4 * n)
-    _on_device(((d_accum, "d_accum"),), raw.device)
-    if d_accum_sq is not None:
-        _tensor(d_accum_sq, "d_accum_sq", _f32(), numel=4 * n)
-        _on_device(((d_accum_sq, "d_accum_sq"),), raw.device)
-    if d_counts is not None:
-        _tensor(d_counts, "d_counts", _int_dtypes(), numel=n)
-        _on_device(((d_counts, "d_counts"),), raw.device)
-    listed = 0
-    if pixels is not None:
-        _tensor(pixels, "pixels", _int_dtypes(), [None])
-        _on_device(((pixels, "pixels"),), raw.device)
-        listed = pixels.shape[0]
-        if listed == 0:      # (an empty tensor has no address to pass: an empty list renders nothing)
-            return
+    _on_device(_tensors((d_accum, "d_accum", _F32, 4 * n)), raw.device)
+    for spec in ((d_accum_sq, "d_accum_sq", _F32, 4 * n), (d_counts, "d_counts", _INT, n), (pixels, "pixels", _INT, [None])):
+        if spec[0] is not None:      # (one at a time, its device included, before the next)
+            _on_device(_tensors(spec), raw.device)
+    listed = pixels.shape[0] if pixels is not None else 0
+    if pixels is not None and listed == 0:      # (an empty tensor has no address to pass: an empty list renders nothing)
+        return
     _check(lib().mirt_render_accumulate_pixels(raw._h, C.byref(p), _ptr(pixels), listed, _ptr(d_accum), _ptr(d_accum_sq), _ptr(d_counts),
                                                int(sample_first), int(sample_count), _stream_ptr(stream)))
 
@@ -812,14 +603,10 @@ def select_pixels(d_accum, d_accum_sq, d_counts, img_width, img_height, min_samp
     variance of the mean exceeds max_variance, in increasing order, into d_pixels_out (int32 / uint32 [num_pixels]); their number
     into d_num_out (one 4-byte integer).  All tensors on the device of d_accum.  Asynchronous on `stream`."""
     import torch
-    p = params if params is not None else render_params(img_width, img_height, 2)
+    p = _frame(params, img_width, img_height, 2)
     n = num_pixels(p)
-    _tensor(d_accum, "d_accum", _f32(), numel=4 * n)
-    _tensor(d_accum_sq, "d_accum_sq", _f32(), numel=4 * n)
-    _tensor(d_counts, "d_counts", _int_dtypes(), numel=n)
-    _tensor(d_pixels_out, "d_pixels_out", _int_dtypes(), numel=n)
-    _tensor(d_num_out, "d_num_out", _int_dtypes(), numel=1)
-    device = _on_device(((d_accum, "d_accum"), (d_accum_sq, "d_accum_sq"), (d_counts, "d_counts"), (d_pixels_out, "d_pixels_out"), (d_num_out, "d_num_out")))
+    device = _on_device(_tensors((d_accum, "d_accum", _F32, 4 * n), (d_accum_sq, "d_accum_sq", _F32, 4 * n), (d_counts, "d_counts", _INT, n),
+                                 (d_pixels_out, "d_pixels_out", _INT, n), (d_num_out, "d_num_out", _INT, 1)))
     with torch.cuda.device(device):
         _check(lib().mirt_select_pixels(C.byref(p), _ptr(d_accum), _ptr(d_accum_sq), _ptr(d_counts), int(min_samples), int(max_samples),
                                         float(max_variance), _ptr(d_pixels_out), _ptr(d_num_out), _stream_ptr(stream)))
@@ -828,12 +615,9 @@ def select_pixels(d_accum, d_accum_sq, d_counts, img_width, img_height, min_samp
 def finalize_counts(d_image, d_accum, d_counts, img_width, img_height, params=None, stream=None):
     """mirt_finalize_counts: finalize with d_counts[pixel] as each pixel's number of samples (0: a zero pixel)."""
     import torch
-    p = params if params is not None else render_params(img_width, img_height, 2)
+    p = _frame(params, img_width, img_height, 2)
     n = num_pixels(p)
-    _tensor(d_image, "d_image", (torch.uint8,), numel=4 * n)
-    _tensor(d_accum, "d_accum", _f32(), numel=4 * n)
-    _tensor(d_counts, "d_counts", _int_dtypes(), numel=n)
-    device = _on_device(((d_accum, "d_accum"), (d_image, "d_image"), (d_counts, "d_counts")))
+    device = _on_device(_tensors((d_image, "d_image", _U8, 4 * n), (d_accum, "d_accum", _F32, 4 * n), (d_counts, "d_counts", _INT, n)), first="d_accum")
     with torch.cuda.device(device):
         _check(lib().mirt_finalize_counts(C.byref(p), _ptr(d_accum), _ptr(d_counts), _ptr(d_image), _stream_ptr(stream)))
 
@@ -847,11 +631,9 @@ def render_adaptive(raw, width, height, min_spp, max_spp, step, max_variance, pa
     import torch
     if min_spp < 2 or max_spp < min_spp or step < 1:
         raise ValueError("render_adaptive needs 2 <= min_spp <= max_spp and step >= 1")
-    p = params if params is not None else render_params(width, height, max(max_spp, 2))
+    p = _frame(params, width, height, max(max_spp, 2))
     n = num_pixels(p)
-    dev = torch.device("cuda", raw.device)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-    with torch.cuda.device(dev), torch.cuda.stream(s):
+    with _device_and_stream(raw.device, stream) as (dev, s):
         accum = torch.zeros(4 * n, dtype=torch.float32, device=dev)
         accum_sq = torch.zeros(4 * n, dtype=torch.float32, device=dev)
         counts = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -874,28 +656,28 @@ def render_adaptive(raw, width, height, min_spp, max_spp, step, max_variance, pa
 # ------------------------------------------------------------------------------------------------------
 # Denoising (mirt_hit_features / mirt_denoise): features are float32 [n, 8] tensors, (Px, Py, Pz, hit, nx, ny, nz, 0) per ray
 # ------------------------------------------------------------------------------------------------------
-# Defaults of the filter's three scales, MIRT_DENOISE_SIGMA_* of include/mirt.h (DESIGN.md section 6f has the table of mean squared
-# errors against converged frames they were chosen from)
-DENOISE_SIGMA_C = 1.0
-DENOISE_SIGMA_N = 0.03
-DENOISE_SIGMA_P = 0.1
+# Defaults of the filter's three scales
+DENOISE_SIGMA_C, DENOISE_SIGMA_N, DENOISE_SIGMA_P = MIRT_DENOISE_SIGMA_C, MIRT_DENOISE_SIGMA_N, MIRT_DENOISE_SIGMA_P
 
 
 def hit_features(raw, d_rays, d_hits, d_features, stream=None):
     """mirt_hit_features: rays (float32 [n, 8]) and their closest-hit records (a 4-byte dtype, [n, 6]) -> d_features (float32
     [n, 8]): hit point and hit flag, normal and 0; a miss gives a zero row.  All contiguous and on the scene's device.
     Asynchronous on `stream` (default: torch's current stream)."""
-    _tensor(d_rays, "d_rays", _f32(), [None, 8])
-    n = d_rays.shape[0]
-    _tensor(d_hits, "d_hits", _hit_dtypes(), [n, 6])
-    _tensor(d_features, "d_features", _f32(), [n, 8])
-    _on_device(((d_rays, "d_rays"), (d_hits, "d_hits"), (d_features, "d_features")), raw.device)
+    n, tensors = _ray_tensors(d_rays, d_hits, (d_features, "d_features"))
+    _on_device(tensors, raw.device)
     _check(lib().mirt_hit_features(raw._h, _ptr(d_rays), _ptr(d_hits), n, _ptr(d_features), _stream_ptr(stream)))
+
+
+def _sigmas(**sigmas):
+    for name, s in sigmas.items():
+        if not (0.0 < float(s) < float("inf")):
+            raise ValueError(f"{name} is {s}; expected a finite positive number")
 
 
 def denoise_work_bytes(img_width, img_height, params=None):
     """mirt_denoise_work_bytes: the bytes of workspace a denoise call of this frame needs (40 per pixel; host arithmetic)."""
-    p = params if params is not None else render_params(img_width, img_height, 2)
+    p = _frame(params, img_width, img_height, 2)
     return int(lib().mirt_denoise_work_bytes(C.byref(p)))
 
 
@@ -907,26 +689,27 @@ def denoise(d_out, d_accum, d_accum_sq, d_counts, d_features, img_width, img_hei
     8-bit image of it; d_work is a float32 tensor of denoise_work_bytes / 4 elements that no other call in flight uses.  All
     tensors contiguous, on one device, and distinct.  Asynchronous on `stream`."""
     import torch
-    p = params if params is not None else render_params(img_width, img_height, 2)
+    p = _frame(params, img_width, img_height, 2)
     if p.num_parts != 1:
         raise ValueError("denoise works on whole frames: params.num_parts must be 1")
     n = num_pixels(p)
-    _tensor(d_out, "d_out", _f32(), numel=4 * n)
-    _tensor(d_accum, "d_accum", _f32(), numel=4 * n)
-    _tensor(d_accum_sq, "d_accum_sq", _f32(), numel=4 * n)
-    _tensor(d_counts, "d_counts", _int_dtypes(), numel=n)
-    _tensor(d_features, "d_features", _f32(), [n, 8])
-    _tensor(d_work, "d_work", _f32(), numel=10 * n)
+    tensors = _tensors((d_out, "d_out", _F32, 4 * n), (d_accum, "d_accum", _F32, 4 * n), (d_accum_sq, "d_accum_sq", _F32, 4 * n), (d_counts, "d_counts", _INT, n),
+                       (d_features, "d_features", _F32, [n, 8]), (d_work, "d_work", _F32, 10 * n))
     if not 0 <= int(iterations) <= 8:
         raise ValueError(f"iterations is {iterations}; expected 0..8")
-    for s, name in ((sigma_c, "sigma_c"), (sigma_n, "sigma_n"), (sigma_p, "sigma_p")):
-        if not (0.0 < float(s) < float("inf")):
-            raise ValueError(f"{name} is {s}; expected a finite positive number")
-    device = _on_device(((d_accum, "d_accum"), (d_out, "d_out"), (d_accum_sq, "d_accum_sq"), (d_counts, "d_counts"), (d_features, "d_features"),
-                         (d_work, "d_work")))
+    _sigmas(sigma_c=sigma_c, sigma_n=sigma_n, sigma_p=sigma_p)
+    device = _on_device(tensors, first="d_accum")
     with torch.cuda.device(device):
         _check(lib().mirt_denoise(C.byref(p), _ptr(d_accum), _ptr(d_accum_sq), _ptr(d_counts), _ptr(d_features), int(iterations), float(sigma_c),
                                   float(sigma_n), float(sigma_p), _ptr(d_work), _ptr(d_out), _stream_ptr(stream)))
+
+
+def _primary_features(raw, params, rays, hits, features, stream):
+    """camera_rays of the frame `params` describes -> trace_rays -> hit_features, into the caller's buffers.  params.spp decides
+    which rays these are (mirt_camera_rays: un-jittered for 0, each pixel's own jitter above 1)."""
+    camera_rays(raw, rays, params.width, params.height, params.spp, params=params, stream=stream)
+    trace_rays(raw, rays, hits, stream=stream)
+    hit_features(raw, rays, hits, features, stream=stream)
 
 
 def denoise_frame(raw, accum, accum_sq, counts, width, height, spp, iterations=5, sigma_c=DENOISE_SIGMA_C, sigma_n=DENOISE_SIGMA_N,
@@ -937,18 +720,14 @@ def denoise_frame(raw, accum, accum_sq, counts, width, height, spp, iterations=5
     import torch
     p = render_params(width, height, max(spp, 2))      # (the seeding of render_accumulate's samples, whatever their number)
     n = num_pixels(p)
-    dev = torch.device("cuda", raw.device)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-    with torch.cuda.device(dev), torch.cuda.stream(s):
+    with _device_and_stream(raw.device, stream) as (dev, s):
         rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
         hits = torch.empty((n, 6), dtype=torch.int32, device=dev)
         features = torch.empty((n, 8), dtype=torch.float32, device=dev)
         work = torch.empty(10 * n, dtype=torch.float32, device=dev)
         out = torch.empty(4 * n, dtype=torch.float32, device=dev)
         image = torch.empty(4 * n, dtype=torch.uint8, device=dev)
-        camera_rays(raw, rays, width, height, p.spp, params=p, stream=s)
-        trace_rays(raw, rays, hits, stream=s)
-        hit_features(raw, rays, hits, features, stream=s)
+        _primary_features(raw, p, rays, hits, features, s)
         denoise(out, accum, accum_sq, counts, features, width, height, work, iterations, sigma_c, sigma_n, sigma_p, params=p, stream=s)
         finalize(image, out, width, height, 1, params=p, stream=s)
     return image, out
@@ -960,35 +739,22 @@ def get_spheres(raw, d_xyzr, first=0, stream=None):
     """mirt_scene_get_spheres: cx, cy, cz, r of spheres first .. first+n-1 (file order) into d_xyzr (float32 [n, 4], contiguous,
     on the scene's device): what update_spheres was given, or the file's values.  Asynchronous on `stream`; the scene stays as
     built as it was."""
-    _tensor(d_xyzr, "d_xyzr", _f32(), [None, 4])
-    _on_device(((d_xyzr, "d_xyzr"),), raw.device)
-    _check(lib().mirt_scene_get_spheres(raw._h, int(first), d_xyzr.shape[0], _ptr(d_xyzr), _stream_ptr(stream)))
+    _range_call("mirt_scene_get_spheres", raw, d_xyzr, "d_xyzr", 4, first, stream)
 
 
 def get_triangles(raw, d_verts, first=0, stream=None):
     """mirt_scene_get_triangles: p0, p1, p2 of triangles first .. first+n-1 (file order) into d_verts (float32 [n, 9], contiguous,
     on the scene's device).  Asynchronous on `stream`; the scene stays as built as it was."""
-    _tensor(d_verts, "d_verts", _f32(), [None, 9])
-    _on_device(((d_verts, "d_verts"),), raw.device)
-    _check(lib().mirt_scene_get_triangles(raw._h, int(first), d_verts.shape[0], _ptr(d_verts), _stream_ptr(stream)))
+    _range_call("mirt_scene_get_triangles", raw, d_verts, "d_verts", 9, first, stream)
 
 
 def prev_features(raw, d_rays, d_hits, d_features, d_prev_xyzr=None, d_prev_verts=None, stream=None):
     """mirt_prev_features: hit_features' rows with the hit point and normal as they were in the previous geometry: d_prev_xyzr
     (float32 [num_spheres, 4]) and d_prev_verts (float32 [num_triangles, 9]) are get_spheres / get_triangles of the whole scene
     before it moved; None: that kind did not move.  All contiguous and on the scene's device.  Asynchronous on `stream`."""
-    _tensor(d_rays, "d_rays", _f32(), [None, 8])
-    n = d_rays.shape[0]
-    _tensor(d_hits, "d_hits", _hit_dtypes(), [n, 6])
-    _tensor(d_features, "d_features", _f32(), [n, 8])
-    tensors = [(d_rays, "d_rays"), (d_hits, "d_hits"), (d_features, "d_features")]
-    if d_prev_xyzr is not None:
-        _tensor(d_prev_xyzr, "d_prev_xyzr", _f32(), [raw.desc.num_spheres, 4])
-        tensors.append((d_prev_xyzr, "d_prev_xyzr"))
-    if d_prev_verts is not None:
-        _tensor(d_prev_verts, "d_prev_verts", _f32(), [raw.desc.num_triangles, 9])
-        tensors.append((d_prev_verts, "d_prev_verts"))
-    _on_device(tensors, raw.device)
+    n, tensors = _ray_tensors(d_rays, d_hits, (d_features, "d_features"))
+    previous = ((d_prev_xyzr, "d_prev_xyzr", _F32, [raw.desc.num_spheres, 4]), (d_prev_verts, "d_prev_verts", _F32, [raw.desc.num_triangles, 9]))
+    _on_device(tensors + _tensors(*(spec for spec in previous if spec[0] is not None)), raw.device)
     _check(lib().mirt_prev_features(raw._h, _ptr(d_rays), _ptr(d_hits), n, _ptr(d_prev_xyzr), _ptr(d_prev_verts), _ptr(d_features), _stream_ptr(stream)))
 
 
@@ -1005,7 +771,7 @@ def temporal_accumulate(d_out_accum, d_out_accum_sq, d_out_counts, d_accum, d_ac
     surface point was, into d_out_*.  An output may be its own current-frame tensor (in place); no other overlap.  All tensors
     contiguous and on one device.  Asynchronous on `stream`."""
     import torch
-    p = params if params is not None else render_params(img_width, img_height, 2)
+    p = _frame(params, img_width, img_height, 2)
     if p.num_parts != 1:
         raise ValueError("temporal_accumulate works on whole frames: params.num_parts must be 1")
     n = num_pixels(p)
@@ -1013,22 +779,16 @@ def temporal_accumulate(d_out_accum, d_out_accum_sq, d_out_counts, d_accum, d_ac
                (d_hist_accum, "d_hist_accum"), (d_hist_accum_sq, "d_hist_accum_sq"))
     counts = ((d_out_counts, "d_out_counts"), (d_counts, "d_counts"), (d_hist_counts, "d_hist_counts"))
     feats = ((d_prev_features, "d_prev_features"), (d_hist_features, "d_hist_features"))
-    for x, name in moments:
-        _tensor(x, name, _f32(), numel=4 * n)
-    for x, name in counts:
-        _tensor(x, name, _int_dtypes(), numel=n)
-    for x, name in feats:
-        _tensor(x, name, _f32(), [n, 8])
+    tensors = _tensors(*[(x, name, _F32, 4 * n) for x, name in moments], *[(x, name, _INT, n) for x, name in counts],
+                       *[(x, name, _F32, [n, 8]) for x, name in feats])
     if not isinstance(prev_camera, Camera):
         raise ValueError("prev_camera must be a Camera")
     if not _is_pinhole(prev_camera):
         raise ValueError("prev_camera must be a pinhole: fisheye, panorama and dof_focus 0")
     if int(max_history) < 1:
         raise ValueError(f"max_history is {max_history}; expected at least 1")
-    for s, name in ((sigma_n, "sigma_n"), (sigma_p, "sigma_p")):
-        if not (0.0 < float(s) < float("inf")):
-            raise ValueError(f"{name} is {s}; expected a finite positive number")
-    device = _on_device(((d_accum, "d_accum"),) + moments + counts + feats)
+    _sigmas(sigma_n=sigma_n, sigma_p=sigma_p)
+    device = _on_device(tensors, first="d_accum")
     with torch.cuda.device(device):
         _check(lib().mirt_temporal_accumulate(C.byref(p), C.byref(prev_camera), _ptr(d_accum), _ptr(d_accum_sq), _ptr(d_counts), _ptr(d_prev_features),
                                               _ptr(d_hist_accum), _ptr(d_hist_accum_sq), _ptr(d_hist_counts), _ptr(d_hist_features), int(max_history),
@@ -1087,21 +847,18 @@ class TemporalAccumulator:
         renderer's limit of 4096 sample indices (after 4096 // spp frames a frame repeats the samples of an earlier one, long
         after max_history has scaled that one away).  Returns (rgba8 uint8 [num_pixels * 4], accum, accum_sq, counts): the image
         and the merged moments, which are the history of the next frame -- they stay valid until the frame after that."""
-        import torch
-        raw, w, h, p, n = self.raw, self.width, self.height, self.params, self.n
+        raw, w, h, p = self.raw, self.width, self.height, self.params
         cam = raw.camera()
         if not _is_pinhole(cam):
             raise ValueError("TemporalAccumulator needs a pinhole camera: fisheye, panorama and dof_focus 0")
-        s = self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
         first = (self.frame_index * self.spp) % (4096 // self.spp * self.spp)
         S, Q, k = self.cur
         old, new = self.slot, 1 - self.slot
-        with torch.cuda.device(self.device), torch.cuda.stream(s):
+        with _device_and_stream(raw.device, self.stream) as (_, s):
             S.zero_(); Q.zero_(); k.zero_()
             render_accumulate_pixels(raw, S, w, h, first, self.spp, None, Q, k, params=p, stream=s)
-            camera_rays(raw, self.rays, w, h, 0, params=render_params(w, h, 0), stream=s)
-            trace_rays(raw, self.rays, self.hits, stream=s)
-            hit_features(raw, self.rays, self.hits, self.features[new], stream=s)
+            # (the un-jittered rays through the pixel centres, not the jittered ones denoise_frame takes: reprojection inverts them)
+            _primary_features(raw, render_params(w, h, 0), self.rays, self.hits, self.features[new], s)
             oS, oQ, ok = self.hist[new]
             if self.have_history:
                 prev_features(raw, self.rays, self.hits, self.reprojected, self.prev_xyzr if self.prev_xyzr.shape[0] else None,

@@ -152,6 +152,12 @@ class RawConfig(_Handle):
         _check(lib().mirt_scene_get_option(self._h, name.encode(), C.byref(v)))
         return v.value
 
+    def stack_info(self):
+        """The read-only facts of mirt_scene_get_option about the traversal stack: {"tree_depth": D of the built tree,
+        "lds_capacity": stack entries held without spilling, "lds_only": the last render ran the trace kernel without a spill path}."""
+        return {"tree_depth": self.get_option("tree_depth"), "lds_capacity": self.get_option("stack_lds_capacity"),
+                "lds_only": bool(self.get_option("stack_lds_only"))}
+
     def camera(self):
         """mirt_scene_get_camera: the scene's camera as a Camera."""
         cam = Camera()

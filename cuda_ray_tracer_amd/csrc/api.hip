@@ -95,6 +95,10 @@ int mirt_scene_get_option(const MirtScene* sc, const char* name, int* value)
   if (!sc || !name || !value) { set_error("mirt_scene_get_option: null argument"); return MIRT_ERR_ARG; }
   for (const OptionDesc& d : OPTIONS)
     if (strcmp(d.name, name) == 0) { *value = sc->opt.*(d.field); return MIRT_OK; }
+  // read-only facts about the traversal stack (mirt.h): the built tree's depth, and which kernel the last render's plan chose
+  if (strcmp(name, "tree_depth") == 0) { *value = sc->built ? sc->tree_depth : -1; return MIRT_OK; }
+  if (strcmp(name, "stack_lds_capacity") == 0) { *value = STACK_LDS_CAPACITY; return MIRT_OK; }
+  if (strcmp(name, "stack_lds_only") == 0) { *value = sc->last_lds_only ? 1 : 0; return MIRT_OK; }
   set_error(std::string("mirt_scene_get_option: unknown option ") + name);
   return MIRT_ERR_ARG;
 }
@@ -209,6 +213,7 @@ int scene_create(const MirtSceneDesc* d, int device, MirtScene** out)
     MIRT_TRY(sc->tris_before.alloc(n + 1, "tris_before"));
   }
   MIRT_TRY(sc->bounds_keys.alloc(6, "bounds_keys"));
+  MIRT_TRY(sc->depth_dev.alloc(1, "depth_dev"));
   MIRT_TRY(sc->qparams.alloc(9, "qparams"));
   MIRT_TRY(sc->tri_boxes.alloc(2 * (size_t)sc->Nt, "tri_boxes"));
   for (RenderCtx& c : sc->ctx) {

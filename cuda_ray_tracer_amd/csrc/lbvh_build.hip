@@ -482,6 +482,23 @@ __global__ void __launch_bounds__(BLOCK) scatter_prims_kernel(int n, const uint3
   }
 }
 
+// D, the most internal nodes on a root-to-leaf path: one thread per leaf counts the parent links up to the root, one atomic
+// per wave.  It bounds the stack of a binary walk (render.hip, MIRT_PUSH), so the render plan can pick a kernel whose stack
+// never leaves LDS.  (A link that was never written is -1 like the root's: the count stops there.  The tree is at most 58
+// levels deep; the cap only bounds the loop.)
+__global__ void __launch_bounds__(BLOCK) tree_depth_kernel(int n, const int* __restrict__ parent, uint32_t* __restrict__ depth)
+{
+  const int j = blockIdx.x * BLOCK + threadIdx.x;
+  uint32_t d = 0;
+  if (j < n) {
+    int p = parent[n - 1 + j];
+    while (p >= 0 && p < n - 1 && d < 255u) { ++d; p = parent[p]; }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) d = max(d, (uint32_t)__shfl_xor((int)d, off));
+  if ((threadIdx.x & 63) == 0 && d > 0) atomicMax(depth, d);
+}
+
 // set_aabb_kernel_adapted, lbvh_builder.cu:324-387.  One thread per leaf; the second thread to arrive at a parent
 // merges the children.  The box stores are published before the arrival counter is bumped, see below (the reference
 // has no fence there).  The merging thread also writes the parent's packed traversal record.
@@ -565,7 +582,8 @@ int build_lbvh(MirtScene* sc, hipStream_t stream)
   const int n = sc->N;
   sc->built = false;
   sc->root_ref = REF_NONE;
-  if (n == 0) { sc->built = true; sc->build_ms = 0.0f; return MIRT_OK; }   // main.cu:44: build skipped when there are no primitives
+  sc->tree_depth = -1;
+  if (n == 0) { sc->built = true; sc->build_ms = 0.0f; sc->tree_depth = 0; return MIRT_OK; }   // main.cu:44: build skipped when there are no primitives
 
   // sort / refit workspace: one allocation, made before the timed region and kept with the scene (a rebuild reuses it)
   const int sblocks = (n + SORT_TILE - 1) / SORT_TILE;
@@ -608,6 +626,9 @@ int build_lbvh(MirtScene* sc, hipStream_t stream)
     MIRT_HIP(hipMemsetAsync(sc->parent, 0xff, sizeof(int) * (2 * (size_t)n - 1), stream));
     const int kblk = (n - 1 + BLOCK - 1) / BLOCK;
     hipLaunchKernelGGL(karras_kernel, dim3(kblk), dim3(BLOCK), 0, stream, sc->codes, n, sc->child_l, sc->child_r, sc->parent, sc->range);
+    // the tree's depth, for the render plan (every build: a rebuild changes the topology)
+    MIRT_HIP(hipMemsetAsync(sc->depth_dev, 0, sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(tree_depth_kernel, dim3(nblk), dim3(BLOCK), 0, stream, n, sc->parent, sc->depth_dev);
   } else {
     MIRT_HIP(hipMemsetAsync(sc->parent, 0xff, sizeof(int), stream));
   }
@@ -647,7 +668,11 @@ int build_lbvh(MirtScene* sc, hipStream_t stream)
   // the test -- one that sits far from the world origin compared with its size -- is walked over the exact records.
   sc->coord_max = 0.0f;
   sc->grid_ok = false;
+  sc->tree_depth = 0;      // (a single primitive: no internal node)
   if (n > 1) {
+    uint32_t depth = 0;
+    MIRT_HIP(hipMemcpy(&depth, sc->depth_dev, sizeof(depth), hipMemcpyDeviceToHost));
+    sc->tree_depth = (int)depth;
     float rec[12];      // left x, y | left z, right x | right y, z  (min, max pairs)
     MIRT_HIP(hipMemcpy(rec, sc->nodes, sizeof(rec), hipMemcpyDeviceToHost));
     for (float v : rec) sc->coord_max = fmaxf(sc->coord_max, fabsf(v));

@@ -65,12 +65,18 @@ MIRT_DEV bool triangle_leaf_reached(const RenderArgs* __restrict__ ap, uint32_t 
 // again, triangle_leaf_reached); then S.inv holds 1 / d.
 // With QN on a scene that has triangles the quantised records are the wide ones (WIDE, scene_dev.h): a step tests the boxes of
 // the node's four grandchildren and descends two levels.
+// SPECX & SPEC_LDS_STACK: the traversal stack never leaves LDS -- push and pop have no arm for the global spill area, and an
+// empty stack is a REF_NONE at its bottom, not a count of zero.  Selected by the plan (render_plan.h, lds_only) for a binary
+// walk over a tree whose depth proves that the entries fit; see MIRT_PUSH below.
+constexpr int SPEC_LDS_STACK = 8;
 template <bool COUNT, int TABLES, bool QN, int SPECX = 0>
 __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel(const RenderArgs* __restrict__ ap, const HotArgs h)
 {
-  constexpr int SPEC = SPECX;
+  constexpr int SPEC = SPECX & ~SPEC_LDS_STACK;
+  constexpr bool LDS_ONLY = (SPECX & SPEC_LDS_STACK) != 0;
   constexpr bool NOTRI = (SPEC & SPEC_NOTRI) != 0;
   constexpr bool WIDE = QN && !NOTRI;
+  static_assert(!(LDS_ONLY && WIDE), "the wide walk pushes up to three entries per step: the depth of the tree does not bound its stack");
   // a finished shadow ray towards a point light that hit something, in a walk that is not the reference's own: the hit is vetted
   // by the shade phase before batch_next reads "occluded" off it (hit_needs_literal_walk); no such lanes in a kernel without bulbs
 #define MIRT_HELD (QN && !(SPEC & SPEC_NOBULB) && h.reach_check && S.batch_pending && !S.trav && S.li >= h.num_suns && S.li < h.num_suns + h.num_bulbs && \
@@ -130,6 +136,9 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
     // (the lanes vetted are exactly those the loop below lets advance() consume: none is looked at twice)
     // (a batch lane: its reflection ray, or a shadow ray towards a point light -- one that hit something is left to this phase
     // by the traversal loop's header, MIRT_HELD)
+    // (LDS_ONLY: every ray this phase starts finds the empty stack's REF_NONE on top -- the lanes that may start one are those
+    // that are not traversing now; a ray that ended on an any-hit exit left its entries behind)
+    if (LDS_ONLY && !S.trav) S.tos = REF_NONE;
     if (a.reach_check && !S.trav && S.g >= 0 && !(exhausted && S.batch_pending && !MIRT_HELD) && (!S.batch_pending || S.li >= a.num_suns)) {
       if (hit_needs_literal_walk<QN>(a, S)) walk_literally<COUNT, NOTRI>(a, S, cn, gid, gthreads);
     }
@@ -225,7 +234,26 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
       if (nwait >= h.refill_k || (drain && nwait > 0)) break;
       // lanes whose batch ray finished move on to the next ray of their batch (cheap; done in groups)
       if (bm != 0 && (__popcll(bm) >= h.batch_k || tm == 0 || drain)) {
-        if (pend) batch_next<COUNT, QN, HotArgs, SPEC>(h, S, cn);
+        if (LDS_ONLY) {
+          // This kernel keeps only the arm's data pointers that are read through (planes, the records' grid) in scalar registers.
+          // The values the arm merely looks at -- the root reference, the counts of planes and lights, the shadow-ray mode -- and
+          // the light array's address are read where the arm runs, through the same opaque pointer as the shade phase: four
+          // scalar loads issued together, one level deep.  Passed by value they, and the loop-invariant conditions the compiler
+          // derives from them, did not fit the scalar registers across the traversal loop and were reloaded from spill lanes in
+          // every execution of the arm.  (All of them read through the pointer, planes and grid included, is two dependent loads
+          // deep and was measured slower than the reloads: DESIGN.md section 4.)
+          if (pend) {
+            const RenderArgs* hq = ap;
+            asm volatile("" : "+s"(hq));
+            HotArgs hh = h;
+            hh.suns = hq->suns; hh.root_ref = hq->root_ref; hh.num_planes = hq->num_planes; hh.num_suns = hq->num_suns; hh.num_bulbs = hq->num_bulbs;
+            hh.shadow_anyhit = hq->shadow_anyhit;
+            batch_next<COUNT, QN, HotArgs, SPEC>(hh, S, cn);
+            S.tos = REF_NONE;      // (the next ray's empty stack)
+          }
+        } else {
+          if (pend) batch_next<COUNT, QN, HotArgs, SPEC>(h, S, cn);
+        }
       }
       // A wave executes the node path and the primitive path one after the other whenever its lanes are split between
       // them, and with ~45 live lanes nearly every iteration has a lane or two at a primitive.  So lanes that reach a
@@ -236,7 +264,11 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
       const bool do_leaf0 = __popcll(lm) >= h.leaf_k || __ballot(S.trav && !leaf0) == 0 || drain;
       // `reps` steps per pass through the header above: the bookkeeping is amortised; a lane whose ray ends in the first
       // step idles through the others, and a primitive reached in a later step waits for the next pass
-      for (int rep = 0; rep < h.reps; ++rep) {
+      // (LDS_ONLY: the count is made opaque here, so that what the compiler derives from it for the loop below -- the count less
+      // the peeled first step -- is computed per pass and not kept, in a spilled scalar register, across the kernel)
+      int reps = h.reps;
+      if (LDS_ONLY) asm volatile("" : "+s"(reps));
+      for (int rep = 0; rep < reps; ++rep) {
       const bool leaf = S.trav && (S.cur & REF_LEAF) != 0;
       const bool do_leaf = rep == 0 && do_leaf0;
       if (S.trav && (!leaf || do_leaf)) {
@@ -292,7 +324,15 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
           // push `v`: the previous top of stack goes to memory, the new top stays in a register.  With n entries on the stack,
           // entry k < n sits in slot k and entry n is S.tos (slot 0 only ever receives the dead S.tos of an empty stack), so
           // the slot to write is simply the current depth.
-#define MIRT_PUSH(v) do { if (S.sp < h.lds_depth) lds_stack[S.sp * TRACE_BLOCK + tid] = S.tos; \
+          // Capacity without the spill area: pushes at depths 0 .. lds_depth - 1 stay in LDS, so lds_depth entries -- the top in
+          // S.tos, entries 1 .. lds_depth - 1 in the slots of their number.  STACK_LDS_CAPACITY (render_plan.h) is that with
+          // lds_depth = STACK_LDS, all the slots there are.
+          // LDS_ONLY: the plan has shown that the entries fit.  This binary walk pushes at most one sibling per internal node on
+          // the path from the root to the current node and pops it before it leaves that node's subtree, so the entries pending
+          // never exceed the internal nodes on that path: at most D, the tree's depth counted in internal nodes (lbvh_build.hip),
+          // and D <= STACK_LDS_CAPACITY.  An empty stack has REF_NONE in S.tos; the first push moves it to slot 0 and the pop
+          // that empties the stack brings it back, so "the popped reference is REF_NONE" ends the walk.
+#define MIRT_PUSH(v) do { if (LDS_ONLY || S.sp < h.lds_depth) lds_stack[S.sp * TRACE_BLOCK + tid] = S.tos; \
                           else h.stack_spill[(size_t)(S.sp - h.lds_depth) * gthreads + gid] = S.tos; \
                           S.tos = (v); ++S.sp; if (COUNT) cn.max_stack = max(cn.max_stack, (uint32_t)S.sp); } while (0)
           if (WIDE && S.qsx != 0u) {
@@ -336,7 +376,8 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
           // (no depth check: the stack cannot outgrow STACK_TOTAL.  A Karras tree over 30-bit codes with the index tie-break of
           // lbvh_builder.cu:76-101 is a radix tree over (code, index) keys of 30 + ceil(log2 N) bits, N < 2^28 (checked at scene
           // creation), so it is at most 58 levels deep, and the walk keeps at most one pending sibling per level.  The
-          // reference's "stack overflow" warning, bvh_traversal.cu:154-164, is unreachable for the same reason.)
+          // reference's "stack overflow" warning, bvh_traversal.cu:154-164, is unreachable for the same reason.  LDS_ONLY: the
+          // same one-sibling-per-level argument with the built tree's own depth D in place of 58, at MIRT_PUSH above.)
           if (both) MIRT_PUSH(rref);
 #undef MIRT_PUSH
           S.cur = hl ? lref : (hr ? rref : S.cur);
@@ -345,11 +386,19 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
         if (pop) {
           // an empty stack ends the traversal; otherwise the top becomes the current node and the new top is reloaded
           // (a dead read of slot 0 when the stack is now empty)
-          S.trav = S.sp != 0;
-          S.cur = S.tos;
-          S.sp = S.sp > 0 ? S.sp - 1 : 0;
-          S.tos = lds_stack[(S.sp < h.lds_depth ? S.sp : 0) * TRACE_BLOCK + tid];
-          if (S.sp >= h.lds_depth) S.tos = h.stack_spill[(size_t)(S.sp - h.lds_depth) * gthreads + gid];
+          if (LDS_ONLY) {
+            // (the walk ends on the REF_NONE below the entries; popping it leaves the depth at zero and reads slot 0 again)
+            S.cur = S.tos;
+            S.trav = S.cur != REF_NONE;
+            S.sp = (int)__builtin_elementwise_sub_sat((uint32_t)S.sp, 1u);
+            S.tos = lds_stack[S.sp * TRACE_BLOCK + tid];
+          } else {
+            S.trav = S.sp != 0;
+            S.cur = S.tos;
+            S.sp = S.sp > 0 ? S.sp - 1 : 0;
+            S.tos = lds_stack[(S.sp < h.lds_depth ? S.sp : 0) * TRACE_BLOCK + tid];
+            if (S.sp >= h.lds_depth) S.tos = h.stack_spill[(size_t)(S.sp - h.lds_depth) * gthreads + gid];
+          }
         }
       }
       }
@@ -621,7 +670,7 @@ static int scene_facts(MirtScene* sc, SceneFacts* out)
   const int rc = settle_facts(sc);
   if (rc != MIRT_OK) return rc;
   SceneFacts f;
-  f.N = sc->N; f.Nt = sc->Nt; f.grid_ok = sc->grid_ok;
+  f.N = sc->N; f.Nt = sc->Nt; f.grid_ok = sc->grid_ok; f.tree_depth = sc->tree_depth;
   f.has_quantised = sc->root_ref_q != REF_NONE; f.has_wide = sc->root_ref_w != REF_NONE;
   f.colors_finite = sc->colors_finite; f.any_trans = sc->any_trans; f.any_rough = sc->any_rough;
   f.gi = sc->d.gi; f.bounces = sc->d.bounces; f.num_suns = sc->d.num_suns; f.num_bulbs = sc->d.num_bulbs;
@@ -844,7 +893,8 @@ static int sample_table_finish(MirtScene* sc, hipStream_t stream)
 }
 
 // one instantiation per form of the random-number tables (device_common.h, xw_init), per node format and per specialisation:
-// 2 (counting) x 2 (tables) x 8 = 32 kernels
+// 2 (counting) x 2 (tables) x 8 = 32 kernels, and the LDS-only stack (SPEC_LDS_STACK) for the five of the eight that walk a
+// binary tree: 20 more
 using TraceKernel = void (*)(const RenderArgs*, HotArgs);
 template <bool C, bool Q, int P>
 static TraceKernel trace_kernel_tables(bool t8) { return t8 ? trace_kernel<C, 8, Q, P> : trace_kernel<C, 4, Q, P>; }
@@ -852,6 +902,11 @@ template <bool C>
 static TraceKernel trace_kernel_spec(bool t8, const CallPlan& pl)
 {
   const bool both = pl.nobulb && pl.nopend;
+  if (pl.lds_only) {
+    constexpr int L = SPEC_LDS_STACK;
+    if (pl.qn) return both ? trace_kernel_tables<C, true, L | SPEC_NOTRI | SPEC_NOBULB | SPEC_NOPEND>(t8) : trace_kernel_tables<C, true, L | SPEC_NOTRI>(t8);      // (the plan: notri)
+    return both ? trace_kernel_tables<C, false, L | SPEC_NOBULB | SPEC_NOPEND>(t8) : pl.nobulb ? trace_kernel_tables<C, false, L | SPEC_NOBULB>(t8) : trace_kernel_tables<C, false, L>(t8);
+  }
   if (pl.qn && pl.notri) return both ? trace_kernel_tables<C, true, SPEC_NOTRI | SPEC_NOBULB | SPEC_NOPEND>(t8) : trace_kernel_tables<C, true, SPEC_NOTRI>(t8);
   if (pl.qn) return both ? trace_kernel_tables<C, true, SPEC_NOBULB | SPEC_NOPEND>(t8) : pl.nobulb ? trace_kernel_tables<C, true, SPEC_NOBULB>(t8) : trace_kernel_tables<C, true, 0>(t8);
   return both ? trace_kernel_tables<C, false, SPEC_NOBULB | SPEC_NOPEND>(t8) : pl.nobulb ? trace_kernel_tables<C, false, SPEC_NOBULB>(t8) : trace_kernel_tables<C, false, 0>(t8);
@@ -969,6 +1024,7 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
   cx.wf_trace_ms = -1.0f;
   cx.launches = pl.nslabs;
   cx.node_bytes = pl.node_bytes;
+  sc->last_lds_only = pl.lds_only;
   MIRT_HIP(hipEventRecord(cx.ev1, stream));
   for (int slab = 0; slab < pl.nslabs; ++slab) {
     const long long p0 = (long long)slab * pl.slab_pixels;

@@ -21,6 +21,9 @@ namespace mirt {
 
 constexpr int TRACE_BLOCK = MIRT_TRACE_BLOCK;
 constexpr int STACK_LDS = MIRT_STACK_LDS;
+// Entries the trace kernel's stack holds without the global spill area: the top entry in a register (Lane::tos) and entries
+// 1 .. STACK_LDS - 1 in LDS slots of the same number.  Slot 0 never holds an entry (render.hip, MIRT_PUSH).
+constexpr int STACK_LDS_CAPACITY = STACK_LDS;
 constexpr int MAX_CHUNK_SHIFT = 8, MIN_CHUNK_SHIFT = 6;   // a wave takes 64..256 consecutive samples from the frame per atomic
 // node record word 14 (after the two child references): which descent orders the node allows
 constexpr uint32_t NODE_SWAP_PURE = 1u;       // both subtrees hold spheres only: near-child-first cannot change the closest hit
@@ -59,6 +62,7 @@ struct SceneFacts {
   bool colors_finite = true, any_trans = false, any_rough = false;
   int gi = 0, bounces = 0;
   int num_suns = 0, num_bulbs = 0;
+  int tree_depth = -1;                     // D: the most internal nodes on a root-to-leaf path of the built tree (lbvh_build.hip); -1: not known
 };
 
 struct CallShape {
@@ -100,6 +104,7 @@ struct CallPlan {
   int skip_unlit = 0, shadow_anyhit = 0;
   // thresholds by kind of kernel
   int refill_k = 0, init_k = 0, leaf_k = 0, reps = 0, lds_depth = 0;
+  bool lds_only = false;                   // the trace kernel compiled without the spill arm of push and pop (SPEC_LDS_STACK)
   HandOut hand_out = HAND_FRAME;
 };
 
@@ -152,6 +157,11 @@ inline CallPlan plan_call(const SceneFacts& s, const Options& opt, const CallSha
   pl.shadow_anyhit = opt.shadow_anyhit != 0 ? 1 : 0;
 
   pl.lds_depth = (opt.stack_lds_depth >= 0 && opt.stack_lds_depth <= STACK_LDS) ? opt.stack_lds_depth : STACK_LDS;   // tests force the spill path
+  // The kernel without a spill arm: a binary walk (the sphere-only quantised records or the exact ones; the wide walk pushes up
+  // to three entries a step) keeps at most one pending sibling per internal node above the current one, so never more than D
+  // entries (render.hip, next to MIRT_PUSH).  Only with the option at its default: any explicit value, the compiled size
+  // included, keeps the general kernel -- that is how the tests force the spill path and how the two kernels are compared.
+  pl.lds_only = !wavefront && opt.stack_lds_depth < 0 && (!pl.qn || pl.notri) && s.tree_depth >= 0 && s.tree_depth <= STACK_LDS_CAPACITY;
   // Thresholds of the two expensive divergent pieces of work, measured per kind of kernel (round 3, tools/r03_i.sh, r03_x.sh): lanes
   // wait to shade until refill_k of them do, lanes without a sample until init_k of them do.  Sphere-only scenes 32 / 10; wide
   // records (2 M-primitive scene) 24 / 8; exact records (redchair.txt) 64 / 64 -- with the samples handed out by cost class

@@ -232,11 +232,14 @@ struct MirtScene {
   mirt::DevBuf<float4> tri_boxes;       // [2 Nt]: exact leaf box of every triangle (scene order), for the quantised walk's triangle check
   mirt::DevBuf<uint32_t> build_ws;      // LBVH build workspace (sort buffers, histograms, arrival counters)
   mirt::DevBuf<uint32_t> bounds_keys;   // [6] ordered-uint min xyz, max xyz
+  mirt::DevBuf<uint32_t> depth_dev;     // [1] the build's max reduction behind tree_depth
   uint32_t root_ref = mirt::REF_NONE;
   bool built = false;
   float build_ms = 0.0f;
   float coord_max = 0.0f;               // largest |coordinate| of the scene box (set by the build)
   bool grid_ok = false;                 // the grid of the quantised records resolves the scene's coordinates (set by the build): they may be walked
+  int tree_depth = -1;                  // D: the most internal nodes on a root-to-leaf path (set by the build; -1: not built).  Bounds the binary walk's stack
+  bool last_lds_only = false;           // the most recent render's plan chose the trace kernel without a stack-spill arm (mirt_scene_get_option, "stack_lds_only")
   // render workspaces: MIRT_MAX_FRAMES contexts so that several frames can be in flight on different streams (the next frame's blocks fill the
   // CUs the draining frame frees); a context is reused only after its previous frame has finished
   mirt::RenderCtx ctx[mirt::MIRT_MAX_FRAMES];

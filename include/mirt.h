@@ -128,7 +128,15 @@ void mirt_scene_destroy(MirtScene* sc);
  *     "wf_pool", "wf_refill_k": tuning (defaults are the measured optima)
  * Environment variables MIRT_<NAME> override the defaults of the TUNING values once, when the scene is created (the mode
  * switches -- bounds_as_shipped, traversal, wavefront, qnodes, shadow_anyhit, skip_unlit -- only with MIRT_ALLOW_ENV=1); nothing
- * reads the environment during a render. */
+ * reads the environment during a render.
+ * mirt_scene_get_option also reads three facts about the traversal stack of the single-kernel path (mirt_scene_set_option does
+ * not know them):
+ *     "tree_depth"         D, the most internal nodes on any root-to-leaf path of the built tree (-1 before a build); every
+ *                          mirt_build_lbvh recomputes it.  A walk over two-child records keeps at most D entries pending
+ *     "stack_lds_capacity" entries the kernel's stack holds before it spills to global memory
+ *     "stack_lds_only"     1 if the most recent render call ran the kernel that has no spill path at all: chosen when
+ *                          D <= stack_lds_capacity, the walk is over two-child records (not the wide ones) and "stack_lds_depth"
+ *                          is at its default, -1 -- any explicit value, the compiled size included, keeps the general kernel */
 #define MIRT_TRAVERSAL_REFERENCE 0
 #define MIRT_TRAVERSAL_ORDERED 1
 #define MIRT_TRAVERSAL_ORDERED_ALL 2

@@ -36,12 +36,14 @@ def _compile(defines):
     return _COMPILED[defines]
 
 
-def analyze(defines=(), kernel="trace_kernelILb0ELi8ELb1ELi7EE"):
+def analyze(defines=(), kernel="trace_kernelILb0ELi8ELb1ELi7EE", also=()):
     """Returns (resources, counts, spills): the kernel's resource usage lines, instruction counts by class inside the
-    traversal loop, and [(position, instruction)] of every spill instruction in it.  `kernel`: the mangled instantiation,
-    trace_kernel<COUNT, TABLES, QN, SPECX>: ...Li8ELb1ELi6EE = byte-indexed RNG tables, quantised nodes, no point lights /
-    transparency / gi (the headline scene's kernel); ...Li8ELb0ELi2EE = 64-byte node records (scenes with triangles), no point
-    lights (redchair.txt); ...Li0EE: the general kernels."""
+    traversal loop, and [(position, instruction)] of every spill instruction in it -- and of every instruction there whose
+    opcode starts with one of `also`.  `kernel`: the mangled instantiation,
+    trace_kernel<COUNT, TABLES, QN, SPECX>: ...Li8ELb1ELi7EE = byte-indexed RNG tables, quantised nodes, no triangles / point
+    lights / transparency / gi (the headline scene's general kernel; ...Li15EE: the same with the LDS-only stack, SPECX + 8, the
+    one the headline runs); ...Li8ELb0ELi2EE = 64-byte node records (scenes with triangles), no point lights (redchair.txt);
+    ...Li0EE: the general kernels."""
     remarks, asm = _compile(tuple(defines))
     res, want = [], False
     for line in remarks.splitlines():
@@ -112,7 +114,7 @@ def analyze(defines=(), kernel="trace_kernelILb0ELi8ELb1ELi7EE"):
         elif op.startswith("s_"): k = "salu"
         else: k = "other"
         cnt[k] += 1
-        if k in ("scratch", "sgpr-spill"):
+        if k in ("scratch", "sgpr-spill") or (also and op.startswith(tuple(also))):
             spills.append((pos, t.split(";")[0].strip()))
     return res, dict(cnt), spills
 

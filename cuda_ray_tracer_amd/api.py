@@ -890,6 +890,10 @@ class TemporalAccumulator:
         return self.image, oS, oQ, ok
 
 
+# Direct light at surface points (include/mirt_light.h): lighting.py holds the extension header's signature and calls
+from .lighting import MIRT_LIGHT_RAW, direct_light, pack_features, direct_light_frame      # noqa: E402,F401
+
+
 def pack_rays(origins, dirs, tmax=float("inf")):
     """float32 [n, 8] MirtRay rows from origins [n, 3] (or [3]), directions [n, 3] (any non-zero length) and tmax (a number or
     [n]), on the directions' device."""

@@ -333,6 +333,14 @@ int mirt_hit_features(MirtScene* sc, const void* d_rays, const void* d_hits, int
   return hit_features(sc, d_rays, d_hits, n, d_features, (hipStream_t)stream);
 }
 
+// (include/mirt_light.h)
+int mirt_direct_light(MirtScene* sc, const void* d_features, int64_t n, void* d_out_f32, uint64_t* d_lit_mask, uint32_t flags, void* stream)
+{
+  if (!sc) { set_error("mirt_direct_light: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return direct_light(sc, d_features, n, d_out_f32, d_lit_mask, flags, (hipStream_t)stream);
+}
+
 size_t mirt_denoise_work_bytes(const MirtRenderParams* p) { return denoise_work_bytes(p); }
 
 int mirt_denoise(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, const void* d_features,

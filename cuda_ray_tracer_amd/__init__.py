@@ -1,6 +1,7 @@
 """cuda_ray_tracer_amd -- MI355X-native LBVH ray tracer (hot path of GJ0407790/cuda_ray_tracer).
 
-Host side: binding.py (include/mirt.h restated for ctypes) and api.py (the calls over it); lighting.py (include/mirt_light.h).
+Host side: binding.py (include/mirt.h restated for ctypes) and api.py (the calls over it); lighting.py (include/mirt_light.h);
+visibility.py (include/mirt_visibility.h).
 Device side: csrc/*.hip, built by build.py into _build/libmirt.so.
 """
 from .api import (MirtError, StlConfig, RawConfig, parseInput, parseText, syntheticScene, initRawConfigFromStl,
@@ -10,7 +11,8 @@ from .api import (MirtError, StlConfig, RawConfig, parseInput, parseText, synthe
                   select_pixels, finalize_counts, render_adaptive, hit_features, denoise,
                   denoise_work_bytes, denoise_frame, get_spheres, get_triangles, prev_features, temporal_accumulate,
                   TemporalAccumulator, Shading, make_plane, update_sphere_materials, update_triangle_materials,
-                  get_sphere_materials, get_triangle_materials, direct_light, pack_features, direct_light_frame)
+                  get_sphere_materials, get_triangle_materials, direct_light, pack_features, direct_light_frame,
+                  hemisphere_visibility, cosine_directions, rotations, ambient_occlusion_frame)
 
 __all__ = ["MirtError", "StlConfig", "RawConfig", "parseInput", "parseText", "syntheticScene", "initRawConfigFromStl",
            "copyConfigDataToDevice", "freeRawConfigDeviceMemory", "build_lbvh_karas", "render", "render_params",
@@ -19,4 +21,5 @@ __all__ = ["MirtError", "StlConfig", "RawConfig", "parseInput", "parseText", "sy
            "select_pixels", "finalize_counts", "render_adaptive", "hit_features", "denoise", "denoise_work_bytes", "denoise_frame",
            "get_spheres", "get_triangles", "prev_features", "temporal_accumulate", "TemporalAccumulator",
            "Shading", "make_plane", "update_sphere_materials", "update_triangle_materials", "get_sphere_materials",
-           "get_triangle_materials", "direct_light", "pack_features", "direct_light_frame"]
+           "get_triangle_materials", "direct_light", "pack_features", "direct_light_frame",
+           "hemisphere_visibility", "cosine_directions", "rotations", "ambient_occlusion_frame"]

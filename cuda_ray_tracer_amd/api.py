@@ -892,6 +892,8 @@ class TemporalAccumulator:
 
 # Direct light at surface points (include/mirt_light.h): lighting.py holds the extension header's signature and calls
 from .lighting import MIRT_LIGHT_RAW, direct_light, pack_features, direct_light_frame      # noqa: E402,F401
+# Hemisphere visibility at surface points (include/mirt_visibility.h): visibility.py holds that header's signature and calls
+from .visibility import hemisphere_visibility, cosine_directions, rotations, ambient_occlusion_frame      # noqa: E402,F401
 
 
 def pack_rays(origins, dirs, tmax=float("inf")):

@@ -267,6 +267,7 @@ struct MirtScene {
   bool any_rough = false;
   int query_blocks = 0;                    // grid size of the ray-query kernel on this scene's device (query.hip; filled on first use)
   int light_blocks = 0;                    // ... and of the direct-light kernel (light.hip)
+  int vis_blocks = 0;                      // ... and of the hemisphere-visibility kernel (visibility.hip)
   bool updated = false;                    // geometry updated in place since the last build (update.hip): mirt_camera_rays waits for the build like every other call
   // Shading values updated in place (update_shading.hip).  The three facts above are prim_flags | host_flags (MAT_* bits,
   // material_flags.h), by source: the primitives' materials -- after a material update known only to the device, until
@@ -318,6 +319,9 @@ int trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits
 int camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, hipStream_t stream);
 // light.hip
 int direct_light(MirtScene* sc, const void* d_features, int64_t n, void* d_out_f32, uint64_t* d_lit_mask, uint32_t flags, hipStream_t stream);
+// visibility.hip
+int hemisphere_visibility(MirtScene* sc, const void* d_features, int64_t n, const void* d_dirs, int num_dirs, const void* d_rot, float radius,
+                          void* d_out_f32, uint64_t* d_vis_mask, uint32_t flags, hipStream_t stream);
 // denoise.hip
 int hit_features(MirtScene* sc, const void* d_rays, const void* d_hits, int64_t n, void* d_features, hipStream_t stream);
 size_t denoise_work_bytes(const MirtRenderParams* p);

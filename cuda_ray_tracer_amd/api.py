@@ -894,6 +894,8 @@ class TemporalAccumulator:
 from .lighting import MIRT_LIGHT_RAW, direct_light, pack_features, direct_light_frame      # noqa: E402,F401
 # Hemisphere visibility at surface points (include/mirt_visibility.h): visibility.py holds that header's signature and calls
 from .visibility import hemisphere_visibility, cosine_directions, rotations, ambient_occlusion_frame      # noqa: E402,F401
+# Indirect light at surface points (include/mirt_indirect.h): indirect.py holds that header's signature and calls
+from .indirect import indirect_light, indirect_light_frame      # noqa: E402,F401
 
 
 def pack_rays(origins, dirs, tmax=float("inf")):

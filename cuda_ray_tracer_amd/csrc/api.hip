@@ -350,6 +350,15 @@ int mirt_hemisphere_visibility(MirtScene* sc, const void* d_features, int64_t n,
   return hemisphere_visibility(sc, d_features, n, d_dirs, num_dirs, d_rot, radius, d_out_f32, d_vis_mask, flags, (hipStream_t)stream);
 }
 
+// (include/mirt_indirect.h)
+int mirt_indirect_light(MirtScene* sc, const void* d_features, int64_t n, const void* d_dirs, int num_dirs, const void* d_rot, float radius,
+                        void* d_out_f32, uint64_t* d_hit_mask, uint32_t flags, void* stream)
+{
+  if (!sc) { set_error("mirt_indirect_light: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return indirect_light(sc, d_features, n, d_dirs, num_dirs, d_rot, radius, d_out_f32, d_hit_mask, flags, (hipStream_t)stream);
+}
+
 size_t mirt_denoise_work_bytes(const MirtRenderParams* p) { return denoise_work_bytes(p); }
 
 int mirt_denoise(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, const void* d_features,

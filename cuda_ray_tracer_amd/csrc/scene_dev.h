@@ -268,6 +268,7 @@ struct MirtScene {
   int query_blocks = 0;                    // grid size of the ray-query kernel on this scene's device (query.hip; filled on first use)
   int light_blocks = 0;                    // ... and of the direct-light kernel (light.hip)
   int vis_blocks = 0;                      // ... and of the hemisphere-visibility kernel (visibility.hip)
+  int indirect_blocks = 0;                 // ... and of the indirect-light kernel (indirect.hip)
   bool updated = false;                    // geometry updated in place since the last build (update.hip): mirt_camera_rays waits for the build like every other call
   // Shading values updated in place (update_shading.hip).  The three facts above are prim_flags | host_flags (MAT_* bits,
   // material_flags.h), by source: the primitives' materials -- after a material update known only to the device, until
@@ -322,6 +323,9 @@ int direct_light(MirtScene* sc, const void* d_features, int64_t n, void* d_out_f
 // visibility.hip
 int hemisphere_visibility(MirtScene* sc, const void* d_features, int64_t n, const void* d_dirs, int num_dirs, const void* d_rot, float radius,
                           void* d_out_f32, uint64_t* d_vis_mask, uint32_t flags, hipStream_t stream);
+// indirect.hip
+int indirect_light(MirtScene* sc, const void* d_features, int64_t n, const void* d_dirs, int num_dirs, const void* d_rot, float radius,
+                   void* d_out_f32, uint64_t* d_hit_mask, uint32_t flags, hipStream_t stream);
 // denoise.hip
 int hit_features(MirtScene* sc, const void* d_rays, const void* d_hits, int64_t n, void* d_features, hipStream_t stream);
 size_t denoise_work_bytes(const MirtRenderParams* p);

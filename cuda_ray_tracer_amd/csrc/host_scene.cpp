@@ -38,6 +38,38 @@ int check_frame(const char* who, const MirtRenderParams* p, int64_t npix, bool* 
   return MIRT_OK;
 }
 
+int check_table_query(const char* who, const char* mask_name, const void* d_features, int64_t n, const void* d_dirs, int num_dirs, const void* d_rot,
+                      float radius, const void* d_out_f32, const uint64_t* d_mask, uint32_t flags, bool built, bool* go)
+{
+  *go = false;
+  const std::string w = std::string(who) + ": ", mask = mask_name;
+  if (flags != 0u) { set_error(w + "flags must be 0"); return MIRT_ERR_ARG; }
+  if (n < 0) { set_error(w + "negative n"); return MIRT_ERR_ARG; }
+  if (num_dirs < 1 || num_dirs > 64) { set_error(w + "num_dirs must be 1..64"); return MIRT_ERR_ARG; }
+  if (!(radius > 0.0f)) { set_error(w + "radius must be positive (or +inf)"); return MIRT_ERR_ARG; }
+  if (n > 0 && (!d_features || !d_dirs || !d_out_f32)) { set_error(w + "null buffer"); return MIRT_ERR_ARG; }
+  if (n > 0 && (!is_aligned(16, d_features, d_dirs, d_out_f32) || !is_aligned(8, d_rot, d_mask))) {
+    set_error(w + "d_features, d_dirs and d_out_f32 must be 16-byte aligned, d_rot and " + mask + " 8-byte aligned");
+    return MIRT_ERR_ARG;
+  }
+  if (n >= (1ll << 56)) { set_error(w + "too many rows"); return MIRT_ERR_ARG; }
+  const size_t N = (size_t)n, K = (size_t)num_dirs;
+  if (n > 0) {
+    // an output against every input, and the two outputs against each other
+    const void* const in[3] = {d_features, d_dirs, d_rot};
+    const size_t in_bytes[3] = {32 * N, 16 * K, 8 * N};
+    bool bad = d_mask && overlaps(d_mask, 8 * N, d_out_f32, 16 * N);
+    for (int i = 0; i < 3; ++i) {
+      if (!in[i]) continue;
+      bad = bad || overlaps(d_out_f32, 16 * N, in[i], in_bytes[i]) || (d_mask && overlaps(d_mask, 8 * N, in[i], in_bytes[i]));
+    }
+    if (bad) { set_error(w + "d_out_f32 and " + mask + " must not overlap d_features, d_dirs, d_rot or each other"); return MIRT_ERR_ARG; }
+  }
+  if (!built) { set_error(w + "call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
+  *go = n > 0;
+  return MIRT_OK;
+}
+
 namespace {
 
 inline MirtVec3 v3(float x, float y, float z) { MirtVec3 v; v.x = x; v.y = y; v.z = z; return v; }

@@ -33,6 +33,11 @@ int check_range(const char* who, const void* d_array, int first, int count, int 
 // The frame and the part of it (npix pixels, render_num_pixels) that a call renders or makes rays for: both within the 32-bit
 // pixel seed and sample index.  MIRT_OK with *go = false: nothing to do (an empty part).
 int check_frame(const char* who, const MirtRenderParams* p, int64_t npix, bool* go);
+// The arguments of a query that traces a caller's table of directions from every row of a feature buffer
+// (mirt_hemisphere_visibility, mirt_indirect_light): mask_name is the mask parameter's own name, built whether the scene has its
+// tree.  MIRT_OK with *go = false: nothing to do (n == 0).
+int check_table_query(const char* who, const char* mask_name, const void* d_features, int64_t n, const void* d_dirs, int num_dirs, const void* d_rot,
+                      float radius, const void* d_out_f32, const uint64_t* d_mask, uint32_t flags, bool built, bool* go);
 
 class HostScene {
 public:

@@ -16,11 +16,12 @@
 //                      phase 3: rho of the hit's material, w from the table; one ballot of "hit" is the wave's 64-bit word, of
 //                               which a row's mask is its G-bit field; the four channels are summed by the xor-butterfly whose
 //                               order the header fixes, and the group's first lane writes them.
-//                      Both walks are copies, kept in this file (walk<ANY> below): query.hip, light.hip and visibility.hip keep
-//                      theirs, so that their assembly stays what it was (section 6l).
+//                      Both walks are walk<ANY> of query_walk.h, which light.hip uses too, and the choice of the winner and
+//                      its normal are the helpers query.hip uses (section 6n).
 #include "scene_dev.h"
 #include "host_scene.h"
 #include "shade_common.h"
+#include "query_walk.h"
 #include "../../include/mirt_indirect.h"
 
 #include <cmath>
@@ -28,13 +29,11 @@
 namespace mirt {
 namespace {
 
-constexpr int IBLOCK = 256;
 // IWAVES_PER_SIMD is a lower bound for the compiler, not the 8 of the other query kernels: this one carries the hit point, the hit's
 // normal, the sum and the material index across the shadow walks, and under a bound of 8 (64 VGPRs) it spills 12 of them.  Under
 // this bound it takes 72 VGPRs without a spill: 7 waves per SIMD.
-// ISTACK_LDS x 4 B x 64 lanes = 5 KiB of LDS per wave, as in the other query kernels
+// (QUERY_STACK_LDS x 4 B x 64 lanes = 5 KiB of LDS per wave, as in the other query kernels)
 constexpr int IWAVES_PER_SIMD = 6;
-constexpr int ISTACK_LDS = 20;
 constexpr uint32_t MAT_NONE = 0xffffffffu;     // the gather ray hit nothing
 constexpr uint32_t MAT_PLANE = 0x80000000u;    // | plane index; else the index into mats (spheres, then triangles)
 
@@ -56,7 +55,7 @@ struct IndirectArgs {
   const LightDev* bulbs; int num_bulbs;
   float radius;
   int num_dirs;                   // K
-  int lds_depth;                  // stack entries kept in LDS (<= ISTACK_LDS)
+  int lds_depth;                  // stack entries kept in LDS (<= QUERY_STACK_LDS)
   int gshift;                     // G = 1 << gshift lanes per row
 };
 
@@ -67,79 +66,17 @@ struct IndirectArgs {
 typedef const IndirectArgs __attribute__((address_space(4))) * KernArgs;
 __device__ __forceinline__ KernArgs fresh(KernArgs p) { asm volatile("" : "+s"(p)); return p; }
 
-// The walk of trace_rays_kernel<ANY> (query.hip) for the ray (o, tmax, d), d normalised: the planes, then the exact 64-byte records
-// left child first.  Leaves tbest / refbest (the tree's answer) and tplane / plane_id (the planes').
-template <bool ANY>
-__device__ __forceinline__ void walk(const unsigned char* heap, uint32_t root_ref, const PlaneDev* planes, int num_planes, const f3& o, const f3& d, float tmax,
-                                     uint32_t* lds_stack, uint32_t* spill, int lds_depth, int tid, float& tbest, uint32_t& refbest, float& tplane,
-                                     int& plane_id)
+__global__ void __launch_bounds__(QUERY_BLOCK, IWAVES_PER_SIMD) indirect_light_kernel(const IndirectArgs q)
 {
-  const float tmin = 0.0001f;
-  // a ray with nothing to look for (tmax <= 0 or NaN) or no direction (shorter than normalize's 1e-6, or NaN) is a miss
-  const bool live = tmax > 0.0f && (fabsf(d.x) + fabsf(d.y) + fabsf(d.z)) > 0.0f;
-  tplane = INFINITY; tbest = INFINITY;
-  plane_id = -1;
-  refbest = REF_NONE;
-  if (live) nearest_plane(planes, num_planes, o, d, tplane, plane_id);
-  // an occlusion query that a plane already answers needs no walk
-  if (live && root_ref != REF_NONE && !(ANY && plane_id >= 0 && tplane < tmax)) {
-    const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    uint32_t cur = root_ref;
-    int sp = 0;
-    for (;;) {
-      const float4* rec = reinterpret_cast<const float4*>(heap + (cur << 4));
-      bool pop;
-      if (cur & REF_LEAF) {
-        // intersect_leaf_primitives, bvh_traversal.cu:47-89
-        float t = 0.0f;
-        bool hit;
-        if (cur & REF_TRI) {
-          hit = triangle_hit(rec[0], rec[1], rec[2], o, d, t);
-        } else {
-          float tc, t_far;
-          hit = sphere_hit(rec[0], o, d, t, tc, t_far);
-        }
-        const bool closer = closer_hit(hit, t, tbest, cur & REF_OFFMASK, refbest);
-        tbest = closer ? t : tbest;
-        refbest = closer ? cur : refbest;
-        if (ANY && closer && t < tmax) break;           // the first occluder ends an occlusion query
-        pop = true;
-      } else {
-        // hit_aabb_adapted on both children, left first (bvh_traversal.cu:11-44, 149-157)
-        const float4 b0 = rec[0], b1 = rec[1], b2 = rec[2];
-        const uint2 ch = *reinterpret_cast<const uint2*>(rec + 3);
-        bool hl, hr;
-        float tel, ter;
-        box_pair(b0, b1, b2, o.x, o.y, o.z, inv.x, inv.y, inv.z, tbest, tmin, hl, hr, tel, ter);
-        if (hl && hr) {
-          // (the tree is at most 58 levels deep, DESIGN.md section 1: sp stays below STACK_TOTAL; the mask only bounds the index)
-          if (sp < lds_depth) lds_stack[sp * IBLOCK + tid] = ch.y;
-          else spill[(sp - lds_depth) & (STACK_TOTAL - 1)] = ch.y;
-          ++sp;
-        }
-        cur = hl ? ch.x : ch.y;
-        pop = !(hl || hr);
-      }
-      if (pop) {
-        if (sp == 0) break;
-        --sp;
-        cur = sp < lds_depth ? lds_stack[sp * IBLOCK + tid] : spill[(sp - lds_depth) & (STACK_TOTAL - 1)];
-      }
-    }
-  }
-}
-
-__global__ void __launch_bounds__(IBLOCK, IWAVES_PER_SIMD) indirect_light_kernel(const IndirectArgs q)
-{
-  __shared__ uint32_t lds_stack[ISTACK_LDS * IBLOCK];
+  __shared__ uint32_t lds_stack[QUERY_STACK_LDS * QUERY_BLOCK];
   uint32_t spill[STACK_TOTAL];                     // (entries lds_depth.. of the lane's stack: the rarely taken spill path)
   const int G = 1 << q.gshift;
   const int rows_per_wave = 64 >> q.gshift;
   const KernArgs ka = (KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
   const unsigned char* const heap = reinterpret_cast<const unsigned char*>(q.nodes);
   // (the same for every lane of a wave: the loop below is uniform, so that every lane reaches the ballot and the exchange)
-  const long long wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (IBLOCK / 64) + (threadIdx.x >> 6)));
-  const long long stride = (long long)gridDim.x * (IBLOCK / 64) * rows_per_wave;
+  const long long wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (QUERY_BLOCK / 64) + (threadIdx.x >> 6)));
+  const long long stride = (long long)gridDim.x * (QUERY_BLOCK / 64) * rows_per_wave;
   for (long long base = wave * rows_per_wave; base < q.n; base += stride) {
     // (as in hemisphere_visibility_kernel: what a lane derives from its index is derived again in every pass, and again after every
     // walk, from a copy of the index the compiler cannot tie to the others, so that none of it lives across the passes or a walk)
@@ -182,39 +119,19 @@ __global__ void __launch_bounds__(IBLOCK, IWAVES_PER_SIMD) indirect_light_kernel
       uint32_t refbest;
       int plane_id;
       walk<false>(heap, q.root_ref, q.planes, q.num_planes, o, d, tmax, lds_stack, spill, q.lds_depth, tid, tbest, refbest, tplane, plane_id);
-      // hitNearest: the nearer of BVH hit and plane hit, the plane winning a tie (draw.cu:292-318), then the caller's bound
-      const bool bvh_hit = refbest != REF_NONE;
-      const bool use_bvh = bvh_hit && (plane_id < 0 || tbest < tplane);
-      const float t = use_bvh ? tbest : tplane;
-      const bool report = (use_bvh || plane_id >= 0) && t < tmax;
-      missed = !report;
-      if (report) {
+      const Nearest w = nearest_of<false>(tbest, refbest, tplane, plane_id, tmax);
+      missed = !w.report;
+      if (w.report) {
         const KernArgs a2 = fresh(ka);
+        const float t = w.t;
         // mirt_hit_features' point, and ObjectInfo.normal of the winner as mirt_trace_rays reports it
         P2 = mk3(o.x + t * d.x, o.y + t * d.y, o.z + t * d.z);
-        if (use_bvh) {
-          const uint32_t off16 = refbest & REF_OFFMASK;
-          const float4* rec = q.nodes + off16;
-          const uint32_t id = a2->unit_prim[off16 - a2->prim_base16] & 0x7fffffffu;
-          if (refbest & REF_TRI) {
-            const float4 q0 = rec[0], q1 = rec[1];
-            const f3 nor = mk3(q0.w, q1.x, q1.y);
-            n2 = (dot(d, nor) < 0.0f) ? nor : -nor;
-            matref = (uint32_t)a2->num_spheres + id;
-          } else {
-            const float4 sph = rec[0];
-            const f3 c = mk3(sph.x, sph.y, sph.z);
-            const f3 p = t * d + o;
-            const f3 cr0 = c - o;
-            const bool inside = (dot(cr0, cr0) < sph.w * sph.w);
-            n2 = normalize(inside ? (c - p) : (p - c));
-            matref = id;
-          }
+        if (w.use_bvh) {
+          const uint32_t id = a2->unit_prim[(refbest & REF_OFFMASK) - a2->prim_base16] & 0x7fffffffu;
+          n2 = prim_normal(q.nodes, refbest, t, o, d);
+          matref = (refbest & REF_TRI) ? (uint32_t)a2->num_spheres + id : id;
         } else {
-          typedef const PlaneDev __attribute__((address_space(4))) * ConstPlanes;
-          const ConstPlanes planes = (ConstPlanes)(unsigned long long)q.planes;
-          const f3 pnor = mk3(planes[plane_id].nx, planes[plane_id].ny, planes[plane_id].nz);
-          n2 = (dot(pnor, d) < 0.0f) ? pnor : -pnor;
+          n2 = plane_normal(q.planes, plane_id, d);
           matref = MAT_PLANE | (uint32_t)plane_id;
         }
       }
@@ -307,32 +224,9 @@ __global__ void __launch_bounds__(IBLOCK, IWAVES_PER_SIMD) indirect_light_kernel
 int indirect_light(MirtScene* sc, const void* d_features, int64_t n, const void* d_dirs, int num_dirs, const void* d_rot, float radius,
                    void* d_out_f32, uint64_t* d_hit_mask, uint32_t flags, hipStream_t stream)
 {
-  if (flags != 0u) { set_error("mirt_indirect_light: flags must be 0"); return MIRT_ERR_ARG; }
-  if (n < 0) { set_error("mirt_indirect_light: negative n"); return MIRT_ERR_ARG; }
-  if (num_dirs < 1 || num_dirs > 64) { set_error("mirt_indirect_light: num_dirs must be 1..64"); return MIRT_ERR_ARG; }
-  if (!(radius > 0.0f)) { set_error("mirt_indirect_light: radius must be positive (or +inf)"); return MIRT_ERR_ARG; }
-  if (n > 0 && (!d_features || !d_dirs || !d_out_f32)) { set_error("mirt_indirect_light: null buffer"); return MIRT_ERR_ARG; }
-  if (n > 0 && (!is_aligned(16, d_features, d_dirs, d_out_f32) || !is_aligned(8, d_rot, d_hit_mask))) {
-    set_error("mirt_indirect_light: d_features, d_dirs and d_out_f32 must be 16-byte aligned, d_rot and d_hit_mask 8-byte aligned");
-    return MIRT_ERR_ARG;
-  }
-  if (n >= (1ll << 56)) { set_error("mirt_indirect_light: too many rows"); return MIRT_ERR_ARG; }
-  const size_t N = (size_t)n, K = (size_t)num_dirs;
-  if (n > 0) {
-    // an output against every input, and the two outputs against each other
-    const void* const in[3] = {d_features, d_dirs, d_rot};
-    const size_t in_bytes[3] = {32 * N, 16 * K, 8 * N};
-    bool bad = d_hit_mask && overlaps(d_hit_mask, 8 * N, d_out_f32, 16 * N);
-    for (int i = 0; i < 3; ++i) {
-      if (!in[i]) continue;
-      bad = bad || overlaps(d_out_f32, 16 * N, in[i], in_bytes[i]) || (d_hit_mask && overlaps(d_hit_mask, 8 * N, in[i], in_bytes[i]));
-    }
-    if (bad) { set_error("mirt_indirect_light: d_out_f32 and d_hit_mask must not overlap d_features, d_dirs, d_rot or each other"); return MIRT_ERR_ARG; }
-  }
-  if (!sc->built) { set_error("mirt_indirect_light: call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
-  if (n == 0) return MIRT_OK;
-  if (!sc->indirect_blocks && persistent_grid_blocks(sc->device, indirect_light_kernel, IBLOCK, IWAVES_PER_SIMD * 4 * 64 / IBLOCK, &sc->indirect_blocks) != hipSuccess)
-    sc->indirect_blocks = 1024;      // per scene, i.e. per device
+  bool go = false;
+  const int rc = check_table_query("mirt_indirect_light", "d_hit_mask", d_features, n, d_dirs, num_dirs, d_rot, radius, d_out_f32, d_hit_mask, flags, sc->built, &go);
+  if (rc != MIRT_OK || !go) return rc;
   IndirectArgs q;
   q.features = reinterpret_cast<const float4*>(d_features);
   q.dirs = reinterpret_cast<const float4*>(d_dirs);
@@ -349,14 +243,10 @@ int indirect_light(MirtScene* sc, const void* d_features, int64_t n, const void*
   q.bulbs = sc->bulbs; q.num_bulbs = sc->d.num_bulbs;
   q.radius = radius;
   q.num_dirs = num_dirs;
-  const int opt = sc->opt.stack_lds_depth;
-  q.lds_depth = (opt >= 0 && opt < ISTACK_LDS) ? opt : ISTACK_LDS;      // tests force the spill path
-  q.gshift = 0;
-  while ((1 << q.gshift) < num_dirs) ++q.gshift;
-  const long long rows_per_block = (long long)(IBLOCK / 64) * (64 >> q.gshift);
-  const long long want = (n + rows_per_block - 1) / rows_per_block;
-  const int blocks = (int)(want < sc->indirect_blocks ? want : sc->indirect_blocks);
-  hipLaunchKernelGGL(indirect_light_kernel, dim3(blocks), dim3(IBLOCK), 0, stream, q);
+  q.lds_depth = query_lds_depth(sc);
+  const GroupLaunch g = group_launch(n, num_dirs, query_grid_blocks(sc, indirect_light_kernel, IWAVES_PER_SIMD, &sc->indirect_blocks));
+  q.gshift = g.gshift;
+  hipLaunchKernelGGL(indirect_light_kernel, dim3(g.blocks), dim3(QUERY_BLOCK), 0, stream, q);
   MIRT_HIP(hipGetLastError());
   return MIRT_OK;
 }

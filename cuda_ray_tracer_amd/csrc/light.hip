@@ -5,15 +5,17 @@
 //
 // direct_light_kernel  one lane = one (row, light) pair.  With L lights, G is the next power of two >= max(L, 1): a wave serves
 //                      64 / G rows at a time (grid-stride), lane g G + li owns light li of the wave's row g, lanes with li >= L
-//                      idle.  A lane does the facing test, then the any-hit walk of its one shadow ray -- the loop of
-//                      trace_rays_kernel<true> (query.hip), kept as a copy here: sharing it would move the query kernels' pinned
-//                      register allocation.  The lane of a light that reaches the point then computes that light's term; one
+//                      idle.  A lane does the facing test, then the any-hit walk of its one shadow ray -- the walk of
+//                      trace_rays_kernel<true> (query.hip): walk<true> of query_walk.h, which indirect.hip uses too (DESIGN.md
+//                      section 6n).
+//                      The lane of a light that reaches the point then computes that light's term; one
 //                      ballot of "facing and not occluded" is the wave's 64-bit word, of which a row's mask is its G-bit field;
 //                      and the terms are summed in light order, every lane of a group fetching term li of its group in step
 //                      li.  The sum order is fixed by construction, so the result's bits do not depend on this shape.
 #include "scene_dev.h"
 #include "host_scene.h"
 #include "shade_common.h"
+#include "query_walk.h"
 #include "../../include/mirt_light.h"
 
 #include <cmath>
@@ -21,10 +23,8 @@
 namespace mirt {
 namespace {
 
-constexpr int LBLOCK = 256;
-// the query kernel's budget: 64 VGPRs, 8 waves per SIMD; LSTACK_LDS x 4 B x 64 lanes = 5 KiB of LDS per wave
+// the query kernel's budget: 64 VGPRs, 8 waves per SIMD; QUERY_STACK_LDS x 4 B x 64 lanes = 5 KiB of LDS per wave
 constexpr int LWAVES_PER_SIMD = 8;
-constexpr int LSTACK_LDS = 20;
 
 struct LightArgs {
   const float4* features;         // mirt_hit_features rows: (P, hit), (n, _)
@@ -37,22 +37,21 @@ struct LightArgs {
   const LightDev* suns; int num_suns;
   const LightDev* bulbs; int num_bulbs;
   float expose;                   // (+inf, which set_expose leaves a term at, also stands for MIRT_LIGHT_RAW)
-  int lds_depth;                  // stack entries kept in LDS (<= LSTACK_LDS)
+  int lds_depth;                  // stack entries kept in LDS (<= QUERY_STACK_LDS)
   int gshift;                     // G = 1 << gshift lanes per row
 };
 
-__global__ void __launch_bounds__(LBLOCK, LWAVES_PER_SIMD) direct_light_kernel(const LightArgs q)
+__global__ void __launch_bounds__(QUERY_BLOCK, LWAVES_PER_SIMD) direct_light_kernel(const LightArgs q)
 {
-  __shared__ uint32_t lds_stack[LSTACK_LDS * LBLOCK];
+  __shared__ uint32_t lds_stack[QUERY_STACK_LDS * QUERY_BLOCK];
   uint32_t spill[STACK_TOTAL];                     // (entries lds_depth.. of the lane's stack: the rarely taken spill path)
   const int G = 1 << q.gshift;
   const int rows_per_wave = 64 >> q.gshift;
   const int nlights = q.num_suns + q.num_bulbs;
   const unsigned char* const heap = reinterpret_cast<const unsigned char*>(q.nodes);
-  const float tmin = 0.0001f;
   // (the same for every lane of a wave: the loop below is uniform, so that every lane reaches the ballot and the exchange)
-  const long long wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (LBLOCK / 64) + (threadIdx.x >> 6)));
-  const long long stride = (long long)gridDim.x * (LBLOCK / 64) * rows_per_wave;
+  const long long wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (QUERY_BLOCK / 64) + (threadIdx.x >> 6)));
+  const long long stride = (long long)gridDim.x * (QUERY_BLOCK / 64) * rows_per_wave;
   for (long long base = wave * rows_per_wave; base < q.n; base += stride) {
     // (what a lane derives from its index -- its light, its row -- is derived again in every pass, and again after the walk, from
     // a copy of the index the compiler cannot tie to the others: nothing of it then stays in registers across the passes or the
@@ -80,69 +79,14 @@ __global__ void __launch_bounds__(LBLOCK, LWAVES_PER_SIMD) direct_light_kernel(c
       const f3 N = normalize(ng);
       const f3 o = P + ng * EPSILON;
       f3 L, d;
-      if (is_sun) {
-        L = mk3(lt->nx, lt->ny, lt->nz);
-        d = normalize(mk3(lt->x, lt->y, lt->z));            // Ray(eye, dir, bounce), object.cuh:69 -- as mirt_trace_rays does it
-      } else {
-        const f3 bd = mk3(lt->x, lt->y, lt->z) - P;
-        tmax = length(bd);
-        L = normalize(bd);
-        d = L;
-      }
+      light_ray(lt, is_sun, P, L, d, tmax);
       lam = dot(N, L);
       if (lam > 0.0f) {
-        // ---- the any-hit query of trace_rays_kernel<true> (query.hip) for the ray (o, tmax, d) --------------------------------
-        const bool live = tmax > 0.0f && (fabsf(d.x) + fabsf(d.y) + fabsf(d.z)) > 0.0f;
-        float tplane = INFINITY, tbest = INFINITY;
-        int plane_id = -1;
-        uint32_t refbest = REF_NONE;
-        if (live) nearest_plane(q.planes, num_planes, o, d, tplane, plane_id);
-        // an occlusion query that a plane already answers needs no walk
-        if (live && root_ref != REF_NONE && !(plane_id >= 0 && tplane < tmax)) {
-          const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-          uint32_t cur = root_ref;
-          int sp = 0;
-          for (;;) {
-            const float4* rec = reinterpret_cast<const float4*>(heap + (cur << 4));
-            bool pop;
-            if (cur & REF_LEAF) {
-              // intersect_leaf_primitives, bvh_traversal.cu:47-89
-              float t = 0.0f;
-              bool hit;
-              if (cur & REF_TRI) {
-                hit = triangle_hit(rec[0], rec[1], rec[2], o, d, t);
-              } else {
-                float tc, t_far;
-                hit = sphere_hit(rec[0], o, d, t, tc, t_far);
-              }
-              const bool closer = closer_hit(hit, t, tbest, cur & REF_OFFMASK, refbest);
-              tbest = closer ? t : tbest;
-              refbest = closer ? cur : refbest;
-              if (closer && t < tmax) break;                  // the first occluder ends an occlusion query
-              pop = true;
-            } else {
-              // hit_aabb_adapted on both children, left first (bvh_traversal.cu:11-44, 149-157)
-              const float4 b0 = rec[0], b1 = rec[1], b2 = rec[2];
-              const uint2 ch = *reinterpret_cast<const uint2*>(rec + 3);
-              bool hl, hr;
-              float tel, ter;
-              box_pair(b0, b1, b2, o.x, o.y, o.z, inv.x, inv.y, inv.z, tbest, tmin, hl, hr, tel, ter);
-              if (hl && hr) {
-                // (the tree is at most 58 levels deep, DESIGN.md section 1: sp stays below STACK_TOTAL; the mask only bounds the index)
-                if (sp < q.lds_depth) lds_stack[sp * LBLOCK + tid] = ch.y;
-                else spill[(sp - q.lds_depth) & (STACK_TOTAL - 1)] = ch.y;
-                ++sp;
-              }
-              cur = hl ? ch.x : ch.y;
-              pop = !(hl || hr);
-            }
-            if (pop) {
-              if (sp == 0) break;
-              --sp;
-              cur = sp < q.lds_depth ? lds_stack[sp * LBLOCK + tid] : spill[(sp - q.lds_depth) & (STACK_TOTAL - 1)];
-            }
-          }
-        }
+        // the any-hit query of trace_rays_kernel<true> (query.hip) for the ray (o, tmax, d)
+        float tbest, tplane;
+        uint32_t refbest;
+        int plane_id;
+        walk<true>(heap, root_ref, q.planes, num_planes, o, d, tmax, lds_stack, spill, q.lds_depth, tid, tbest, refbest, tplane, plane_id);
         // what the query reports as kind != 0: an occluder of the tree or a plane, nearer than tmax
         const bool occluded = (refbest != REF_NONE && tbest < tmax) || (plane_id >= 0 && tplane < tmax);
         lit = !occluded;
@@ -163,9 +107,8 @@ __global__ void __launch_bounds__(LBLOCK, LWAVES_PER_SIMD) direct_light_kernel(c
         term = term * i2;
       }
     }
-    const unsigned long long word = __ballot(lit);
     const int lane2 = tid2 & 63, group2 = lane2 >> q.gshift;
-    const unsigned long long field = ((word >> (group2 << q.gshift)) << (64 - G)) >> (64 - G);
+    const unsigned long long field = group_field(lit, lane2, q.gshift);
     // the sum in light order: in step k every lane fetches term k of its group (only the group's first lane keeps the result)
     f3 acc = mk3(0.0f, 0.0f, 0.0f);
     const int first = lane2 & ~(G - 1);
@@ -202,8 +145,6 @@ int direct_light(MirtScene* sc, const void* d_features, int64_t n, void* d_out_f
   }
   if (!sc->built) { set_error("mirt_direct_light: call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
   if (n == 0) return MIRT_OK;
-  if (!sc->light_blocks && persistent_grid_blocks(sc->device, direct_light_kernel, LBLOCK, LWAVES_PER_SIMD * 4 * 64 / LBLOCK, &sc->light_blocks) != hipSuccess)
-    sc->light_blocks = 1024;      // per scene, i.e. per device
   LightArgs q;
   q.features = reinterpret_cast<const float4*>(d_features);
   q.out = reinterpret_cast<float4*>(d_out_f32);
@@ -215,15 +156,11 @@ int direct_light(MirtScene* sc, const void* d_features, int64_t n, void* d_out_f
   q.suns = sc->suns; q.num_suns = sc->d.num_suns;
   q.bulbs = sc->bulbs; q.num_bulbs = sc->d.num_bulbs;
   q.expose = (flags & MIRT_LIGHT_RAW) ? INFINITY : sc->d.expose;
-  const int opt = sc->opt.stack_lds_depth;
-  q.lds_depth = (opt >= 0 && opt < LSTACK_LDS) ? opt : LSTACK_LDS;      // tests force the spill path
+  q.lds_depth = query_lds_depth(sc);
   const int nlights = q.num_suns + q.num_bulbs;      // (at most 64: mirt_scene_create)
-  q.gshift = 0;
-  while ((1 << q.gshift) < nlights) ++q.gshift;
-  const long long rows_per_block = (long long)(LBLOCK / 64) * (64 >> q.gshift);
-  const long long want = (n + rows_per_block - 1) / rows_per_block;
-  const int blocks = (int)(want < sc->light_blocks ? want : sc->light_blocks);
-  hipLaunchKernelGGL(direct_light_kernel, dim3(blocks), dim3(LBLOCK), 0, stream, q);
+  const GroupLaunch g = group_launch(n, nlights, query_grid_blocks(sc, direct_light_kernel, LWAVES_PER_SIMD, &sc->light_blocks));
+  q.gshift = g.gshift;
+  hipLaunchKernelGGL(direct_light_kernel, dim3(g.blocks), dim3(QUERY_BLOCK), 0, stream, q);
   MIRT_HIP(hipGetLastError());
   return MIRT_OK;
 }

@@ -6,12 +6,15 @@
 //                     of traverse_lbvh (bvh_traversal.cu:92-183) over the exact 64-byte node records, left child first -- the
 //                     reference's own walk, so no vetting and no second walk is ever needed.  A lane carries the ray, 1/d, the
 //                     best distance and record and a stack pointer; the stack lives in LDS ([entry][lane]), entries deeper
-//                     than QSTACK_LDS in a per-lane private array (scratch) that the bundled scenes rarely reach.
+//                     than QUERY_STACK_LDS in a per-lane private array (scratch) that the bundled scenes rarely reach.
+//                     light.hip and indirect.hip take this walk from query_walk.h; here it is written out, because as a
+//                     function it cost the closest-hit kernel 21 to 37 %.
 // camera_rays_kernel  one lane = one pixel: the ray sample 0 of the pixel starts with in the render (init_sample_core +
 //                     primary_ray), before the Ray constructor normalises its direction.
 #include "scene_dev.h"
 #include "host_scene.h"
 #include "shade_common.h"
+#include "query_walk.h"
 
 #include <cmath>
 #include <cstring>
@@ -20,10 +23,8 @@
 namespace mirt {
 namespace {
 
-constexpr int QBLOCK = 256;
-// 64 VGPRs: 8 waves per SIMD, 32 per CU.  LDS: QSTACK_LDS x 4 B x 64 lanes = 5 KiB per wave, 160 KiB per CU at full occupancy.
+// 64 VGPRs: 8 waves per SIMD, 32 per CU.  LDS: QUERY_STACK_LDS x 4 B x 64 lanes = 5 KiB per wave, 160 KiB per CU at full occupancy.
 constexpr int QWAVES_PER_SIMD = 8;
-constexpr int QSTACK_LDS = 20;
 
 struct QueryArgs {
   const float4* rays;             // MirtRay: (o, tmax), (d, pad)
@@ -34,19 +35,19 @@ struct QueryArgs {
   const PlaneDev* planes; int num_planes;
   uint32_t root_ref;              // the exact records' root (REF_NONE: no primitive)
   uint32_t prim_base16;
-  int lds_depth;                  // stack entries kept in LDS (<= QSTACK_LDS)
+  int lds_depth;                  // stack entries kept in LDS (<= QUERY_STACK_LDS)
 };
 
 template <bool ANY>
-__global__ void __launch_bounds__(QBLOCK, QWAVES_PER_SIMD) trace_rays_kernel(const QueryArgs q)
+__global__ void __launch_bounds__(QUERY_BLOCK, QWAVES_PER_SIMD) trace_rays_kernel(const QueryArgs q)
 {
-  __shared__ uint32_t lds_stack[QSTACK_LDS * QBLOCK];
+  __shared__ uint32_t lds_stack[QUERY_STACK_LDS * QUERY_BLOCK];
   uint32_t spill[STACK_TOTAL];                     // (entries lds_depth.. of the lane's stack: the rarely taken spill path)
   const int tid = threadIdx.x;
-  const long long stride = (long long)gridDim.x * QBLOCK;
+  const long long stride = (long long)gridDim.x * QUERY_BLOCK;
   const unsigned char* const heap = reinterpret_cast<const unsigned char*>(q.nodes);
   const float tmin = 0.0001f;
-  for (long long i = (long long)blockIdx.x * QBLOCK + tid; i < q.num_rays; i += stride) {
+  for (long long i = (long long)blockIdx.x * QUERY_BLOCK + tid; i < q.num_rays; i += stride) {
     const float4 r0 = q.rays[2 * i], r1 = q.rays[2 * i + 1];
     const f3 o = mk3(r0.x, r0.y, r0.z);
     const float tmax = r0.w;
@@ -89,7 +90,7 @@ __global__ void __launch_bounds__(QBLOCK, QWAVES_PER_SIMD) trace_rays_kernel(con
           box_pair(b0, b1, b2, o.x, o.y, o.z, inv.x, inv.y, inv.z, tbest, tmin, hl, hr, tel, ter);
           if (hl && hr) {
             // (the tree is at most 58 levels deep, DESIGN.md section 1: sp stays below STACK_TOTAL; the mask only bounds the index)
-            if (sp < q.lds_depth) lds_stack[sp * QBLOCK + tid] = ch.y;
+            if (sp < q.lds_depth) lds_stack[sp * QUERY_BLOCK + tid] = ch.y;
             else spill[(sp - q.lds_depth) & (STACK_TOTAL - 1)] = ch.y;
             ++sp;
           }
@@ -99,43 +100,23 @@ __global__ void __launch_bounds__(QBLOCK, QWAVES_PER_SIMD) trace_rays_kernel(con
         if (pop) {
           if (sp == 0) break;
           --sp;
-          cur = sp < q.lds_depth ? lds_stack[sp * QBLOCK + tid] : spill[(sp - q.lds_depth) & (STACK_TOTAL - 1)];
+          cur = sp < q.lds_depth ? lds_stack[sp * QUERY_BLOCK + tid] : spill[(sp - q.lds_depth) & (STACK_TOTAL - 1)];
         }
       }
     }
-    // hitNearest: the nearer of BVH hit and plane hit, the plane winning a tie (draw.cu:292-318); an occlusion query reports the
-    // occluder it found.  Then the caller's bound (draw.cu:365-370).
-    const bool bvh_hit = refbest != REF_NONE;
-    const bool use_bvh = bvh_hit && (ANY ? tbest < tmax : (plane_id < 0 || tbest < tplane));
-    const float t = use_bvh ? tbest : tplane;
-    const bool report = (use_bvh || plane_id >= 0) && t < tmax;
+    const Nearest w = nearest_of<ANY>(tbest, refbest, tplane, plane_id, tmax);
+    const bool report = w.report;
+    const float t = w.t;
     uint32_t kind = 0u, id = 0u;
     f3 n = mk3(0.0f, 0.0f, 0.0f);
     if (report) {
-      // ObjectInfo.normal of the winner, from p = t d + o (struct.cu:64-163, draw.cu:581-615)
-      if (use_bvh) {
-        const uint32_t off16 = refbest & REF_OFFMASK;
-        const float4* rec = q.nodes + off16;
-        id = q.unit_prim[off16 - q.prim_base16] & 0x7fffffffu;
-        if (refbest & REF_TRI) {
-          const float4 q0 = rec[0], q1 = rec[1];
-          const f3 nor = mk3(q0.w, q1.x, q1.y);
-          n = (dot(d, nor) < 0.0f) ? nor : -nor;
-          kind = MIRT_HIT_TRIANGLE;
-        } else {
-          const float4 s = rec[0];
-          const f3 c = mk3(s.x, s.y, s.z);
-          const f3 p = t * d + o;
-          const f3 cr0 = c - o;
-          const bool inside = (dot(cr0, cr0) < s.w * s.w);
-          n = normalize(inside ? (c - p) : (p - c));
-          kind = MIRT_HIT_SPHERE;
-        }
+      // the winner's file-order id, its normal and MirtHit's kind
+      if (w.use_bvh) {
+        id = q.unit_prim[(refbest & REF_OFFMASK) - q.prim_base16] & 0x7fffffffu;
+        n = prim_normal(q.nodes, refbest, t, o, d);
+        kind = (refbest & REF_TRI) ? MIRT_HIT_TRIANGLE : MIRT_HIT_SPHERE;
       } else {
-        typedef const PlaneDev __attribute__((address_space(4))) * ConstPlanes;
-        const ConstPlanes planes = (ConstPlanes)(unsigned long long)q.planes;
-        const f3 pnor = mk3(planes[plane_id].nx, planes[plane_id].ny, planes[plane_id].nz);
-        n = (dot(pnor, d) < 0.0f) ? pnor : -pnor;
+        n = plane_normal(q.planes, plane_id, d);
         id = (uint32_t)plane_id;
         kind = MIRT_HIT_PLANE;
       }
@@ -151,9 +132,9 @@ __global__ void __launch_bounds__(QBLOCK, QWAVES_PER_SIMD) trace_rays_kernel(con
 }
 
 // init_sample_core (sample 0 of local pixel i of the part) + primary_dir
-__global__ void __launch_bounds__(QBLOCK) camera_rays_kernel(const RenderArgs a, float4* __restrict__ rays, long long num_pixels)
+__global__ void __launch_bounds__(QUERY_BLOCK) camera_rays_kernel(const RenderArgs a, float4* __restrict__ rays, long long num_pixels)
 {
-  const long long i = (long long)blockIdx.x * QBLOCK + threadIdx.x;
+  const long long i = (long long)blockIdx.x * QUERY_BLOCK + threadIdx.x;
   if (i >= num_pixels) return;
   // local pixel of the part -> frame pixel, as init_sample_core does it (a part has < 2^31 pixels: checked by camera_rays)
   const uint32_t stripe_pixels = (uint32_t)a.stripe_rows * (uint32_t)a.width;
@@ -194,8 +175,7 @@ int trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits
   }
   if (!sc->built) { set_error("mirt_trace_rays: call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
   if (num_rays == 0) return MIRT_OK;
-  if (!sc->query_blocks && persistent_grid_blocks(sc->device, trace_rays_kernel<false>, QBLOCK, QWAVES_PER_SIMD * 4 * 64 / QBLOCK, &sc->query_blocks) != hipSuccess)
-    sc->query_blocks = 1024;      // per scene, i.e. per device
+  const int grid = query_grid_blocks(sc, trace_rays_kernel<false>, QWAVES_PER_SIMD, &sc->query_blocks);
   QueryArgs q;
   q.rays = reinterpret_cast<const float4*>(d_rays);
   q.hits = reinterpret_cast<uint32_t*>(d_hits);
@@ -203,12 +183,11 @@ int trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits
   q.nodes = sc->nodes; q.unit_prim = sc->unit_prim;
   q.planes = sc->planes; q.num_planes = sc->d.num_planes;
   q.root_ref = sc->root_ref; q.prim_base16 = sc->prim_base / 16u;
-  const int opt = sc->opt.stack_lds_depth;
-  q.lds_depth = (opt >= 0 && opt < QSTACK_LDS) ? opt : QSTACK_LDS;      // tests force the spill path
-  const long long want = (num_rays + QBLOCK - 1) / QBLOCK;
-  const int blocks = (int)(want < sc->query_blocks ? want : sc->query_blocks);
-  if (flags & MIRT_QUERY_ANY_HIT) hipLaunchKernelGGL(trace_rays_kernel<true>, dim3(blocks), dim3(QBLOCK), 0, stream, q);
-  else hipLaunchKernelGGL(trace_rays_kernel<false>, dim3(blocks), dim3(QBLOCK), 0, stream, q);
+  q.lds_depth = query_lds_depth(sc);
+  const long long want = (num_rays + QUERY_BLOCK - 1) / QUERY_BLOCK;
+  const int blocks = (int)(want < grid ? want : grid);
+  if (flags & MIRT_QUERY_ANY_HIT) hipLaunchKernelGGL(trace_rays_kernel<true>, dim3(blocks), dim3(QUERY_BLOCK), 0, stream, q);
+  else hipLaunchKernelGGL(trace_rays_kernel<false>, dim3(blocks), dim3(QUERY_BLOCK), 0, stream, q);
   MIRT_HIP(hipGetLastError());
   return MIRT_OK;
 }
@@ -234,8 +213,8 @@ int camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, hipStrea
     rc = ensure_rng_tables(&sc->rng, p->spp > 1 ? 1 : 0, (long long)p->width * p->height, stream, &a.rng, true);
     if (rc != MIRT_OK) return rc;
   }
-  const int blocks = (int)((npix + QBLOCK - 1) / QBLOCK);
-  hipLaunchKernelGGL(camera_rays_kernel, dim3(blocks), dim3(QBLOCK), 0, stream, a, reinterpret_cast<float4*>(d_rays), (long long)npix);
+  const int blocks = (int)((npix + QUERY_BLOCK - 1) / QUERY_BLOCK);
+  hipLaunchKernelGGL(camera_rays_kernel, dim3(blocks), dim3(QUERY_BLOCK), 0, stream, a, reinterpret_cast<float4*>(d_rays), (long long)npix);
   MIRT_HIP(hipGetLastError());
   return MIRT_OK;
 }

@@ -9,6 +9,7 @@
 #include "../../include/mirt.h"
 #include "dev_mem.h"
 #include "device_common.h"
+#include "query_launch.h"
 #include "render_plan.h"
 #include "xorwow_tables.h"
 
@@ -374,6 +375,23 @@ hipError_t persistent_grid_blocks(int device, K kernel, int block, int per_cu_fa
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0) != hipSuccess || per_cu < 1) per_cu = per_cu_fallback;
   *blocks = prop.multiProcessorCount * per_cu;
   return hipSuccess;
+}
+
+// The query kernels' host side (query.hip, light.hip, visibility.hip, indirect.hip; launch arithmetic: query_launch.h).
+// Stack entries their walk keeps in LDS: the compiled size, unless the option names a smaller one (tests force the spill path).
+inline int query_lds_depth(const MirtScene* sc)
+{
+  const int opt = sc->opt.stack_lds_depth;
+  return (opt >= 0 && opt < QUERY_STACK_LDS) ? opt : QUERY_STACK_LDS;
+}
+
+// The persistent grid of a query kernel compiled for waves_per_simd waves: *cache (one of MirtScene's *_blocks, since occupancy
+// is per kernel), filled on first use -- per scene, i.e. per device.
+template <class K>
+int query_grid_blocks(const MirtScene* sc, K kernel, int waves_per_simd, int* cache)
+{
+  if (!*cache && persistent_grid_blocks(sc->device, kernel, QUERY_BLOCK, waves_per_simd * 4 * 64 / QUERY_BLOCK, cache) != hipSuccess) *cache = 1024;
+  return *cache;
 }
 
 // the frame, camera and partition block of RenderArgs (what a primary ray is made from, apart from spp and the rng tables)

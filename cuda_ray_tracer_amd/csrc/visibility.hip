@@ -6,9 +6,9 @@
 // hemisphere_visibility_kernel  the shape of direct_light_kernel (light.hip): one lane = one (row, direction) pair.  G is the next
 //                      power of two >= K: a wave serves 64 / G rows at a time (grid-stride, a wave-uniform trip count), lane
 //                      g G + k owns direction k of the wave's row g, lanes with k >= K idle.  A lane builds its ray and does the
-//                      any-hit walk of trace_rays_kernel<true> (query.hip) -- a copy, as in light.hip: a walk shared with
-//                      light.hip through a header moved that kernel's assembly (section 6l).  One ballot of "visible" is the
-//                      wave's 64-bit word, of which a row's mask is its G-bit field; the four channels are summed by an
+//                      any-hit walk of trace_rays_kernel<true> (query.hip), written out here: walk<true> of query_walk.h, which
+//                      light.hip and indirect.hip use, measured up to 0.7 % slower in this kernel (section 6n).  One ballot
+//                      of "visible" is the wave's 64-bit word, of which a row's mask is its G-bit field; the four channels are summed by an
 //                      xor-butterfly inside the group, whose order the header fixes, so every lane of a group ends with the same
 //                      bits and the group's first lane writes them.
 #include "scene_dev.h"
@@ -21,10 +21,8 @@
 namespace mirt {
 namespace {
 
-constexpr int VBLOCK = 256;
-// the query kernel's budget: 64 VGPRs, 8 waves per SIMD; VSTACK_LDS x 4 B x 64 lanes = 5 KiB of LDS per wave
+// the query kernel's budget: 64 VGPRs, 8 waves per SIMD; QUERY_STACK_LDS x 4 B x 64 lanes = 5 KiB of LDS per wave
 constexpr int VWAVES_PER_SIMD = 8;
-constexpr int VSTACK_LDS = 20;
 
 struct VisArgs {
   const float4* features;         // mirt_hit_features rows: (P, hit), (n, _)
@@ -38,21 +36,21 @@ struct VisArgs {
   uint32_t root_ref;              // the exact records' root (REF_NONE: no primitive)
   float radius;
   int num_dirs;                   // K
-  int lds_depth;                  // stack entries kept in LDS (<= VSTACK_LDS)
+  int lds_depth;                  // stack entries kept in LDS (<= QUERY_STACK_LDS)
   int gshift;                     // G = 1 << gshift lanes per row
 };
 
-__global__ void __launch_bounds__(VBLOCK, VWAVES_PER_SIMD) hemisphere_visibility_kernel(const VisArgs q)
+__global__ void __launch_bounds__(QUERY_BLOCK, VWAVES_PER_SIMD) hemisphere_visibility_kernel(const VisArgs q)
 {
-  __shared__ uint32_t lds_stack[VSTACK_LDS * VBLOCK];
+  __shared__ uint32_t lds_stack[QUERY_STACK_LDS * QUERY_BLOCK];
   uint32_t spill[STACK_TOTAL];                     // (entries lds_depth.. of the lane's stack: the rarely taken spill path)
   const int G = 1 << q.gshift;
   const int rows_per_wave = 64 >> q.gshift;
   const unsigned char* const heap = reinterpret_cast<const unsigned char*>(q.nodes);
   const float tmin = 0.0001f;
   // (the same for every lane of a wave: the loop below is uniform, so that every lane reaches the ballot and the exchange)
-  const long long wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (VBLOCK / 64) + (threadIdx.x >> 6)));
-  const long long stride = (long long)gridDim.x * (VBLOCK / 64) * rows_per_wave;
+  const long long wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (QUERY_BLOCK / 64) + (threadIdx.x >> 6)));
+  const long long stride = (long long)gridDim.x * (QUERY_BLOCK / 64) * rows_per_wave;
   for (long long base = wave * rows_per_wave; base < q.n; base += stride) {
     // (as in direct_light_kernel: what a lane derives from its index is derived again in every pass, and again after the walk,
     // from a copy of the index the compiler cannot tie to the others, so that none of it lives across the passes or the walk)
@@ -130,7 +128,7 @@ __global__ void __launch_bounds__(VBLOCK, VWAVES_PER_SIMD) hemisphere_visibility
             box_pair(b0, b1, b2, o.x, o.y, o.z, inv.x, inv.y, inv.z, tbest, tmin, hl, hr, tel, ter);
             if (hl && hr) {
               // (the tree is at most 58 levels deep, DESIGN.md section 1: sp stays below STACK_TOTAL; the mask only bounds the index)
-              if (sp < q.lds_depth) lds_stack[sp * VBLOCK + tid] = ch.y;
+              if (sp < q.lds_depth) lds_stack[sp * QUERY_BLOCK + tid] = ch.y;
               else spill[(sp - q.lds_depth) & (STACK_TOTAL - 1)] = ch.y;
               ++sp;
             }
@@ -140,7 +138,7 @@ __global__ void __launch_bounds__(VBLOCK, VWAVES_PER_SIMD) hemisphere_visibility
           if (pop) {
             if (sp == 0) break;
             --sp;
-            cur = sp < q.lds_depth ? lds_stack[sp * VBLOCK + tid] : spill[(sp - q.lds_depth) & (STACK_TOTAL - 1)];
+            cur = sp < q.lds_depth ? lds_stack[sp * QUERY_BLOCK + tid] : spill[(sp - q.lds_depth) & (STACK_TOTAL - 1)];
           }
         }
       }
@@ -178,32 +176,9 @@ __global__ void __launch_bounds__(VBLOCK, VWAVES_PER_SIMD) hemisphere_visibility
 int hemisphere_visibility(MirtScene* sc, const void* d_features, int64_t n, const void* d_dirs, int num_dirs, const void* d_rot, float radius,
                           void* d_out_f32, uint64_t* d_vis_mask, uint32_t flags, hipStream_t stream)
 {
-  if (flags != 0u) { set_error("mirt_hemisphere_visibility: flags must be 0"); return MIRT_ERR_ARG; }
-  if (n < 0) { set_error("mirt_hemisphere_visibility: negative n"); return MIRT_ERR_ARG; }
-  if (num_dirs < 1 || num_dirs > 64) { set_error("mirt_hemisphere_visibility: num_dirs must be 1..64"); return MIRT_ERR_ARG; }
-  if (!(radius > 0.0f)) { set_error("mirt_hemisphere_visibility: radius must be positive (or +inf)"); return MIRT_ERR_ARG; }
-  if (n > 0 && (!d_features || !d_dirs || !d_out_f32)) { set_error("mirt_hemisphere_visibility: null buffer"); return MIRT_ERR_ARG; }
-  if (n > 0 && (!is_aligned(16, d_features, d_dirs, d_out_f32) || !is_aligned(8, d_rot, d_vis_mask))) {
-    set_error("mirt_hemisphere_visibility: d_features, d_dirs and d_out_f32 must be 16-byte aligned, d_rot and d_vis_mask 8-byte aligned");
-    return MIRT_ERR_ARG;
-  }
-  if (n >= (1ll << 56)) { set_error("mirt_hemisphere_visibility: too many rows"); return MIRT_ERR_ARG; }
-  const size_t N = (size_t)n, K = (size_t)num_dirs;
-  if (n > 0) {
-    // an output against every input, and the two outputs against each other
-    const void* const in[3] = {d_features, d_dirs, d_rot};
-    const size_t in_bytes[3] = {32 * N, 16 * K, 8 * N};
-    bool bad = d_vis_mask && overlaps(d_vis_mask, 8 * N, d_out_f32, 16 * N);
-    for (int i = 0; i < 3; ++i) {
-      if (!in[i]) continue;
-      bad = bad || overlaps(d_out_f32, 16 * N, in[i], in_bytes[i]) || (d_vis_mask && overlaps(d_vis_mask, 8 * N, in[i], in_bytes[i]));
-    }
-    if (bad) { set_error("mirt_hemisphere_visibility: d_out_f32 and d_vis_mask must not overlap d_features, d_dirs, d_rot or each other"); return MIRT_ERR_ARG; }
-  }
-  if (!sc->built) { set_error("mirt_hemisphere_visibility: call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
-  if (n == 0) return MIRT_OK;
-  if (!sc->vis_blocks && persistent_grid_blocks(sc->device, hemisphere_visibility_kernel, VBLOCK, VWAVES_PER_SIMD * 4 * 64 / VBLOCK, &sc->vis_blocks) != hipSuccess)
-    sc->vis_blocks = 1024;      // per scene, i.e. per device
+  bool go = false;
+  const int rc = check_table_query("mirt_hemisphere_visibility", "d_vis_mask", d_features, n, d_dirs, num_dirs, d_rot, radius, d_out_f32, d_vis_mask, flags, sc->built, &go);
+  if (rc != MIRT_OK || !go) return rc;
   VisArgs q;
   q.features = reinterpret_cast<const float4*>(d_features);
   q.dirs = reinterpret_cast<const float4*>(d_dirs);
@@ -216,14 +191,10 @@ int hemisphere_visibility(MirtScene* sc, const void* d_features, int64_t n, cons
   q.root_ref = sc->root_ref;
   q.radius = radius;
   q.num_dirs = num_dirs;
-  const int opt = sc->opt.stack_lds_depth;
-  q.lds_depth = (opt >= 0 && opt < VSTACK_LDS) ? opt : VSTACK_LDS;      // tests force the spill path
-  q.gshift = 0;
-  while ((1 << q.gshift) < num_dirs) ++q.gshift;
-  const long long rows_per_block = (long long)(VBLOCK / 64) * (64 >> q.gshift);
-  const long long want = (n + rows_per_block - 1) / rows_per_block;
-  const int blocks = (int)(want < sc->vis_blocks ? want : sc->vis_blocks);
-  hipLaunchKernelGGL(hemisphere_visibility_kernel, dim3(blocks), dim3(VBLOCK), 0, stream, q);
+  q.lds_depth = query_lds_depth(sc);
+  const GroupLaunch g = group_launch(n, num_dirs, query_grid_blocks(sc, hemisphere_visibility_kernel, VWAVES_PER_SIMD, &sc->vis_blocks));
+  q.gshift = g.gshift;
+  hipLaunchKernelGGL(hemisphere_visibility_kernel, dim3(g.blocks), dim3(QUERY_BLOCK), 0, stream, q);
   MIRT_HIP(hipGetLastError());
   return MIRT_OK;
 }

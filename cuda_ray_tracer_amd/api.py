@@ -896,6 +896,8 @@ from .lighting import MIRT_LIGHT_RAW, direct_light, pack_features, direct_light_
 from .visibility import hemisphere_visibility, cosine_directions, rotations, ambient_occlusion_frame      # noqa: E402,F401
 # Indirect light at surface points (include/mirt_indirect.h): indirect.py holds that header's signature and calls
 from .indirect import indirect_light, indirect_light_frame      # noqa: E402,F401
+# Closest-point queries (include/mirt_closest.h): closest.py holds that header's signature and call
+from .closest import closest_points, pack_points      # noqa: E402,F401
 
 
 def pack_rays(origins, dirs, tmax=float("inf")):

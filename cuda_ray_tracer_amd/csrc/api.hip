@@ -359,6 +359,14 @@ int mirt_indirect_light(MirtScene* sc, const void* d_features, int64_t n, const 
   return indirect_light(sc, d_features, n, d_dirs, num_dirs, d_rot, radius, d_out_f32, d_hit_mask, flags, (hipStream_t)stream);
 }
 
+// (include/mirt_closest.h)
+int mirt_closest_points(MirtScene* sc, const void* d_points, int64_t n, void* d_hits, void* d_features, uint32_t flags, void* stream)
+{
+  if (!sc) { set_error("mirt_closest_points: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return closest_points(sc, d_points, n, d_hits, d_features, flags, (hipStream_t)stream);
+}
+
 size_t mirt_denoise_work_bytes(const MirtRenderParams* p) { return denoise_work_bytes(p); }
 
 int mirt_denoise(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, const void* d_features,

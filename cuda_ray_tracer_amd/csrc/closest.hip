@@ -1,0 +1,249 @@
+// Closest-point queries on a built scene (include/mirt_closest.h: mirt_closest_points): for each point the
+// nearest plane, sphere or triangle within the row's radius -- the admitted candidate with the smallest (dist, kind, id), which the
+// header defines over the scene's arrays, so the order of the visits is free.  Like the ray queries it reads the scene only and
+// touches no render context, counter, hand-out table or RNG table.
+//
+// closest_points_kernel  one lane = one row (grid-stride over the batch).  The planes from scalar loads, then a best-first stack walk
+//                        over the exact 64-byte node records: the squared point-box distance of both children against
+//                        (best + sigma)^2, the nearer child first, the other pushed.  best starts at the row's radius and shrinks
+//                        with every admitted candidate; sigma is the header's slack, once per row.  The loop computes distances
+//                        only; the winner's point and normal are made after it, by the same operations.  The stack is the query
+//                        kernels': [entry][lane] in LDS, deeper entries in the lane's private array.
+//                        Left-first order, stack entries that carry their box distance (so that a pop is dropped without a visit
+//                        once best has shrunk: two words per entry, half the waves) and unsquared box distances were measured and
+//                        lost: section 6o.
+#include "scene_dev.h"
+#include "host_scene.h"
+#include "shade_common.h"
+#include "../../include/mirt_closest.h"
+
+#include <cmath>
+
+namespace mirt {
+namespace {
+
+// the query kernels' budget: 64 VGPRs, 8 waves per SIMD; QUERY_STACK_LDS x 4 B x 64 lanes = 5 KiB of LDS per wave
+constexpr int CWAVES_PER_SIMD = 8;
+constexpr float SLACK = 3.814697265625e-06f;         // 2^-18 (mirt_closest.h, "Pruning")
+
+struct ClosestArgs {
+  const float4* points;           // (q, R)
+  uint32_t* hits;                 // MirtHit: 6 words
+  float4* features;               // nullable: (P, 1), (n, 0)
+  long long n;
+  const float4* nodes;            // record heap (scene_dev.h)
+  const uint32_t* unit_prim;
+  const float4* tri_verts;        // file order: p0, p1, p2 of every triangle
+  const PlaneDev* planes; int num_planes;
+  uint32_t root_ref;              // the exact records' root (REF_NONE: no primitive)
+  uint32_t prim_base16;
+  float coord_max;                // largest coordinate magnitude of the scene box
+  int lds_depth;                  // stack entries kept in LDS (<= QUERY_STACK_LDS)
+};
+
+// squared distance of q to the box [x0, x1] x [y0, y1] x [z0, z1]
+MIRT_DEV float box_dist2(float x0, float x1, float y0, float y1, float z0, float z1, const f3& q)
+{
+  const float ex = fmaxf(fmaxf(x0 - q.x, q.x - x1), 0.0f);
+  const float ey = fmaxf(fmaxf(y0 - q.y, q.y - y1), 0.0f);
+  const float ez = fmaxf(fmaxf(z0 - q.z, q.z - z1), 0.0f);
+  return ex * ex + ey * ey + ez * ez;
+}
+
+// the closest point of the triangle (a, b, c) to q: mirt_closest.h, region by region
+MIRT_DEV f3 closest_on_triangle(const f3& a, const f3& b, const f3& c, const f3& q)
+{
+  const f3 ab = b - a, ac = c - a, ap = q - a;
+  const float d1 = dot(ab, ap), d2 = dot(ac, ap);
+  if (d1 <= 0.0f && d2 <= 0.0f) return a;
+  const f3 bp = q - b;
+  const float d3 = dot(ab, bp), d4 = dot(ac, bp);
+  if (d3 >= 0.0f && d4 <= d3) return b;
+  const float vc = d1 * d4 - d3 * d2;
+  if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) return a + ab * (d1 / (d1 - d3));
+  const f3 cp = q - c;
+  const float d5 = dot(ab, cp), d6 = dot(ac, cp);
+  if (d6 >= 0.0f && d5 <= d6) return c;
+  const float vb = d5 * d2 - d1 * d6;
+  if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) return a + ac * (d2 / (d2 - d6));
+  const float va = d3 * d6 - d5 * d4;
+  const float e = d4 - d3, f = d5 - d6;
+  if (va <= 0.0f && e >= 0.0f && f >= 0.0f) return b + (c - b) * (e / (e + f));
+  const float den = 1.0f / ((va + vb) + vc);
+  return (a + ab * (vb * den)) + ac * (vc * den);
+}
+
+MIRT_DEV f3 triangle_point(const float4* tri_verts, uint32_t id, const f3& q)
+{
+  const float4* v = tri_verts + 3 * (size_t)id;
+  const float4 a = v[0], b = v[1], c = v[2];
+  return closest_on_triangle(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), q);
+}
+
+__global__ void __launch_bounds__(QUERY_BLOCK, CWAVES_PER_SIMD) closest_points_kernel(const ClosestArgs a)
+{
+  __shared__ uint32_t lds_stack[QUERY_STACK_LDS * QUERY_BLOCK];
+  uint32_t spill[STACK_TOTAL];             // (entries lds_depth.. of the lane's stack: the rarely taken spill path)
+  const int tid = threadIdx.x;
+  const long long stride = (long long)gridDim.x * QUERY_BLOCK;
+  const unsigned char* const heap = reinterpret_cast<const unsigned char*>(a.nodes);
+  // (the planes are the same for every lane and never written by a kernel: scalar loads through the constant address space)
+  typedef const PlaneDev __attribute__((address_space(4))) * ConstPlanes;
+  const ConstPlanes planes = (ConstPlanes)(unsigned long long)a.planes;
+  for (long long i = (long long)blockIdx.x * QUERY_BLOCK + tid; i < a.n; i += stride) {
+    const float4 row = a.points[i];
+    const f3 q = mk3(row.x, row.y, row.z);
+    const float R = row.w;
+    // (x - x is 0 for a finite x and NaN for an infinity or a NaN)
+    const bool live = R > 0.0f && (q.x - q.x) == 0.0f && (q.y - q.y) == 0.0f && (q.z - q.z) == 0.0f;
+    float best = R;                  // the smallest admitted distance so far; without a winner, the radius
+    uint32_t refbest = REF_NONE;     // the winner, a primitive record of the heap ...
+    int plane_id = -1;               // ... or a plane
+    if (live) {
+      for (int j = 0; j < a.num_planes; ++j) {
+        const f3 N = normalize(mk3(planes[j].nx, planes[j].ny, planes[j].nz));
+        const float dist = fabsf(dot(N, q - mk3(planes[j].px, planes[j].py, planes[j].pz)));
+        if (dist < best) { best = dist; plane_id = j; }      // (an equal distance: the lower index stays)
+      }
+    }
+    if (live && a.root_ref != REF_NONE) {
+      const float sigma = (fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z)) + a.coord_max) * SLACK;
+      float reach = best + sigma;
+      float bound2 = reach * reach;      // a box farther than this (squared) holds nothing that wins or ties
+      uint32_t cur = a.root_ref;
+      int sp = 0;
+      for (;;) {
+        const float4* rec = reinterpret_cast<const float4*>(heap + (cur << 4));
+        bool pop;
+        if (cur & REF_LEAF) {
+          float dist;
+          uint32_t id = 0u;
+          if (cur & REF_TRI) {
+            id = a.unit_prim[(cur & REF_OFFMASK) - a.prim_base16] & 0x7fffffffu;
+            dist = length(q - triangle_point(a.tri_verts, id, q));
+          } else {
+            const float4 s = rec[0];
+            dist = fabsf(length(q - mk3(s.x, s.y, s.z)) - s.w);
+          }
+          bool better = dist < best;
+          if (dist == best && (plane_id >= 0 || refbest != REF_NONE)) {
+            // a tie with the winner: (kind, id) decides -- a primitive before a plane, a sphere before a triangle, the lower index
+            if (plane_id >= 0 || (cur & REF_TRI) != (refbest & REF_TRI)) {
+              better = plane_id >= 0 || !(cur & REF_TRI);
+            } else {
+              if (!(cur & REF_TRI)) id = a.unit_prim[(cur & REF_OFFMASK) - a.prim_base16] & 0x7fffffffu;
+              better = id < (a.unit_prim[(refbest & REF_OFFMASK) - a.prim_base16] & 0x7fffffffu);
+            }
+          }
+          if (better) {
+            best = dist; refbest = cur; plane_id = -1;
+            reach = best + sigma;
+            bound2 = reach * reach;
+          }
+          pop = true;
+        } else {
+          const float4 b0 = rec[0], b1 = rec[1], b2 = rec[2];
+          const uint2 ch = *reinterpret_cast<const uint2*>(rec + 3);
+          const float l2 = box_dist2(b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, q);
+          const float r2 = box_dist2(b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, q);
+          const bool hl = !(l2 > bound2), hr = !(r2 > bound2);
+          const bool right_first = r2 < l2;      // the nearer child first
+          if (hl && hr) {
+            // (the tree is at most 58 levels deep, DESIGN.md section 1: sp stays below STACK_TOTAL; the mask only bounds the index)
+            const uint32_t later = right_first ? ch.x : ch.y;
+            if (sp < a.lds_depth) lds_stack[sp * QUERY_BLOCK + tid] = later;
+            else spill[(sp - a.lds_depth) & (STACK_TOTAL - 1)] = later;
+            ++sp;
+          }
+          cur = (hl && hr) ? (right_first ? ch.y : ch.x) : (hl ? ch.x : ch.y);
+          pop = !(hl || hr);
+        }
+        if (pop) {
+          if (sp == 0) break;
+          --sp;
+          cur = sp < a.lds_depth ? lds_stack[sp * QUERY_BLOCK + tid] : spill[(sp - a.lds_depth) & (STACK_TOTAL - 1)];
+        }
+      }
+    }
+    // the winner's record: its point and normal by the header's operations (the loop kept the distance only)
+    float t = -1.0f;
+    uint32_t kind = MIRT_HIT_NONE, id = 0u;
+    f3 P = mk3(0.0f, 0.0f, 0.0f), n = P;
+    const bool hit = plane_id >= 0 || refbest != REF_NONE;
+    if (plane_id >= 0) {
+      const f3 N = normalize(mk3(planes[plane_id].nx, planes[plane_id].ny, planes[plane_id].nz));
+      const float s = dot(N, q - mk3(planes[plane_id].px, planes[plane_id].py, planes[plane_id].pz));
+      P = q - N * s;
+      n = s < 0.0f ? -N : N;
+      kind = MIRT_HIT_PLANE; id = (uint32_t)plane_id;
+    } else if (refbest != REF_NONE) {
+      id = a.unit_prim[(refbest & REF_OFFMASK) - a.prim_base16] & 0x7fffffffu;
+      const float4* rec = a.nodes + (refbest & REF_OFFMASK);
+      if (refbest & REF_TRI) {
+        const float4 q0 = rec[0], q1 = rec[1];
+        const f3 nor = mk3(q0.w, q1.x, q1.y);
+        P = triangle_point(a.tri_verts, id, q);
+        n = dot(q - P, nor) < 0.0f ? -nor : nor;
+        kind = MIRT_HIT_TRIANGLE;
+      } else {
+        const float4 s = rec[0];
+        const f3 c = mk3(s.x, s.y, s.z), v = q - c;
+        const f3 u = normalize(v);
+        P = c + u * s.w;
+        n = length(v) < s.w ? -u : u;
+        kind = MIRT_HIT_SPHERE;
+      }
+    }
+    if (hit) t = best;
+    uint32_t* const h = a.hits + 6 * i;
+    h[0] = __float_as_uint(t);
+    h[1] = kind;
+    h[2] = id;
+    h[3] = __float_as_uint(n.x);
+    h[4] = __float_as_uint(n.y);
+    h[5] = __float_as_uint(n.z);
+    if (a.features) {
+      a.features[2 * i] = make_float4(P.x, P.y, P.z, hit ? 1.0f : 0.0f);
+      a.features[2 * i + 1] = make_float4(n.x, n.y, n.z, 0.0f);
+    }
+  }
+}
+
+} // namespace
+
+int closest_points(MirtScene* sc, const void* d_points, int64_t n, void* d_hits, void* d_features, uint32_t flags, hipStream_t stream)
+{
+  const char* const who = "mirt_closest_points";
+  if (flags != 0u) { set_error(std::string(who) + ": unknown flag bits"); return MIRT_ERR_ARG; }
+  if (n < 0) { set_error(std::string(who) + ": negative n"); return MIRT_ERR_ARG; }
+  if (n > 0 && (!d_points || !d_hits)) { set_error(std::string(who) + ": null buffer"); return MIRT_ERR_ARG; }
+  if (!is_aligned(16, (const char*)d_points, (const char*)d_features) || !is_aligned(4, (const char*)d_hits)) {
+    set_error(std::string(who) + ": d_points and d_features must be 16-byte aligned, d_hits 4-byte aligned"); return MIRT_ERR_ARG;
+  }
+  const size_t rows = (size_t)n;
+  if (n > 0 && (overlaps(d_hits, 24 * rows, d_points, 16 * rows) ||
+                (d_features && (overlaps(d_features, 32 * rows, d_points, 16 * rows) || overlaps(d_features, 32 * rows, d_hits, 24 * rows))))) {
+    set_error(std::string(who) + ": d_hits and d_features must not overlap d_points or each other"); return MIRT_ERR_ARG;
+  }
+  if (!sc->built) { set_error(std::string(who) + ": call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
+  if (n == 0) return MIRT_OK;
+  const int grid = query_grid_blocks(sc, closest_points_kernel, CWAVES_PER_SIMD, &sc->closest_blocks);
+  ClosestArgs q;
+  q.points = reinterpret_cast<const float4*>(d_points);
+  q.hits = reinterpret_cast<uint32_t*>(d_hits);
+  q.features = reinterpret_cast<float4*>(d_features);
+  q.n = n;
+  q.nodes = sc->nodes; q.unit_prim = sc->unit_prim;
+  q.tri_verts = sc->tri_verts;
+  q.planes = sc->planes; q.num_planes = sc->d.num_planes;
+  q.root_ref = sc->root_ref; q.prim_base16 = sc->prim_base / 16u;
+  q.coord_max = sc->coord_max;
+  q.lds_depth = query_lds_depth(sc);
+  const long long want = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;
+  const int blocks = (int)(want < grid ? want : grid);
+  hipLaunchKernelGGL(closest_points_kernel, dim3(blocks), dim3(QUERY_BLOCK), 0, stream, q);
+  MIRT_HIP(hipGetLastError());
+  return MIRT_OK;
+}
+
+} // namespace mirt

@@ -270,6 +270,7 @@ struct MirtScene {
   int light_blocks = 0;                    // ... and of the direct-light kernel (light.hip)
   int vis_blocks = 0;                      // ... and of the hemisphere-visibility kernel (visibility.hip)
   int indirect_blocks = 0;                 // ... and of the indirect-light kernel (indirect.hip)
+  int closest_blocks = 0;                  // ... and of the closest-point kernel (closest.hip)
   bool updated = false;                    // geometry updated in place since the last build (update.hip): mirt_camera_rays waits for the build like every other call
   // Shading values updated in place (update_shading.hip).  The three facts above are prim_flags | host_flags (MAT_* bits,
   // material_flags.h), by source: the primitives' materials -- after a material update known only to the device, until
@@ -327,6 +328,8 @@ int hemisphere_visibility(MirtScene* sc, const void* d_features, int64_t n, cons
 // indirect.hip
 int indirect_light(MirtScene* sc, const void* d_features, int64_t n, const void* d_dirs, int num_dirs, const void* d_rot, float radius,
                    void* d_out_f32, uint64_t* d_hit_mask, uint32_t flags, hipStream_t stream);
+// closest.hip
+int closest_points(MirtScene* sc, const void* d_points, int64_t n, void* d_hits, void* d_features, uint32_t flags, hipStream_t stream);
 // denoise.hip
 int hit_features(MirtScene* sc, const void* d_rays, const void* d_hits, int64_t n, void* d_features, hipStream_t stream);
 size_t denoise_work_bytes(const MirtRenderParams* p);
@@ -377,7 +380,7 @@ hipError_t persistent_grid_blocks(int device, K kernel, int block, int per_cu_fa
   return hipSuccess;
 }
 
-// The query kernels' host side (query.hip, light.hip, visibility.hip, indirect.hip; launch arithmetic: query_launch.h).
+// The query kernels' host side (query.hip, light.hip, visibility.hip, indirect.hip, closest.hip; launch arithmetic: query_launch.h).
 // Stack entries their walk keeps in LDS: the compiled size, unless the option names a smaller one (tests force the spill path).
 inline int query_lds_depth(const MirtScene* sc)
 {

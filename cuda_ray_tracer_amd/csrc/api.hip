@@ -45,7 +45,7 @@ const OptionDesc OPTIONS[] = {
   {"stack_lds_depth", &Options::stack_lds_depth, -1, 64, false}, {"refill_k", &Options::refill_k, 0, 64, false}, {"batch_k", &Options::batch_k, 1, 64, false},
   {"leaf_k", &Options::leaf_k, 0, 64, false}, {"init_k", &Options::init_k, 0, 64, false}, {"reps", &Options::reps, 0, 8, false}, {"drain_lanes", &Options::drain_lanes, 0, 64, false},
   {"chunk_shift", &Options::chunk_shift, 0, 12, false}, {"trace_waves", &Options::trace_waves, 0, 1 << 20, false}, {"sched", &Options::sched, 0, 2, false},
-  {"specialise", &Options::specialise, 0, 1, false}, {"slab_log2", &Options::slab_log2, 8, 30, false},
+  {"specialise", &Options::specialise, 0, 1, false}, {"ray_start_lds", &Options::ray_start_lds, 0, 1, false}, {"slab_log2", &Options::slab_log2, 8, 30, false},
   {"wf_pool", &Options::wf_pool, 256, 1 << 24, false}, {"wf_refill_k", &Options::wf_refill_k, 1, 64, false},
 };
 
@@ -99,6 +99,7 @@ int mirt_scene_get_option(const MirtScene* sc, const char* name, int* value)
   if (strcmp(name, "tree_depth") == 0) { *value = sc->built ? sc->tree_depth : -1; return MIRT_OK; }
   if (strcmp(name, "stack_lds_capacity") == 0) { *value = STACK_LDS_CAPACITY; return MIRT_OK; }
   if (strcmp(name, "stack_lds_only") == 0) { *value = sc->last_lds_only ? 1 : 0; return MIRT_OK; }
+  if (strcmp(name, "stack_lds_slots") == 0) { *value = sc->last_stack_slots; return MIRT_OK; }
   set_error(std::string("mirt_scene_get_option: unknown option ") + name);
   return MIRT_ERR_ARG;
 }

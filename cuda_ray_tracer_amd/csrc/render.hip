@@ -68,14 +68,26 @@ MIRT_DEV bool triangle_leaf_reached(const RenderArgs* __restrict__ ap, uint32_t 
 // SPECX & SPEC_LDS_STACK: the traversal stack never leaves LDS -- push and pop have no arm for the global spill area, and an
 // empty stack is a REF_NONE at its bottom, not a count of zero.  Selected by the plan (render_plan.h, lds_only) for a binary
 // walk over a tree whose depth proves that the entries fit; see MIRT_PUSH below.
+// SPECX & SPEC_START_LDS (with SPEC_LDS_STACK, on the sphere-only quantised records, no point lights): the loop header's ray
+// start reads nothing through the vector memory path.  What that arm looks at -- root reference, counts of planes and suns,
+// shadow-ray mode -- and the sun record each lane indexes are written once per wave into the first stack slot's 256 bytes of
+// LDS; the stack itself starts one slot later and has START_LDS_SLOTS slots, which the plan has shown to be enough (start_lds).
 constexpr int SPEC_LDS_STACK = 8;
+constexpr int SPEC_START_LDS = 16;
+// a sun as the loop header's ray start reads it from LDS: LightDev's direction and reciprocal
+struct SunLds { float nx, ny, nz, ix, iy, iz; };
+struct StartLdsArgs : HotArgs { const SunLds* suns; };      // (hides HotArgs::suns: batch_next indexes whichever it is given)
+static_assert(sizeof(SunLds) == 24 && offsetof(LightDev, ix) == offsetof(LightDev, nx) + 12, "six consecutive words of a LightDev");
 template <bool COUNT, int TABLES, bool QN, int SPECX = 0>
 __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel(const RenderArgs* __restrict__ ap, const HotArgs h)
 {
-  constexpr int SPEC = SPECX & ~SPEC_LDS_STACK;
+  constexpr int SPEC = SPECX & ~(SPEC_LDS_STACK | SPEC_START_LDS);
   constexpr bool LDS_ONLY = (SPECX & SPEC_LDS_STACK) != 0;
+  constexpr bool START_LDS = (SPECX & SPEC_START_LDS) != 0;
   constexpr bool NOTRI = (SPEC & SPEC_NOTRI) != 0;
   constexpr bool WIDE = QN && !NOTRI;
+  static_assert(!START_LDS || (LDS_ONLY && QN && NOTRI && (SPEC & SPEC_NOBULB) != 0), "the ray-start block holds suns only, and its room comes from a stack that cannot spill");
+  constexpr int HEAD_AT = 0, SUNS_AT = 16, STACK_AT = START_LDS ? TRACE_BLOCK * 4 : 0;      // START_LDS: the ray-start block in slot 0's bytes, the stack after it
   static_assert(!(LDS_ONLY && WIDE), "the wide walk pushes up to three entries per step: the depth of the tree does not bound its stack");
   // a finished shadow ray towards a point light that hit something, in a walk that is not the reference's own: the hit is vetted
   // by the shade phase before batch_next reads "occluded" off it (hit_needs_literal_walk); no such lanes in a kernel without bulbs
@@ -88,7 +100,7 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
   // Likewise eight words of shading state that the traversal loop and its batch transitions never touch (radiance so far,
   // alpha, the diffuse weight, the node's index of refraction).
   __shared__ uint4 lds_park[2][TRACE_BLOCK];
-  uint32_t* const lds_stack = reinterpret_cast<uint32_t*>(lds_raw);
+  uint32_t* const lds_stack = reinterpret_cast<uint32_t*>(lds_raw + STACK_AT);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   (void)lane;
@@ -123,6 +135,15 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
   lds_rng[1][tid] = make_uint4(0, 0, 0, 0);
   lds_park[0][tid] = make_uint4(0, 0, 0, 0);
   lds_park[1][tid] = make_uint4(0, 0, 0, __float_as_uint(1.458f));
+  if (START_LDS) {
+    // once per wave: the head (root reference, planes, suns, shadow-ray mode) and six words per sun (the plan: num_suns <=
+    // START_LDS_SUNS; a workgroup is one wave)
+    static_assert(TRACE_BLOCK == 64 && 6 * START_LDS_SUNS <= TRACE_BLOCK, "one pass of the wave fills the block");
+    if (tid == 0) *reinterpret_cast<uint4*>(lds_raw + HEAD_AT) = make_uint4(ap->root_ref, (uint32_t)ap->num_planes, (uint32_t)ap->num_suns, (uint32_t)ap->shadow_anyhit);
+    if (tid < 6 * START_LDS_SUNS)
+      reinterpret_cast<float*>(lds_raw + SUNS_AT)[tid] = tid < 6 * ap->num_suns ? (&ap->suns[tid / 6].nx)[tid % 6] : 0.0f;
+    __syncthreads();
+  }
   for (;;) {
     // ================= shade / refill phase: lanes that are not traversing =================
     // The shade phase reads the frame's RenderArgs through a pointer the optimiser cannot see through, so that those
@@ -234,7 +255,20 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
       if (nwait >= h.refill_k || (drain && nwait > 0)) break;
       // lanes whose batch ray finished move on to the next ray of their batch (cheap; done in groups)
       if (bm != 0 && (__popcll(bm) >= h.batch_k || tm == 0 || drain)) {
-        if (LDS_ONLY) {
+        if (START_LDS) {
+          // The values the arm merely looks at and the sun record each lane indexes come from the wave's LDS block: no
+          // vector-memory load, no wait on one, before start_ray.  Planes and the records' grid stay scalar loads through `h`.
+          if (pend) {
+            const uint4 hd = *reinterpret_cast<const uint4*>(lds_raw + HEAD_AT);
+            StartLdsArgs hh;
+            static_cast<HotArgs&>(hh) = h;
+            hh.root_ref = __builtin_amdgcn_readfirstlane(hd.x); hh.num_planes = (int)__builtin_amdgcn_readfirstlane(hd.y);
+            hh.num_suns = (int)__builtin_amdgcn_readfirstlane(hd.z); hh.num_bulbs = 0; hh.shadow_anyhit = (int)__builtin_amdgcn_readfirstlane(hd.w);
+            hh.suns = reinterpret_cast<const SunLds*>(lds_raw + SUNS_AT);
+            batch_next<COUNT, QN, StartLdsArgs, SPEC>(hh, S, cn);
+            S.tos = REF_NONE;      // (the next ray's empty stack)
+          }
+        } else if (LDS_ONLY) {
           // This kernel keeps only the arm's data pointers that are read through (planes, the records' grid) in scalar registers.
           // The values the arm merely looks at -- the root reference, the counts of planes and lights, the shadow-ray mode -- and
           // the light array's address are read where the arm runs, through the same opaque pointer as the shade phase: four
@@ -774,7 +808,8 @@ static int fill_args(const RenderCall& c, RenderCtx& cx, const CallPlan& pl, int
   a.gi = sc->d.gi; a.spp = pl.args_spp; a.expose = sc->d.expose;
   a.sample_first = c.sample_first; a.sample_count = c.sample_count; a.seed_per_pixel = pl.per_pixel_seed ? 1 : 0;
   a.nodes = sc->nodes; a.unit_prim = sc->unit_prim; a.mats = sc->mats;
-  a.root_ref = pl.qn ? (pl.notri ? sc->root_ref_q : sc->root_ref_w) : sc->root_ref; a.num_spheres = sc->Ns; a.num_prims = sc->N;
+  a.root_ref = pl.qn ? (pl.notri ? sc->root_ref_q : sc->root_ref_w) : sc->root_ref;
+  a.num_spheres = sc->Ns; a.num_prims = sc->N;
   a.qparams = pl.qn ? sc->qparams : nullptr;
   a.tri_boxes = sc->tri_boxes;
   a.prim_base16 = sc->prim_base / 16u;
@@ -894,7 +929,7 @@ static int sample_table_finish(MirtScene* sc, hipStream_t stream)
 
 // one instantiation per form of the random-number tables (device_common.h, xw_init), per node format and per specialisation:
 // 2 (counting) x 2 (tables) x 8 = 32 kernels, and the LDS-only stack (SPEC_LDS_STACK) for the five of the eight that walk a
-// binary tree: 20 more
+// binary tree: 20 more; the form with the ray-start block (SPEC_START_LDS) of the sphere-only one among those: 4 more
 using TraceKernel = void (*)(const RenderArgs*, HotArgs);
 template <bool C, bool Q, int P>
 static TraceKernel trace_kernel_tables(bool t8) { return t8 ? trace_kernel<C, 8, Q, P> : trace_kernel<C, 4, Q, P>; }
@@ -902,6 +937,7 @@ template <bool C>
 static TraceKernel trace_kernel_spec(bool t8, const CallPlan& pl)
 {
   const bool both = pl.nobulb && pl.nopend;
+  if (pl.start_lds) return trace_kernel_tables<C, true, SPEC_START_LDS | SPEC_LDS_STACK | SPEC_NOTRI | SPEC_NOBULB | SPEC_NOPEND>(t8);      // (the plan: qn, notri, nobulb, nopend)
   if (pl.lds_only) {
     constexpr int L = SPEC_LDS_STACK;
     if (pl.qn) return both ? trace_kernel_tables<C, true, L | SPEC_NOTRI | SPEC_NOBULB | SPEC_NOPEND>(t8) : trace_kernel_tables<C, true, L | SPEC_NOTRI>(t8);      // (the plan: notri)
@@ -1025,6 +1061,7 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
   cx.launches = pl.nslabs;
   cx.node_bytes = pl.node_bytes;
   sc->last_lds_only = pl.lds_only;
+  sc->last_stack_slots = pl.start_lds ? START_LDS_SLOTS : STACK_LDS;
   MIRT_HIP(hipEventRecord(cx.ev1, stream));
   for (int slab = 0; slab < pl.nslabs; ++slab) {
     const long long p0 = (long long)slab * pl.slab_pixels;

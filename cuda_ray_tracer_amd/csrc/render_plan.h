@@ -24,6 +24,13 @@ constexpr int STACK_LDS = MIRT_STACK_LDS;
 // Entries the trace kernel's stack holds without the global spill area: the top entry in a register (Lane::tos) and entries
 // 1 .. STACK_LDS - 1 in LDS slots of the same number.  Slot 0 never holds an entry (render.hip, MIRT_PUSH).
 constexpr int STACK_LDS_CAPACITY = STACK_LDS;
+// The kernel with the ray-start block (render.hip, SPEC_START_LDS).  The LDS-only kernel's walk never holds more than D entries
+// (the argument at MIRT_PUSH), so a tree with D < STACK_LDS leaves the last slot of every lane untouched: this kernel moves its
+// stack up by one slot and keeps, in the 256 bytes that frees per wave, what the loop header's ray start reads -- one 16-byte
+// head (root reference, planes, suns, shadow-ray mode) and up to START_LDS_SUNS sun records of 24 bytes.
+constexpr int START_LDS_SLOTS = STACK_LDS - 1;
+constexpr int START_LDS_SUNS = 10;
+static_assert(16 + START_LDS_SUNS * 24 <= TRACE_BLOCK * 4, "head and suns fit the bytes of one stack slot");
 constexpr int MAX_CHUNK_SHIFT = 8, MIN_CHUNK_SHIFT = 6;   // a wave takes 64..256 consecutive samples from the frame per atomic
 // node record word 14 (after the two child references): which descent orders the node allows
 constexpr uint32_t NODE_SWAP_PURE = 1u;       // both subtrees hold spheres only: near-child-first cannot change the closest hit
@@ -48,6 +55,7 @@ struct Options {
   int skip_unlit = 1;          // 0: shadow rays towards lights the shading normal faces away from are traced as well (draw.cu:342-374 traces them all)
   int qnodes = 1;              // quantised node records in the single-kernel path: 0 never; 1 sphere-only scenes (traversal >= 1) and scenes with
                                // triangles of 65536 primitives or more (wide records, traversal = 1); 2 every scene
+  int ray_start_lds = 1;       // 1: the sphere-only LDS-only kernel whose loop header starts rays from values kept in LDS, where the plan allows (plan_call)
   int specialise = 1;          // kernels compiled without what the scene does not have: point lights; transparency and gi (SPEC_*, shade_common.h)
   int sched = 2;               // longest-first hand-out measured on the first call of a shape: 2 by sample (stable within a cost class), 1 by chunk (one-slab calls), 0 off
   int slab_log2 = 28;          // a call is rendered in slabs of at most 2^slab_log2 samples (4 GiB of per-sample workspace; 2^26: +1.8 % on config 5)
@@ -105,6 +113,7 @@ struct CallPlan {
   // thresholds by kind of kernel
   int refill_k = 0, init_k = 0, leaf_k = 0, reps = 0, lds_depth = 0;
   bool lds_only = false;                   // the trace kernel compiled without the spill arm of push and pop (SPEC_LDS_STACK)
+  bool start_lds = false;                  // ... and with the loop header's ray-start values in LDS, the stack one slot shorter (SPEC_START_LDS)
   HandOut hand_out = HAND_FRAME;
 };
 
@@ -162,6 +171,10 @@ inline CallPlan plan_call(const SceneFacts& s, const Options& opt, const CallSha
   // entries (render.hip, next to MIRT_PUSH).  Only with the option at its default: any explicit value, the compiled size
   // included, keeps the general kernel -- that is how the tests force the spill path and how the two kernels are compared.
   pl.lds_only = !wavefront && opt.stack_lds_depth < 0 && (!pl.qn || pl.notri) && s.tree_depth >= 0 && s.tree_depth <= STACK_LDS_CAPACITY;
+  // The kernel with the ray-start block: the sphere-only quantised kernel without point lights, transparency or gi (the only
+  // LDS-only kernel compiled in that form), a tree that leaves one stack slot free, no more suns than the block has room for.
+  pl.start_lds = pl.lds_only && opt.ray_start_lds != 0 && pl.qn && pl.notri && pl.nobulb && pl.nopend && s.tree_depth <= START_LDS_SLOTS &&
+                 s.num_suns <= START_LDS_SUNS;
   // Thresholds of the two expensive divergent pieces of work, measured per kind of kernel (round 3, tools/r03_i.sh, r03_x.sh): lanes
   // wait to shade until refill_k of them do, lanes without a sample until init_k of them do.  Sphere-only scenes 32 / 10; wide
   // records (2 M-primitive scene) 24 / 8; exact records (redchair.txt) 64 / 64 -- with the samples handed out by cost class

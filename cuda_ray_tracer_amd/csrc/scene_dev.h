@@ -240,6 +240,7 @@ struct MirtScene {
   float coord_max = 0.0f;               // largest |coordinate| of the scene box (set by the build)
   bool grid_ok = false;                 // the grid of the quantised records resolves the scene's coordinates (set by the build): they may be walked
   int tree_depth = -1;                  // D: the most internal nodes on a root-to-leaf path (set by the build; -1: not built).  Bounds the binary walk's stack
+  int last_stack_slots = 0;             // ... LDS slots of that kernel's traversal stack, "stack_lds_slots" (0: nothing rendered yet)
   bool last_lds_only = false;           // the most recent render's plan chose the trace kernel without a stack-spill arm (mirt_scene_get_option, "stack_lds_only")
   // render workspaces: MIRT_MAX_FRAMES contexts so that several frames can be in flight on different streams (the next frame's blocks fill the
   // CUs the draining frame frees); a context is reused only after its previous frame has finished

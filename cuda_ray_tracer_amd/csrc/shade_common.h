@@ -505,7 +505,7 @@ MIRT_DEV void batch_next(const Args& a, Lane& S, Counters& cn)
     if (COUNT) cn.shadow_rays++;
     if (NOBULB || S.li < a.num_suns) {
       // direction and its reciprocal are per-light constants (host-computed, same arithmetic)
-      const LightDev& lt = a.suns[S.li];
+      const auto& lt = a.suns[S.li];      // (a LightDev, or the SPEC_START_LDS kernel's LDS copy of these six words)
       S.d = mk3(lt.nx, lt.ny, lt.nz); S.inv = mk3(lt.ix, lt.iy, lt.iz);
     } else {
       const LightDev& lt = a.bulbs[S.li - a.num_suns];

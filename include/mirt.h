@@ -118,6 +118,10 @@ void mirt_scene_destroy(MirtScene* sc);
  *     "specialise"        0/1 (default 1): a scene without point lights (and, sphere-only scenes, without transparent materials
  *                         and gi) is rendered by the kernel compiled without those features (same pixels and counters;
  *                         0: the general kernel)
+ *     "ray_start_lds"     0/1 (default 1): a sphere-only scene without point lights, transparent materials and gi, with at most
+ *                         ten suns and a tree at most 23 internal nodes deep, is rendered by the kernel whose traversal loop
+ *                         starts the next ray of a batch from values kept in LDS, in the bytes of a stack slot such a tree never
+ *                         fills (same pixels and counters; 0: the kernel that loads them from memory)
  *     "wavefront"         0/1: the trace/shade kernel pair instead of the single kernel
  *     "slab_log2"         (default 28) a call is rendered in slabs of at most 2^slab_log2 samples: 16 B of workspace per
  *                         sample, i.e. at most 4 GiB per frame in flight, however large the frame
@@ -129,14 +133,16 @@ void mirt_scene_destroy(MirtScene* sc);
  * Environment variables MIRT_<NAME> override the defaults of the TUNING values once, when the scene is created (the mode
  * switches -- bounds_as_shipped, traversal, wavefront, qnodes, shadow_anyhit, skip_unlit -- only with MIRT_ALLOW_ENV=1); nothing
  * reads the environment during a render.
- * mirt_scene_get_option also reads three facts about the traversal stack of the single-kernel path (mirt_scene_set_option does
+ * mirt_scene_get_option also reads four facts about the traversal stack of the single-kernel path (mirt_scene_set_option does
  * not know them):
  *     "tree_depth"         D, the most internal nodes on any root-to-leaf path of the built tree (-1 before a build); every
  *                          mirt_build_lbvh recomputes it.  A walk over two-child records keeps at most D entries pending
  *     "stack_lds_capacity" entries the kernel's stack holds before it spills to global memory
  *     "stack_lds_only"     1 if the most recent render call ran the kernel that has no spill path at all: chosen when
  *                          D <= stack_lds_capacity, the walk is over two-child records (not the wide ones) and "stack_lds_depth"
- *                          is at its default, -1 -- any explicit value, the compiled size included, keeps the general kernel */
+ *                          is at its default, -1 -- any explicit value, the compiled size included, keeps the general kernel
+ *     "stack_lds_slots"    LDS slots of the traversal stack of the kernel the most recent render call ran (0 before a render):
+ *                          stack_lds_capacity, or one fewer when "ray_start_lds" chose its kernel */
 #define MIRT_TRAVERSAL_REFERENCE 0
 #define MIRT_TRAVERSAL_ORDERED 1
 #define MIRT_TRAVERSAL_ORDERED_ALL 2

@@ -84,6 +84,15 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
   constexpr int SPEC = SPECX & ~(SPEC_LDS_STACK | SPEC_START_LDS);
   constexpr bool LDS_ONLY = (SPECX & SPEC_LDS_STACK) != 0;
   constexpr bool START_LDS = (SPECX & SPEC_START_LDS) != 0;
+  // CUR_MARK: inside the traversal loop's steps a lane that is not traversing holds S.cur == REF_NONE, and the steps read that
+  // instead of S.trav (a bool the compiler keeps as a byte per lane: moves, a select in the pop and a mask rebuilt per step).
+  // REF_NONE has the REF_LEAF bit, so "(int)S.cur >= 0" is "traversing, at an internal node" in one compare.  S.trav is brought
+  // up to date once per header pass, after the steps; everything outside them reads S.trav as before.  Only the kernel that
+  // starts rays from LDS takes this form: in the other LDS-only sphere kernel it put scalar-register spill reloads back into the
+  // loop.
+  constexpr bool CUR_MARK = START_LDS;
+  static_assert(!CUR_MARK || LDS_ONLY, "the pop that empties an LDS-only stack yields REF_NONE");
+  static_assert((REF_NONE & REF_LEAF) != 0, "REF_NONE reads as a leaf reference");
   constexpr bool NOTRI = (SPEC & SPEC_NOTRI) != 0;
   constexpr bool WIDE = QN && !NOTRI;
   static_assert(!START_LDS || (LDS_ONLY && QN && NOTRI && (SPEC & SPEC_NOBULB) != 0), "the ray-start block holds suns only, and its room comes from a stack that cannot spill");
@@ -293,6 +302,8 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
       // them, and with ~45 live lanes nearly every iteration has a lane or two at a primitive.  So lanes that reach a
       // primitive wait until leaf_k of them have one pending (or nothing else is left to do): the primitive code then
       // runs in a fraction of the iterations.  Each ray still performs exactly the same sequence of steps.
+      // (nothing reads S.cur of a lane that is not traversing: a ray start overwrites it, the shade phase goes by S.refbest)
+      if (CUR_MARK && !S.trav) S.cur = REF_NONE;
       const bool leaf0 = S.trav && (S.cur & REF_LEAF) != 0;
       const unsigned long long lm = __ballot(leaf0);
       const bool do_leaf0 = __popcll(lm) >= h.leaf_k || __ballot(S.trav && !leaf0) == 0 || drain;
@@ -303,9 +314,9 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
       int reps = h.reps;
       if (LDS_ONLY) asm volatile("" : "+s"(reps));
       for (int rep = 0; rep < reps; ++rep) {
-      const bool leaf = S.trav && (S.cur & REF_LEAF) != 0;
+      const bool leaf = (CUR_MARK ? S.cur != REF_NONE : S.trav) && (S.cur & REF_LEAF) != 0;
       const bool do_leaf = rep == 0 && do_leaf0;
-      if (S.trav && (!leaf || do_leaf)) {
+      if (CUR_MARK ? (int)S.cur >= 0 || (leaf && do_leaf) : S.trav && (!leaf || do_leaf)) {
         if (COUNT) ++S.steps;      // (scheduling statistic: the frames that measure their chunks run the counting kernels)
         // one record per step: a node (64 B: two child boxes + two child references) or a primitive (sphere 16 B,
         // triangle 48 B), addressed by one scalar base (the record heap) + a 32-bit byte offset.  Each kind loads the
@@ -342,8 +353,10 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
           }
           S.tbest = closer ? t : S.tbest;
           S.refbest = closer ? S.cur : S.refbest;
-          S.trav = !(closer && S.shadow && t < S.limit);      // any-hit exit
-          pop = S.trav;
+          // any-hit exit (LDS_ONLY: the entries it leaves on the stack go at the next ray start, S.tos = REF_NONE)
+          pop = !(closer && S.shadow && t < S.limit);
+          if (CUR_MARK) { if (!pop) S.cur = REF_NONE; }
+          else S.trav = pop;
         } else {
           if (COUNT) cn.internal_visits++;
           // hit_aabb_adapted, bvh_traversal.cu:11-44, on both children
@@ -423,7 +436,7 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
           if (LDS_ONLY) {
             // (the walk ends on the REF_NONE below the entries; popping it leaves the depth at zero and reads slot 0 again)
             S.cur = S.tos;
-            S.trav = S.cur != REF_NONE;
+            if (!CUR_MARK) S.trav = S.cur != REF_NONE;
             S.sp = (int)__builtin_elementwise_sub_sat((uint32_t)S.sp, 1u);
             S.tos = lds_stack[S.sp * TRACE_BLOCK + tid];
           } else {
@@ -436,6 +449,7 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
         }
       }
       }
+      if (CUR_MARK) S.trav = S.cur != REF_NONE;
     }
   }
 

@@ -899,6 +899,9 @@ from .indirect import indirect_light, indirect_light_frame      # noqa: E402,F40
 # Closest-point queries (include/mirt_closest.h): closest.py holds that header's signature and call
 from .closest import closest_points, pack_points      # noqa: E402,F401
 
+# Multi-hit ray queries (include/mirt_multihit.h): multihit.py holds that header's signature and calls
+from .multihit import trace_rays_multi, count_hits      # noqa: E402,F401
+
 
 def pack_rays(origins, dirs, tmax=float("inf")):
     """float32 [n, 8] MirtRay rows from origins [n, 3] (or [3]), directions [n, 3] (any non-zero length) and tmax (a number or

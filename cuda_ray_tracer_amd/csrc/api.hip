@@ -368,6 +368,14 @@ int mirt_closest_points(MirtScene* sc, const void* d_points, int64_t n, void* d_
   return closest_points(sc, d_points, n, d_hits, d_features, flags, (hipStream_t)stream);
 }
 
+// (include/mirt_multihit.h)
+int mirt_trace_rays_multi(MirtScene* sc, const void* d_rays, int64_t num_rays, int k, void* d_hits, uint32_t* d_counts, uint32_t flags, void* stream)
+{
+  if (!sc) { set_error("mirt_trace_rays_multi: null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return trace_rays_multi(sc, d_rays, num_rays, k, d_hits, d_counts, flags, (hipStream_t)stream);
+}
+
 size_t mirt_denoise_work_bytes(const MirtRenderParams* p) { return denoise_work_bytes(p); }
 
 int mirt_denoise(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, const void* d_features,

@@ -204,6 +204,23 @@ def lib():
     return L
 
 
+_applied = {}      # id of an extension's signature table -> the library it was last applied to
+
+
+def extension_lib(signatures):
+    """lib() with an extension header's table (symbol -> (restype, argtypes)) applied, once per loaded library.  A library
+    without one of its symbols is an error here: there is no other implementation."""
+    L = lib()
+    if _applied.get(id(signatures)) is not L:
+        for name, (restype, argtypes) in signatures.items():
+            f = getattr(L, name, None)
+            if f is None:
+                raise MirtError(-1, f"{LIB_PATH} does not export {name}: rebuild it with `python -m cuda_ray_tracer_amd.build`")
+            f.restype, f.argtypes = restype, argtypes
+        _applied[id(signatures)] = L
+    return L
+
+
 def _check(rc):
     if rc != MIRT_OK:
         raise MirtError(rc, lib().mirt_last_error().decode("utf-8", "replace"))

@@ -38,12 +38,8 @@ def _stale(target, deps):
 
 def _all_deps():
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
-    deps.append(os.path.join(HERE, "..", "include", "mirt.h"))
-    deps.append(os.path.join(HERE, "..", "include", "mirt_light.h"))
-    deps.append(os.path.join(HERE, "..", "include", "mirt_visibility.h"))
-    deps.append(os.path.join(HERE, "..", "include", "mirt_indirect.h"))
-    deps.append(os.path.join(HERE, "..", "include", "mirt_closest.h"))
-    deps.append(os.path.join(HERE, "..", "include", "mirt_multihit.h"))
+    include = os.path.join(HERE, "..", "include")
+    deps += [os.path.join(include, f) for f in os.listdir(include) if f.startswith("mirt") and f.endswith(".h")]
     deps.append(os.path.abspath(__file__))
     return deps
 

@@ -2,7 +2,7 @@
 
 mirt_closest.h is an extension header like mirt_light.h, mirt_visibility.h and mirt_indirect.h: binding.SIGNATURES stays the table
 of include/mirt.h, the other modules' tables those of their headers, and the one entry point more lives here.
-tests/test_closest_abi.py holds the table to the header the way tests/test_binding_header.py holds binding.py to mirt.h.
+tests/test_extension_abi.py holds the table to the header the way tests/test_binding_header.py holds binding.py to mirt.h.
 
 Needs ctypes only: torch and numpy are imported when a call needs them.
 """
@@ -18,22 +18,10 @@ CLOSEST_SIGNATURES = {
     "mirt_closest_points": (_int, [_vp, _vp, _i64, _vp, _vp, _u32, _vp]),
 }
 
-_applied = None
-
 
 def lib():
-    """binding.lib() with the signatures of mirt_closest.h applied.  A library without the symbol is an error here: there is no
-    other implementation."""
-    global _applied
-    L = binding.lib()
-    if _applied is not L:
-        for name, (restype, argtypes) in CLOSEST_SIGNATURES.items():
-            f = getattr(L, name, None)
-            if f is None:
-                raise binding.MirtError(-1, f"{binding.LIB_PATH} does not export {name}: rebuild it with `python -m cuda_ray_tracer_amd.build`")
-            f.restype, f.argtypes = restype, argtypes
-        _applied = L
-    return L
+    """binding.lib() with the signatures of mirt_closest.h applied."""
+    return binding.extension_lib(CLOSEST_SIGNATURES)
 
 
 def closest_points(raw, d_points, d_hits, d_features=None, stream=None):

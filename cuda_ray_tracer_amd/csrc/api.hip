@@ -66,6 +66,14 @@ void options_from_env(Options& o)
 
 int scene_create(const MirtSceneDesc* d, int device, MirtScene** out);
 
+// the prologue of an entry point that works on a scene's device: "<who>: null scene", then the device made current
+int enter_scene(const MirtScene* sc, const char* who)
+{
+  if (!sc) { set_error(std::string(who) + ": null scene"); return MIRT_ERR_ARG; }
+  MIRT_HIP(hipSetDevice(sc->device));
+  return MIRT_OK;
+}
+
 // mirt_get_stats: take a context's overflow count and zero it in one atomic step (a frame issued meanwhile from another host
 // thread keeps every increment: it lands either in this reading or in the next)
 __global__ void take_overflow_kernel(unsigned long long* counters)
@@ -244,8 +252,7 @@ void mirt_scene_destroy(MirtScene* sc)
 
 int mirt_build_lbvh(MirtScene* sc, void* stream, float* build_ms)
 {
-  if (!sc) { set_error("mirt_build_lbvh: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_build_lbvh"));
   int rc = build_lbvh(sc, (hipStream_t)stream);
   if (rc == MIRT_OK) sc->updated = false;
   if (rc == MIRT_OK && build_ms) *build_ms = sc->build_ms;
@@ -312,8 +319,7 @@ int mirt_scatter_part(const MirtRenderParams* p, const void* d_part_rgba8, void*
 
 int mirt_trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits, uint32_t flags, void* stream)
 {
-  if (!sc) { set_error("mirt_trace_rays: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_trace_rays"));
   return trace_rays(sc, d_rays, num_rays, d_hits, flags, (hipStream_t)stream);
 }
 
@@ -329,16 +335,14 @@ int mirt_camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, voi
 
 int mirt_hit_features(MirtScene* sc, const void* d_rays, const void* d_hits, int64_t n, void* d_features, void* stream)
 {
-  if (!sc) { set_error("mirt_hit_features: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_hit_features"));
   return hit_features(sc, d_rays, d_hits, n, d_features, (hipStream_t)stream);
 }
 
 // (include/mirt_light.h)
 int mirt_direct_light(MirtScene* sc, const void* d_features, int64_t n, void* d_out_f32, uint64_t* d_lit_mask, uint32_t flags, void* stream)
 {
-  if (!sc) { set_error("mirt_direct_light: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_direct_light"));
   return direct_light(sc, d_features, n, d_out_f32, d_lit_mask, flags, (hipStream_t)stream);
 }
 
@@ -346,8 +350,7 @@ int mirt_direct_light(MirtScene* sc, const void* d_features, int64_t n, void* d_
 int mirt_hemisphere_visibility(MirtScene* sc, const void* d_features, int64_t n, const void* d_dirs, int num_dirs, const void* d_rot, float radius,
                                void* d_out_f32, uint64_t* d_vis_mask, uint32_t flags, void* stream)
 {
-  if (!sc) { set_error("mirt_hemisphere_visibility: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_hemisphere_visibility"));
   return hemisphere_visibility(sc, d_features, n, d_dirs, num_dirs, d_rot, radius, d_out_f32, d_vis_mask, flags, (hipStream_t)stream);
 }
 
@@ -355,24 +358,21 @@ int mirt_hemisphere_visibility(MirtScene* sc, const void* d_features, int64_t n,
 int mirt_indirect_light(MirtScene* sc, const void* d_features, int64_t n, const void* d_dirs, int num_dirs, const void* d_rot, float radius,
                         void* d_out_f32, uint64_t* d_hit_mask, uint32_t flags, void* stream)
 {
-  if (!sc) { set_error("mirt_indirect_light: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_indirect_light"));
   return indirect_light(sc, d_features, n, d_dirs, num_dirs, d_rot, radius, d_out_f32, d_hit_mask, flags, (hipStream_t)stream);
 }
 
 // (include/mirt_closest.h)
 int mirt_closest_points(MirtScene* sc, const void* d_points, int64_t n, void* d_hits, void* d_features, uint32_t flags, void* stream)
 {
-  if (!sc) { set_error("mirt_closest_points: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_closest_points"));
   return closest_points(sc, d_points, n, d_hits, d_features, flags, (hipStream_t)stream);
 }
 
 // (include/mirt_multihit.h)
 int mirt_trace_rays_multi(MirtScene* sc, const void* d_rays, int64_t num_rays, int k, void* d_hits, uint32_t* d_counts, uint32_t flags, void* stream)
 {
-  if (!sc) { set_error("mirt_trace_rays_multi: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_trace_rays_multi"));
   return trace_rays_multi(sc, d_rays, num_rays, k, d_hits, d_counts, flags, (hipStream_t)stream);
 }
 
@@ -407,29 +407,25 @@ int mirt_scene_set_camera(MirtScene* sc, const MirtCamera* cam)
 
 int mirt_scene_update_spheres(MirtScene* sc, const void* d_spheres, int first, int count, void* stream)
 {
-  if (!sc) { set_error("mirt_scene_update_spheres: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_scene_update_spheres"));
   return update_spheres(sc, d_spheres, first, count, (hipStream_t)stream);
 }
 
 int mirt_scene_update_triangles(MirtScene* sc, const void* d_verts, int first, int count, void* stream)
 {
-  if (!sc) { set_error("mirt_scene_update_triangles: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_scene_update_triangles"));
   return update_triangles(sc, d_verts, first, count, (hipStream_t)stream);
 }
 
 int mirt_scene_get_spheres(MirtScene* sc, int first, int count, void* d_xyzr_out, void* stream)
 {
-  if (!sc) { set_error("mirt_scene_get_spheres: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_scene_get_spheres"));
   return get_spheres(sc, first, count, d_xyzr_out, (hipStream_t)stream);
 }
 
 int mirt_scene_get_triangles(MirtScene* sc, int first, int count, void* d_verts_out, void* stream)
 {
-  if (!sc) { set_error("mirt_scene_get_triangles: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_scene_get_triangles"));
   return get_triangles(sc, first, count, d_verts_out, (hipStream_t)stream);
 }
 
@@ -443,8 +439,7 @@ int mirt_scene_get_lights(const MirtScene* sc, MirtLight* suns_out, MirtLight* b
 
 int mirt_scene_set_lights(MirtScene* sc, const MirtLight* suns, const MirtLight* bulbs, void* stream)
 {
-  if (!sc) { set_error("mirt_scene_set_lights: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_scene_set_lights"));
   return set_lights(sc, suns, bulbs, (hipStream_t)stream);
 }
 
@@ -460,8 +455,7 @@ int mirt_scene_get_planes(const MirtScene* sc, int first, int count, MirtPlane* 
 
 int mirt_scene_set_planes(MirtScene* sc, const MirtPlane* planes, int first, int count, void* stream)
 {
-  if (!sc) { set_error("mirt_scene_set_planes: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_scene_set_planes"));
   return set_planes(sc, planes, first, count, (hipStream_t)stream);
 }
 
@@ -483,37 +477,32 @@ int mirt_scene_set_shading(MirtScene* sc, const MirtShading* sh)
 
 int mirt_scene_update_sphere_materials(MirtScene* sc, const void* d_mats, int first, int count, void* stream)
 {
-  if (!sc) { set_error("mirt_scene_update_sphere_materials: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_scene_update_sphere_materials"));
   return update_materials(sc, "mirt_scene_update_sphere_materials", d_mats, 0, sc->Ns, first, count, (hipStream_t)stream);
 }
 
 int mirt_scene_update_triangle_materials(MirtScene* sc, const void* d_mats, int first, int count, void* stream)
 {
-  if (!sc) { set_error("mirt_scene_update_triangle_materials: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_scene_update_triangle_materials"));
   return update_materials(sc, "mirt_scene_update_triangle_materials", d_mats, sc->Ns, sc->Nt, first, count, (hipStream_t)stream);
 }
 
 int mirt_scene_get_sphere_materials(MirtScene* sc, int first, int count, void* d_mats_out, void* stream)
 {
-  if (!sc) { set_error("mirt_scene_get_sphere_materials: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_scene_get_sphere_materials"));
   return get_materials(sc, "mirt_scene_get_sphere_materials", 0, sc->Ns, first, count, d_mats_out, (hipStream_t)stream);
 }
 
 int mirt_scene_get_triangle_materials(MirtScene* sc, int first, int count, void* d_mats_out, void* stream)
 {
-  if (!sc) { set_error("mirt_scene_get_triangle_materials: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_scene_get_triangle_materials"));
   return get_materials(sc, "mirt_scene_get_triangle_materials", sc->Ns, sc->Nt, first, count, d_mats_out, (hipStream_t)stream);
 }
 
 int mirt_prev_features(MirtScene* sc, const void* d_rays, const void* d_hits, int64_t n, const void* d_prev_xyzr, const void* d_prev_verts,
                        void* d_features, void* stream)
 {
-  if (!sc) { set_error("mirt_prev_features: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_prev_features"));
   return prev_features(sc, d_rays, d_hits, n, d_prev_xyzr, d_prev_verts, d_features, (hipStream_t)stream);
 }
 
@@ -574,8 +563,7 @@ int mirt_get_stats(MirtScene* sc, MirtStats* out)
 
 int mirt_get_tree(MirtScene* sc, MirtTreeNode* nodes, uint32_t* codes, MirtPrimRef* refs, float* bounds)
 {
-  if (!sc) { set_error("mirt_get_tree: null scene"); return MIRT_ERR_ARG; }
-  MIRT_HIP(hipSetDevice(sc->device));
+  MIRT_TRY(enter_scene(sc, "mirt_get_tree"));
   return get_tree(sc, nodes, codes, refs, bounds);
 }
 

@@ -15,6 +15,7 @@
 #include "scene_dev.h"
 #include "host_scene.h"
 #include "shade_common.h"
+#include "query_walk.h"
 #include "../../include/mirt_closest.h"
 
 #include <cmath>
@@ -87,9 +88,7 @@ __global__ void __launch_bounds__(QUERY_BLOCK, CWAVES_PER_SIMD) closest_points_k
   const int tid = threadIdx.x;
   const long long stride = (long long)gridDim.x * QUERY_BLOCK;
   const unsigned char* const heap = reinterpret_cast<const unsigned char*>(a.nodes);
-  // (the planes are the same for every lane and never written by a kernel: scalar loads through the constant address space)
-  typedef const PlaneDev __attribute__((address_space(4))) * ConstPlanes;
-  const ConstPlanes planes = (ConstPlanes)(unsigned long long)a.planes;
+  const ConstPlanes planes = const_planes(a.planes);
   for (long long i = (long long)blockIdx.x * QUERY_BLOCK + tid; i < a.n; i += stride) {
     const float4 row = a.points[i];
     const f3 q = mk3(row.x, row.y, row.z);
@@ -149,7 +148,7 @@ __global__ void __launch_bounds__(QUERY_BLOCK, CWAVES_PER_SIMD) closest_points_k
           const bool hl = !(l2 > bound2), hr = !(r2 > bound2);
           const bool right_first = r2 < l2;      // the nearer child first
           if (hl && hr) {
-            // (the tree is at most 58 levels deep, DESIGN.md section 1: sp stays below STACK_TOTAL; the mask only bounds the index)
+            // (stack_push and stack_pop of query_walk.h, written out: as calls they move this loop's blocks)
             const uint32_t later = right_first ? ch.x : ch.y;
             if (sp < a.lds_depth) lds_stack[sp * QUERY_BLOCK + tid] = later;
             else spill[(sp - a.lds_depth) & (STACK_TOTAL - 1)] = later;
@@ -195,6 +194,7 @@ __global__ void __launch_bounds__(QUERY_BLOCK, CWAVES_PER_SIMD) closest_points_k
       }
     }
     if (hit) t = best;
+    // (store_hit of query_walk.h, written out like the stack above: section 6q)
     uint32_t* const h = a.hits + 6 * i;
     h[0] = __float_as_uint(t);
     h[1] = kind;
@@ -239,8 +239,7 @@ int closest_points(MirtScene* sc, const void* d_points, int64_t n, void* d_hits,
   q.root_ref = sc->root_ref; q.prim_base16 = sc->prim_base / 16u;
   q.coord_max = sc->coord_max;
   q.lds_depth = query_lds_depth(sc);
-  const long long want = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;
-  const int blocks = (int)(want < grid ? want : grid);
+  const int blocks = row_launch(n, grid);
   hipLaunchKernelGGL(closest_points_kernel, dim3(blocks), dim3(QUERY_BLOCK), 0, stream, q);
   MIRT_HIP(hipGetLastError());
   return MIRT_OK;

@@ -86,16 +86,14 @@ __global__ void __launch_bounds__(QUERY_BLOCK, multihit_waves(CAP)) multihit_ker
   const int tid = threadIdx.x;
   const long long stride = (long long)gridDim.x * QUERY_BLOCK;
   const unsigned char* const heap = reinterpret_cast<const unsigned char*>(q.nodes);
-  typedef const PlaneDev __attribute__((address_space(4))) * ConstPlanes;
-  const ConstPlanes planes = (ConstPlanes)(unsigned long long)q.planes;
+  const ConstPlanes planes = const_planes(q.planes);
   const float tmin = 0.0001f;
   for (long long i = (long long)blockIdx.x * QUERY_BLOCK + tid; i < q.num_rays; i += stride) {
     const float4 r0 = q.rays[2 * i], r1 = q.rays[2 * i + 1];
     const f3 o = mk3(r0.x, r0.y, r0.z);
     const float tmax = r0.w;
     const f3 d = normalize(mk3(r1.x, r1.y, r1.z));      // Ray(eye, dir, bounce), object.cuh:69
-    // mirt_trace_rays' rule: nothing to look for (tmax <= 0 or NaN) or no direction (shorter than normalize's 1e-6, or NaN)
-    const bool live = tmax > 0.0f && (fabsf(d.x) + fabsf(d.y) + fabsf(d.z)) > 0.0f;
+    const bool live = ray_is_live(tmax, d);
     KeyList<CAP> best;
     best.clear();
     uint32_t count = 0u;
@@ -139,19 +137,13 @@ __global__ void __launch_bounds__(QUERY_BLOCK, multihit_waves(CAP)) multihit_ker
           bool hl, hr;
           float tel, ter;
           box_pair(b0, b1, b2, o.x, o.y, o.z, inv.x, inv.y, inv.z, tmax, tmin, hl, hr, tel, ter);
-          if (hl && hr) {
-            // (the tree is at most 58 levels deep, DESIGN.md section 1: sp stays below STACK_TOTAL; the mask only bounds the index)
-            if (sp < q.lds_depth) lds_stack[sp * QUERY_BLOCK + tid] = ch.y;
-            else spill[(sp - q.lds_depth) & (STACK_TOTAL - 1)] = ch.y;
-            ++sp;
-          }
+          if (hl && hr) stack_push(lds_stack, spill, q.lds_depth, tid, sp, ch.y);
           cur = hl ? ch.x : ch.y;
           pop = !(hl || hr);
         }
         if (pop) {
           if (sp == 0) break;
-          --sp;
-          cur = sp < q.lds_depth ? lds_stack[sp * QUERY_BLOCK + tid] : spill[(sp - q.lds_depth) & (STACK_TOTAL - 1)];
+          cur = stack_pop(lds_stack, spill, q.lds_depth, tid, sp);
         }
       }
     }
@@ -178,7 +170,7 @@ __global__ void __launch_bounds__(QUERY_BLOCK, multihit_waves(CAP)) multihit_ker
             kind = MIRT_HIT_PLANE;
           }
         }
-        // (word by word: three 8-byte stores for an 8-byte aligned buffer were measured and took 20 to 58 % longer)
+        // (store_hit of query_walk.h, written out: as a call it renames this loop's registers)
         h[0] = __float_as_uint(t);
         h[1] = kind;
         h[2] = id;
@@ -194,8 +186,7 @@ template <int CAP>
 int launch(MirtScene* sc, const MultiArgs& q, int* cache, hipStream_t stream)
 {
   const int grid = query_grid_blocks(sc, multihit_kernel<CAP>, multihit_waves(CAP), cache);
-  const long long want = (q.num_rays + QUERY_BLOCK - 1) / QUERY_BLOCK;
-  const int blocks = (int)(want < grid ? want : grid);
+  const int blocks = row_launch(q.num_rays, grid);
   hipLaunchKernelGGL(multihit_kernel<CAP>, dim3(blocks), dim3(QUERY_BLOCK), 0, stream, q);
   MIRT_HIP(hipGetLastError());
   return MIRT_OK;

@@ -52,8 +52,7 @@ __global__ void __launch_bounds__(QUERY_BLOCK, QWAVES_PER_SIMD) trace_rays_kerne
     const f3 o = mk3(r0.x, r0.y, r0.z);
     const float tmax = r0.w;
     const f3 d = normalize(mk3(r1.x, r1.y, r1.z));      // Ray(eye, dir, bounce), object.cuh:69
-    // a ray with nothing to look for (tmax <= 0 or NaN) or no direction (shorter than normalize's 1e-6, or NaN) is a miss
-    const bool live = tmax > 0.0f && (fabsf(d.x) + fabsf(d.y) + fabsf(d.z)) > 0.0f;
+    const bool live = ray_is_live(tmax, d);
     float tplane = INFINITY, tbest = INFINITY;
     int plane_id = -1;
     uint32_t refbest = REF_NONE;
@@ -88,19 +87,13 @@ __global__ void __launch_bounds__(QUERY_BLOCK, QWAVES_PER_SIMD) trace_rays_kerne
           bool hl, hr;
           float tel, ter;
           box_pair(b0, b1, b2, o.x, o.y, o.z, inv.x, inv.y, inv.z, tbest, tmin, hl, hr, tel, ter);
-          if (hl && hr) {
-            // (the tree is at most 58 levels deep, DESIGN.md section 1: sp stays below STACK_TOTAL; the mask only bounds the index)
-            if (sp < q.lds_depth) lds_stack[sp * QUERY_BLOCK + tid] = ch.y;
-            else spill[(sp - q.lds_depth) & (STACK_TOTAL - 1)] = ch.y;
-            ++sp;
-          }
+          if (hl && hr) stack_push(lds_stack, spill, q.lds_depth, tid, sp, ch.y);
           cur = hl ? ch.x : ch.y;
           pop = !(hl || hr);
         }
         if (pop) {
           if (sp == 0) break;
-          --sp;
-          cur = sp < q.lds_depth ? lds_stack[sp * QUERY_BLOCK + tid] : spill[(sp - q.lds_depth) & (STACK_TOTAL - 1)];
+          cur = stack_pop(lds_stack, spill, q.lds_depth, tid, sp);
         }
       }
     }
@@ -121,13 +114,7 @@ __global__ void __launch_bounds__(QUERY_BLOCK, QWAVES_PER_SIMD) trace_rays_kerne
         kind = MIRT_HIT_PLANE;
       }
     }
-    uint32_t* const h = q.hits + 6 * i;
-    h[0] = __float_as_uint(report ? t : -1.0f);
-    h[1] = kind;
-    h[2] = id;
-    h[3] = __float_as_uint(n.x);
-    h[4] = __float_as_uint(n.y);
-    h[5] = __float_as_uint(n.z);
+    store_hit(q.hits + 6 * i, report ? t : -1.0f, kind, id, n);
   }
 }
 
@@ -184,8 +171,7 @@ int trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits
   q.planes = sc->planes; q.num_planes = sc->d.num_planes;
   q.root_ref = sc->root_ref; q.prim_base16 = sc->prim_base / 16u;
   q.lds_depth = query_lds_depth(sc);
-  const long long want = (num_rays + QUERY_BLOCK - 1) / QUERY_BLOCK;
-  const int blocks = (int)(want < grid ? want : grid);
+  const int blocks = row_launch(num_rays, grid);
   if (flags & MIRT_QUERY_ANY_HIT) hipLaunchKernelGGL(trace_rays_kernel<true>, dim3(blocks), dim3(QUERY_BLOCK), 0, stream, q);
   else hipLaunchKernelGGL(trace_rays_kernel<false>, dim3(blocks), dim3(QUERY_BLOCK), 0, stream, q);
   MIRT_HIP(hipGetLastError());

@@ -1,9 +1,11 @@
-// Device code that query kernels share: the walk over the exact 64-byte records (light.hip, indirect.hip),
-// hitNearest's choice between the tree's hit and the planes' and the winner's normal (query.hip, indirect.hip), a light's shadow
-// ray and a row's field of the wave's ballot (light.hip).  Which file uses which piece was decided by measurement, kernel by
-// kernel: section 6n.  Everything here is inlined into its caller, and every helper keeps the operation order the headers under
-// include/ fix, so the results' bits do not depend on who calls it.  The render's walks (render.hip, wavefront.hip) are
-// quantised, batched and another loop: they do not use this file.
+// Device code that query kernels share (DESIGN.md sections 6n, 6q): the walk over the exact 64-byte records (light.hip,
+// indirect.hip), the pieces every walk is made of -- the lane's stack, the live-ray rule, the planes' scalar loads, a MirtHit's
+// stores (also query.hip, multihit.hip, closest.hip, which write their own loops) --, hitNearest's choice between the tree's hit
+// and the planes' and the winner's normal (query.hip, indirect.hip), a light's shadow ray and a row's field of the wave's ballot
+// (light.hip).  Which file uses which piece was decided by measurement, kernel by kernel: sections 6n, 6q.  Everything here is
+// inlined into its caller, and every helper keeps the operation order the headers under include/ fix, so the results' bits do
+// not depend on who calls it.  The render's walks (render.hip, wavefront.hip) are quantised, batched and another loop: they do
+// not use this file.
 #ifndef MIRT_QUERY_WALK_H
 #define MIRT_QUERY_WALK_H
 
@@ -15,21 +17,60 @@
 
 namespace mirt {
 
+// A lane's stack of node references: entry sp lives in the block's LDS (lds_stack[QUERY_STACK_LDS * QUERY_BLOCK], [entry][lane],
+// tid the lane's index in the block) while sp < lds_depth, deeper entries in the lane's private array spill[STACK_TOTAL]
+// (scratch: the rarely taken path).  The tree is at most 58 levels deep, so sp stays below STACK_TOTAL;
+// the mask only bounds the index.
+__device__ __forceinline__ void stack_push(uint32_t* lds_stack, uint32_t* spill, int lds_depth, int tid, int& sp, uint32_t ref)
+{
+  if (sp < lds_depth) lds_stack[sp * QUERY_BLOCK + tid] = ref;
+  else spill[(sp - lds_depth) & (STACK_TOTAL - 1)] = ref;
+  ++sp;
+}
+__device__ __forceinline__ uint32_t stack_pop(const uint32_t* lds_stack, const uint32_t* spill, int lds_depth, int tid, int& sp)
+{
+  --sp;
+  return sp < lds_depth ? lds_stack[sp * QUERY_BLOCK + tid] : spill[(sp - lds_depth) & (STACK_TOTAL - 1)];
+}
+
+// mirt_trace_rays' rule, d normalised: a ray with nothing to look for (tmax <= 0 or NaN) or no direction (shorter than
+// normalize's 1e-6, or NaN) is a miss.
+__device__ __forceinline__ bool ray_is_live(float tmax, const f3& d)
+{
+  return tmax > 0.0f && (fabsf(d.x) + fabsf(d.y) + fabsf(d.z)) > 0.0f;
+}
+
+// The planes are the same for every lane and never written by a kernel: scalar loads through the constant address space.
+typedef const PlaneDev __attribute__((address_space(4))) * ConstPlanes;
+__device__ __forceinline__ ConstPlanes const_planes(const PlaneDev* planes)
+{
+  return (ConstPlanes)(unsigned long long)planes;
+}
+
+// One MirtHit record (6 words at h).  Word by word: three 8-byte stores for an 8-byte aligned buffer were measured and took 20
+// to 58 % longer.
+__device__ __forceinline__ void store_hit(uint32_t* h, float t, uint32_t kind, uint32_t id, const f3& n)
+{
+  h[0] = __float_as_uint(t);
+  h[1] = kind;
+  h[2] = id;
+  h[3] = __float_as_uint(n.x);
+  h[4] = __float_as_uint(n.y);
+  h[5] = __float_as_uint(n.z);
+}
+
 // The reference's hitNearest without the final choice, for the ray (o, tmax, d), d normalised: the planes (checkPlane,
 // draw.cu:581-615), then the walk of traverse_lbvh (bvh_traversal.cu:92-183) over the exact 64-byte node records, left child
 // first -- the reference's own walk, so no vetting and no second walk is ever needed.  ANY: an occlusion query, which ends at the
 // first occluder nearer than tmax.  Leaves tbest / refbest (the tree's answer) and tplane / plane_id (the planes').
-// A lane carries the ray, 1/d, the best distance and record and a stack pointer; the stack lives in the block's LDS
-// (lds_stack[QUERY_STACK_LDS * QUERY_BLOCK], [entry][lane], of which lds_depth entries are used), deeper entries in the lane's
-// private array spill[STACK_TOTAL] (scratch), which the bundled scenes rarely reach.  tid: the lane's index in the block.
+// A lane carries the ray, 1/d, the best distance and record and a stack pointer; the stack is stack_push's.
 template <bool ANY>
 __device__ __forceinline__ void walk(const unsigned char* heap, uint32_t root_ref, const PlaneDev* planes, int num_planes, const f3& o, const f3& d, float tmax,
                                      uint32_t* lds_stack, uint32_t* spill, int lds_depth, int tid, float& tbest, uint32_t& refbest, float& tplane,
                                      int& plane_id)
 {
   const float tmin = 0.0001f;
-  // a ray with nothing to look for (tmax <= 0 or NaN) or no direction (shorter than normalize's 1e-6, or NaN) is a miss
-  const bool live = tmax > 0.0f && (fabsf(d.x) + fabsf(d.y) + fabsf(d.z)) > 0.0f;
+  const bool live = ray_is_live(tmax, d);
   tplane = INFINITY; tbest = INFINITY;
   plane_id = -1;
   refbest = REF_NONE;
@@ -64,19 +105,13 @@ __device__ __forceinline__ void walk(const unsigned char* heap, uint32_t root_re
         bool hl, hr;
         float tel, ter;
         box_pair(b0, b1, b2, o.x, o.y, o.z, inv.x, inv.y, inv.z, tbest, tmin, hl, hr, tel, ter);
-        if (hl && hr) {
-          // (the tree is at most 58 levels deep, DESIGN.md section 1: sp stays below STACK_TOTAL; the mask only bounds the index)
-          if (sp < lds_depth) lds_stack[sp * QUERY_BLOCK + tid] = ch.y;
-          else spill[(sp - lds_depth) & (STACK_TOTAL - 1)] = ch.y;
-          ++sp;
-        }
+        if (hl && hr) stack_push(lds_stack, spill, lds_depth, tid, sp, ch.y);
         cur = hl ? ch.x : ch.y;
         pop = !(hl || hr);
       }
       if (pop) {
         if (sp == 0) break;
-        --sp;
-        cur = sp < lds_depth ? lds_stack[sp * QUERY_BLOCK + tid] : spill[(sp - lds_depth) & (STACK_TOTAL - 1)];
+        cur = stack_pop(lds_stack, spill, lds_depth, tid, sp);
       }
     }
   }
@@ -115,8 +150,7 @@ __device__ __forceinline__ f3 prim_normal(const float4* nodes, uint32_t refbest,
 }
 __device__ __forceinline__ f3 plane_normal(const PlaneDev* planes_generic, int plane_id, const f3& d)
 {
-  typedef const PlaneDev __attribute__((address_space(4))) * ConstPlanes;
-  const ConstPlanes planes = (ConstPlanes)(unsigned long long)planes_generic;
+  const ConstPlanes planes = const_planes(planes_generic);
   const f3 pnor = mk3(planes[plane_id].nx, planes[plane_id].ny, planes[plane_id].nz);
   return (dot(pnor, d) < 0.0f) ? pnor : -pnor;
 }

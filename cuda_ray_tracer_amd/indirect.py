@@ -2,7 +2,7 @@
 
 mirt_indirect.h is an extension header like mirt_light.h and mirt_visibility.h: binding.SIGNATURES stays the table of
 include/mirt.h, lighting.LIGHT_SIGNATURES and visibility.VISIBILITY_SIGNATURES the tables of the other two, and the one entry point
-more lives here.  tests/test_indirect_abi.py holds the table to the header the way tests/test_binding_header.py holds binding.py to
+more lives here.  tests/test_extension_abi.py holds the table to the header the way tests/test_binding_header.py holds binding.py to
 mirt.h.
 
 Needs ctypes only: torch and numpy are imported when a call needs them.
@@ -19,22 +19,10 @@ INDIRECT_SIGNATURES = {
     "mirt_indirect_light": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _float, _vp, _vp, _u32, _vp]),
 }
 
-_applied = None
-
 
 def lib():
-    """binding.lib() with the signatures of mirt_indirect.h applied.  A library without the symbol is an error here: there is no
-    other implementation."""
-    global _applied
-    L = binding.lib()
-    if _applied is not L:
-        for name, (restype, argtypes) in INDIRECT_SIGNATURES.items():
-            f = getattr(L, name, None)
-            if f is None:
-                raise binding.MirtError(-1, f"{binding.LIB_PATH} does not export {name}: rebuild it with `python -m cuda_ray_tracer_amd.build`")
-            f.restype, f.argtypes = restype, argtypes
-        _applied = L
-    return L
+    """binding.lib() with the signatures of mirt_indirect.h applied."""
+    return binding.extension_lib(INDIRECT_SIGNATURES)
 
 
 def indirect_light(raw, d_features, d_dirs, d_out, d_hit_mask=None, d_rot=None, radius=float("inf"), stream=None):
@@ -71,15 +59,11 @@ def indirect_light_frame(raw, width, height, spp=0, directions=16, radius=float(
     the cosine table out[:, :3] estimates the bounced irradiance over pi."""
     import torch
     from . import api
-    from .visibility import cosine_directions, rotations
+    from .visibility import _frame_directions
     p = api._frame(params, width, height, spp)
     n = api.num_pixels(p)
     with api._device_and_stream(raw.device, stream) as (dev, s):
-        if isinstance(directions, int):
-            dirs = cosine_directions(directions, dev)
-        else:
-            dirs = torch.as_tensor(directions, dtype=torch.float32).to(dev).contiguous()
-        rot = rotations(n, rotate_seed, dev) if rotate_seed is not None else None
+        dirs, rot = _frame_directions(directions, n, rotate_seed, dev)
         rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
         hits = torch.empty((n, 6), dtype=torch.int32, device=dev)
         features = torch.empty((n, 8), dtype=torch.float32, device=dev)

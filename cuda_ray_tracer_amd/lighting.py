@@ -1,7 +1,7 @@
 """Direct light at surface points: include/mirt_light.h restated for ctypes, and the calls over it.
 
 mirt_light.h is an extension header: binding.SIGNATURES stays the table of include/mirt.h, and the one entry point more lives
-here with its constant.  tests/test_light_abi.py holds both to the header the way tests/test_binding_header.py holds binding.py
+here with its constant.  tests/test_extension_abi.py holds both to the header the way tests/test_binding_header.py holds binding.py
 to mirt.h.
 
 Needs ctypes only: torch is imported when a call needs it, numpy not at all.
@@ -20,22 +20,10 @@ LIGHT_SIGNATURES = {
     "mirt_direct_light": (_int, [_vp, _vp, _i64, _vp, _vp, _u32, _vp]),
 }
 
-_applied = None
-
 
 def lib():
-    """binding.lib() with the signatures of mirt_light.h applied.  A library without the symbol is an error here: there is no
-    other implementation."""
-    global _applied
-    L = binding.lib()
-    if _applied is not L:
-        for name, (restype, argtypes) in LIGHT_SIGNATURES.items():
-            f = getattr(L, name, None)
-            if f is None:
-                raise binding.MirtError(-1, f"{binding.LIB_PATH} does not export {name}: rebuild it with `python -m cuda_ray_tracer_amd.build`")
-            f.restype, f.argtypes = restype, argtypes
-        _applied = L
-    return L
+    """binding.lib() with the signatures of mirt_light.h applied."""
+    return binding.extension_lib(LIGHT_SIGNATURES)
 
 
 def direct_light(raw, d_features, d_out, d_lit_mask=None, raw_units=False, stream=None):

@@ -1,7 +1,7 @@
 """Hemisphere visibility at surface points: include/mirt_visibility.h restated for ctypes, and the calls over it.
 
 mirt_visibility.h is an extension header like mirt_light.h: binding.SIGNATURES stays the table of include/mirt.h,
-lighting.LIGHT_SIGNATURES the table of mirt_light.h, and the one entry point more lives here.  tests/test_visibility_abi.py holds
+lighting.LIGHT_SIGNATURES the table of mirt_light.h, and the one entry point more lives here.  tests/test_extension_abi.py holds
 the table to the header the way tests/test_binding_header.py holds binding.py to mirt.h.
 
 Needs ctypes only: torch and numpy are imported when a call needs them.
@@ -20,22 +20,10 @@ VISIBILITY_SIGNATURES = {
 
 GOLDEN_ANGLE = 2.399963229728653
 
-_applied = None
-
 
 def lib():
-    """binding.lib() with the signatures of mirt_visibility.h applied.  A library without the symbol is an error here: there is
-    no other implementation."""
-    global _applied
-    L = binding.lib()
-    if _applied is not L:
-        for name, (restype, argtypes) in VISIBILITY_SIGNATURES.items():
-            f = getattr(L, name, None)
-            if f is None:
-                raise binding.MirtError(-1, f"{binding.LIB_PATH} does not export {name}: rebuild it with `python -m cuda_ray_tracer_amd.build`")
-            f.restype, f.argtypes = restype, argtypes
-        _applied = L
-    return L
+    """binding.lib() with the signatures of mirt_visibility.h applied."""
+    return binding.extension_lib(VISIBILITY_SIGNATURES)
 
 
 def hemisphere_visibility(raw, d_features, d_dirs, d_out, d_vis_mask=None, d_rot=None, radius=float("inf"), stream=None):
@@ -93,6 +81,17 @@ def rotations(n, seed, device=None):
     return _placed(np.ascontiguousarray(np.stack([np.cos(angle), np.sin(angle)], axis=1), dtype=np.float32), device)
 
 
+def _frame_directions(directions, n, rotate_seed, device):
+    """The direction table and the rotations of a frame call, on `device`: cosine_directions(directions) for an int, else the
+    caller's float32 [K, 4] table; rotations(n, rotate_seed), or None without a seed."""
+    import torch
+    if isinstance(directions, int):
+        dirs = cosine_directions(directions, device)
+    else:
+        dirs = torch.as_tensor(directions, dtype=torch.float32).to(device).contiguous()
+    return dirs, (rotations(n, rotate_seed, device) if rotate_seed is not None else None)
+
+
 def ambient_occlusion_frame(raw, width, height, spp=0, directions=16, radius=float("inf"), rotate_seed=None, want_mask=False, params=None,
                             stream=None):
     """The hemisphere visibility at the first hit of every pixel's camera ray: camera_rays (sample 0 of every pixel of a
@@ -105,11 +104,7 @@ def ambient_occlusion_frame(raw, width, height, spp=0, directions=16, radius=flo
     p = api._frame(params, width, height, spp)
     n = api.num_pixels(p)
     with api._device_and_stream(raw.device, stream) as (dev, s):
-        if isinstance(directions, int):
-            dirs = cosine_directions(directions, dev)
-        else:
-            dirs = torch.as_tensor(directions, dtype=torch.float32).to(dev).contiguous()
-        rot = rotations(n, rotate_seed, dev) if rotate_seed is not None else None
+        dirs, rot = _frame_directions(directions, n, rotate_seed, dev)
         rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
         hits = torch.empty((n, 6), dtype=torch.int32, device=dev)
         features = torch.empty((n, 8), dtype=torch.float32, device=dev)

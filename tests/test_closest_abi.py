@@ -1,91 +1,32 @@
-"""Closest-point queries (include/mirt_closest.h: mirt_closest_points): the extension header against closest.py's signature table and
-the built library, the wrappers' checks, the kernel's code generation, the numpy restatement of the header (tests/closest_ref.py)
-against a float64 brute force that shares no code with it, and the header's pruning rule -- the slack -- checked on the CPU over
-the oracle's tree: with it the pruned walk gives the brute force's bits, without it it loses answers.  No GPU needed."""
-import ctypes as C
+"""Closest-point queries (include/mirt_closest.h: mirt_closest_points): what only this header says, the wrappers' checks, the
+kernel's code generation, the numpy restatement of the header (tests/closest_ref.py) against a float64 brute force that shares no
+code with it, and the header's pruning rule -- the slack -- checked on the CPU over the oracle's tree: with it the pruned walk
+gives the brute force's bits, without it it loses answers.  The header against closest.py's signature table and the built
+library: tests/test_extension_abi.py.  No GPU needed."""
 import functools
 import os
-import re
-import subprocess
-import sys
 import types
 
 import numpy as np
 import pytest
 
 import cuda_ray_tracer_amd as m
-from cuda_ray_tracer_amd import api, binding, closest, indirect, lighting, visibility
-from cuda_ray_tracer_amd import build as B
 import closest_ref as cr
 import edge_scenes
 import light_scenes
 import oracle_lib as ol
 import pyscene
-from test_binding_header import compare_prototypes, constants, prototypes
-from test_query_abi import _kernel_body, _resource_usage
+from codegen_lib import _kernel_body, _resource_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
-NAME = "mirt_closest_points"
 U = 2.0 ** -24      # float32's unit roundoff
 
 
-def _strip(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-
-
-HEADER = _strip(os.path.join(ROOT, "include", "mirt_closest.h"))
-
-
-# ---- header, signature table, library ---------------------------------------------------------------------------------------------
-def test_the_extension_header_agrees_with_the_signature_table():
-    assert [name for name, _, _ in prototypes(HEADER)] == list(closest.CLOSEST_SIGNATURES) == [NAME]
-    assert sorted(set(re.findall(r"\b(mirt_[a-z0-9_]+)\s*\(", HEADER))) == [NAME]
-    assert compare_prototypes(HEADER, closest.CLOSEST_SIGNATURES) == []
-    pointer, i32, i64, u32 = "pointer", (4, True, False), (8, True, False), (4, False, False)
-    assert prototypes(HEADER)[0] == (NAME, i32, [pointer, pointer, i64, pointer, pointer, u32, pointer])
-    assert constants(HEADER) == {}
-    assert re.search(r'^#include "mirt.h"$', HEADER, flags=re.M)
-    restype, argtypes = closest.CLOSEST_SIGNATURES[NAME]
-    assert compare_prototypes(HEADER, {NAME: (restype, argtypes[:-1])}) == [f"{NAME}: 7 parameters, the table has 6"]
-    # the header says that the answer does not depend on the tree, and states the slack
+# ---- header, wrappers ----------------------------------------------------------------------------------------------------------------
+def test_the_header_says_that_the_arrays_define_the_answer_and_states_the_slack():
     text = open(os.path.join(ROOT, "include", "mirt_closest.h")).read()
     assert "not by the tree" in text and "sigma = 2^-18" in text and "(dist, kind, id)" in text
-
-
-def test_the_other_headers_and_tables_do_not_know_the_extension():
-    for header in ("mirt.h", "mirt_light.h", "mirt_visibility.h", "mirt_indirect.h"):
-        assert NAME not in open(os.path.join(ROOT, "include", header)).read()
-    for table in (binding.SIGNATURES, lighting.LIGHT_SIGNATURES, visibility.VISIBILITY_SIGNATURES, indirect.INDIRECT_SIGNATURES):
-        assert NAME not in table
-
-
-def test_library_exports_the_symbol_and_the_signature_is_applied():
-    out = subprocess.run(["nm", "-D", "--defined-only", B.LIB], capture_output=True, text=True, check=True).stdout
-    assert re.search(r"\bT mirt_closest_points$", out, flags=re.M)
-    f = closest.lib().mirt_closest_points
-    assert f.restype is C.c_int and list(f.argtypes) == closest.CLOSEST_SIGNATURES[NAME][1]
-    for name in ("closest_points", "pack_points"):
-        assert getattr(m, name) is getattr(closest, name) is getattr(api, name) and name in m.__all__, name
-
-
-def test_the_closest_module_needs_neither_torch_nor_numpy():
-    code = "import sys; import cuda_ray_tracer_amd.closest; assert 'torch' not in sys.modules and 'numpy' not in sys.modules, sorted(sys.modules)"
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-
-
-def test_the_build_depends_on_the_extension_header_and_the_kernel():
-    deps = [os.path.normpath(d) for d in B._all_deps()]
-    assert os.path.join(ROOT, "include", "mirt_closest.h") in deps and os.path.join(B.CSRC, "closest.hip") in deps
-    assert "closest.hip" in B.LIB_SOURCES
-
-
-def test_null_scene_is_an_argument_error():
-    L = closest.lib()
-    assert L.mirt_closest_points(None, None, 0, None, None, 0, None) == 3
-    assert L.mirt_closest_points(None, None, 5, None, None, 0, None) == 3
-    assert b"mirt_closest_points" in m.lib().mirt_last_error()
 
 
 def test_wrappers_check_their_tensors_before_calling_the_library():

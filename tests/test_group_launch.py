@@ -1,7 +1,7 @@
-"""The launch arithmetic the grouped query kernels share (csrc/query_launch.h: group_launch, used by light.hip, visibility.hip and
-indirect.hip) needs no GPU: a stand-alone probe, tests/group_launch_probe.cpp, is compiled with the host compiler (address +
-undefined sanitizers where they link) and prints gshift and the block count of every case it reads.  Checked here against the
-expressions each of the three files had of its own before they were shared, restated below."""
+"""The launch arithmetic the query kernels share (csrc/query_launch.h: group_launch, used by light.hip, visibility.hip and
+indirect.hip; row_launch, used by query.hip, closest.hip and multihit.hip) needs no GPU: a stand-alone probe, tests/group_launch_probe.cpp, is compiled with the host compiler (address +
+undefined sanitizers where they link) and prints gshift and the block counts of every case it reads.  Checked here against the
+expressions each of the files had of its own before they were shared, restated below."""
 import os
 import shutil
 import subprocess
@@ -28,6 +28,14 @@ def former(n, lanes_per_row, cached_blocks):
     rows_per_block = (BLOCK // 64) * (64 >> gshift)
     want = (n + rows_per_block - 1) // rows_per_block
     return gshift, min(want, cached_blocks)
+
+
+def former_rows(n, cached_blocks):
+    """query.hip, closest.hip and multihit.hip as they were, with the cached grid = cached_blocks:
+        const long long want = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;
+        const int blocks = (int)(want < grid ? want : grid);"""
+    want = (n + BLOCK - 1) // BLOCK
+    return min(want, cached_blocks)
 
 
 @pytest.fixture(scope="module")
@@ -98,3 +106,24 @@ def test_block_count_covers_the_rows_and_stops_at_the_cached_grid(probe):
     assert [p["blocks"] for p in probe([(3, 64, CACHED), (4, 64, CACHED), (5, 64, CACHED)])] == [1, 1, 2]
     # just under 2^56 rows: the count is the cached grid's, whatever it is
     assert [p["blocks"] for p in probe([((1 << 56) - 1, 64, 1), ((1 << 56) - 1, 1, CACHED), ((1 << 56) - 1, 0, (1 << 31) - 1)])] == [1, CACHED, (1 << 31) - 1]
+
+
+def test_row_launch_gives_one_lane_per_row_and_stops_at_the_cached_grid(probe):
+    """Around one block's rows, a count above what the cached grid serves at a time, the largest n the entry points admit, and a
+    cached grid of one block."""
+    ns = (1, 255, 256, 257, 5 * 256 + 1, CACHED * 256, CACHED * 256 + 1, 3 * CACHED * 256 + 7, (1 << 56) - 1)
+    cases = [(n, 1, cached) for n in ns for cached in (1, 3, CACHED, (1 << 31) - 1)]
+    got = probe(cases)
+    for (n, _, cached), p in zip(cases, got):
+        want = -(-n // BLOCK)
+        assert p["row_blocks"] == former_rows(n, cached) == min(want, cached), (n, cached, p)
+        assert 1 <= p["row_blocks"] <= cached
+        assert p["row_blocks"] == p["blocks"]                                    # a grouped launch with G = 1 is the same grid
+        if want <= cached:
+            assert (p["row_blocks"] - 1) * BLOCK < n <= p["row_blocks"] * BLOCK      # the last block has a row, and no row is left over
+    by = {(n, cached): p["row_blocks"] for (n, _, cached), p in zip(cases, got)}
+    assert [by[(n, CACHED)] for n in (1, 255, 256, 257)] == [1, 1, 1, 2]
+    assert by[(CACHED * 256, CACHED)] == CACHED and by[(CACHED * 256 + 1, CACHED)] == CACHED and by[(3 * CACHED * 256 + 7, CACHED)] == CACHED
+    assert all(by[(n, 1)] == 1 for n in ns)
+    # the lanes of a row do not enter it
+    assert [p["row_blocks"] for p in probe([(1000, k, CACHED) for k in (0, 1, 16, 64)])] == [4, 4, 4, 4]

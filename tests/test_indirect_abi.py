@@ -1,21 +1,16 @@
-"""Indirect light at surface points (include/mirt_indirect.h: mirt_indirect_light): the extension header against indirect.py's
-signature table and the built library, the kernel's code generation, the properties of tests/indirect_ref.py -- the numpy
-restatement of the header's text -- and the restatement decided twice on the CPU: by f64_arbiter in float64 and by the float32
-brute force of tests/test_gpu_queries.py.  No GPU needed."""
-import ctypes as C
+"""Indirect light at surface points (include/mirt_indirect.h: mirt_indirect_light): the wrappers' checks, the kernel's code
+generation, the properties of tests/indirect_ref.py -- the numpy restatement of the header's text -- and the restatement decided
+twice on the CPU: by f64_arbiter in float64 and by the float32 brute force of tests/test_gpu_queries.py.  The header against
+indirect.py's signature table and the built library: tests/test_extension_abi.py.  No GPU needed."""
 import functools
 import os
-import re
-import subprocess
-import sys
 import types
 
 import numpy as np
 import pytest
 
 import cuda_ray_tracer_amd as m
-from cuda_ray_tracer_amd import api, binding, indirect, lighting, visibility
-from cuda_ray_tracer_amd import build as B
+from cuda_ray_tracer_amd import binding, indirect, visibility
 import denoise_ref as dr
 import f64_arbiter as arb
 import indirect_ref as ir
@@ -24,9 +19,8 @@ import light_scenes
 import oracle_lib as ol
 import pyscene
 import visibility_ref as vr
-from test_binding_header import compare_prototypes, constants, prototypes
 from test_denoise_abi import _pinhole_rays
-from test_query_abi import _resource_usage
+from codegen_lib import _resource_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
@@ -39,13 +33,6 @@ KERNEL_VGPRS, KERNEL_WAVES_PER_SIMD = 72, 7
 # bound asserted, 8 x that
 RGB_WORST_SEEN = 6.21e-8      # (mixed_planes, K 16, radius inf; rgb up to 0.66)
 RGB_TOLERANCE = 8 * RGB_WORST_SEEN
-
-
-def _strip(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-
-
-HEADER = _strip(os.path.join(ROOT, "include", "mirt_indirect.h"))
 
 # ---- scenes -------------------------------------------------------------------------------------------------------------------------
 # light_scenes' geometries with materials of their own: a coloured sphere, a glass sphere, a half-shiny sphere, a matte cream back
@@ -67,63 +54,15 @@ def material_scene(geometry, nlights, kind, w=light_scenes.W, h=light_scenes.H):
     return "".join([f"png {w} {h} indirect.png\n", light_scenes.lights(nlights, kind), _PLANES if geometry.endswith("_planes") else ""] + body)
 
 
-# ---- header, signature table, library ---------------------------------------------------------------------------------------------
-def test_the_extension_header_agrees_with_the_signature_table():
-    assert [name for name, _, _ in prototypes(HEADER)] == list(indirect.INDIRECT_SIGNATURES) == [NAME]
-    assert sorted(set(re.findall(r"\b(mirt_[a-z0-9_]+)\s*\(", HEADER))) == [NAME]
-    assert compare_prototypes(HEADER, indirect.INDIRECT_SIGNATURES) == []
-    pointer, i32, i64, u32, flt = "pointer", (4, True, False), (8, True, False), (4, False, False), (4, True, True)
-    assert prototypes(HEADER)[0] == (NAME, i32, [pointer, pointer, i64, pointer, i32, pointer, flt, pointer, pointer, u32, pointer])
-    assert constants(HEADER) == {}
-    assert re.search(r'^#include "mirt.h"$', HEADER, flags=re.M)
-    # a table that disagrees is a mismatch
-    restype, argtypes = indirect.INDIRECT_SIGNATURES[NAME]
-    wrong = compare_prototypes(HEADER, {NAME: (restype, [C.c_double if t is C.c_float else t for t in argtypes])})
-    assert wrong == [f"{NAME}: parameter 6 is (4, True, True), the table says (8, True, True)"]
-    assert compare_prototypes(HEADER, {NAME: (restype, argtypes[:-1])}) == [f"{NAME}: 11 parameters, the table has 10"]
-    # the same parameters as the hemisphere visibility, whose meaning the header takes over
+# ---- header, library, wrappers -------------------------------------------------------------------------------------------------------
+def test_the_header_takes_over_the_parameters_of_the_hemisphere_visibility():
     assert indirect.INDIRECT_SIGNATURES[NAME] == visibility.VISIBILITY_SIGNATURES["mirt_hemisphere_visibility"]
-    assert re.search(r"#define MIRT_VERSION 3\b", open(os.path.join(ROOT, "include", "mirt.h")).read())
-
-
-def test_the_other_headers_and_tables_do_not_know_the_extension():
-    for header in ("mirt.h", "mirt_light.h", "mirt_visibility.h"):
-        assert NAME not in open(os.path.join(ROOT, "include", header)).read()
-    assert NAME not in binding.SIGNATURES and NAME not in lighting.LIGHT_SIGNATURES and NAME not in visibility.VISIBILITY_SIGNATURES
-
-
-def test_library_exports_the_symbol_and_the_signature_is_applied():
-    out = subprocess.run(["nm", "-D", "--defined-only", B.LIB], capture_output=True, text=True, check=True).stdout
-    assert re.search(r"\bT mirt_indirect_light$", out, flags=re.M)
-    f = indirect.lib().mirt_indirect_light
-    assert f.restype is C.c_int and list(f.argtypes) == indirect.INDIRECT_SIGNATURES[NAME][1]
-    for name in ("indirect_light", "indirect_light_frame"):
-        assert getattr(m, name) is getattr(indirect, name) is getattr(api, name) and name in m.__all__, name
 
 
 def test_a_library_without_the_symbol_is_an_error(monkeypatch):
     monkeypatch.setattr(binding, "lib", lambda: types.SimpleNamespace())
-    monkeypatch.setattr(indirect, "_applied", None)
     with pytest.raises(binding.MirtError, match="does not export mirt_indirect_light"):
         indirect.lib()
-
-
-def test_the_indirect_module_needs_neither_torch_nor_numpy():
-    code = "import sys; import cuda_ray_tracer_amd.indirect; assert 'torch' not in sys.modules and 'numpy' not in sys.modules, sorted(sys.modules)"
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-
-
-def test_the_build_depends_on_the_extension_header_and_the_kernel():
-    deps = [os.path.normpath(d) for d in B._all_deps()]
-    assert os.path.join(ROOT, "include", "mirt_indirect.h") in deps and os.path.join(B.CSRC, "indirect.hip") in deps
-    assert "indirect.hip" in B.LIB_SOURCES
-
-
-def test_null_scene_is_an_argument_error():
-    L = indirect.lib()
-    assert L.mirt_indirect_light(None, None, 0, None, 1, None, 1.0, None, None, 0, None) == 3
-    assert L.mirt_indirect_light(None, None, 5, None, 16, None, float("inf"), None, None, 0, None) == 3
 
 
 def test_wrappers_check_their_tensors_before_calling_the_library():

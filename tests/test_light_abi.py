@@ -1,6 +1,7 @@
-"""Direct light at surface points (include/mirt_light.h: mirt_direct_light): the extension header against lighting.py's signature
-table and the built library, the kernel's code generation, and tests/light_ref.py -- the numpy restatement of the header's text --
-against the oracle's renders of matte-white scenes.  No GPU needed."""
+"""Direct light at surface points (include/mirt_light.h: mirt_direct_light): the wrappers' checks, the kernel's code generation,
+and tests/light_ref.py -- the numpy restatement of the header's text -- against the oracle's renders of matte-white scenes.  The
+header against lighting.py's signature table and the built library, as this file has held them since the first extension;
+tests/test_extension_abi.py holds every extension header, this one among them, by one table.  No GPU needed."""
 import ctypes as C
 import os
 import re
@@ -22,16 +23,10 @@ import oracle_lib as ol
 import pyscene
 from test_binding_header import compare_prototypes, constants, prototypes
 from test_denoise_abi import _pinhole_rays
-from test_query_abi import _resource_usage
+from codegen_lib import _resource_usage, _strip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
-
-
-def _strip(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-
-
 HEADER = _strip(os.path.join(ROOT, "include", "mirt_light.h"))
 
 

@@ -1,93 +1,33 @@
-"""Multi-hit ray queries (include/mirt_multihit.h: mirt_trace_rays_multi): the extension header against multihit.py's signature
-table and the built library, the wrappers' checks, the kernel's code generation, and the numpy restatement of the header
-(tests/multihit_ref.py) against itself over the oracle's tree: on the inputs the GPU tests use, the set the tree defines equals a
-brute force over the scene's arrays, and the records, counts and order have the properties the header states.  No GPU needed."""
-import ctypes as C
+"""Multi-hit ray queries (include/mirt_multihit.h: mirt_trace_rays_multi): what only this header says, the wrappers' checks,
+the kernel's code generation, and the numpy restatement of the header (tests/multihit_ref.py) against itself over the oracle's
+tree: on the inputs the GPU tests use, the set the tree defines equals a brute force over the scene's arrays, and the records,
+counts and order have the properties the header states.  The header against multihit.py's signature table and the built library:
+tests/test_extension_abi.py.  No GPU needed."""
 import functools
 import os
 import re
-import subprocess
-import sys
 import types
 
 import numpy as np
 import pytest
 
 import cuda_ray_tracer_amd as m
-from cuda_ray_tracer_amd import api, binding, closest, indirect, lighting, multihit, visibility
-from cuda_ray_tracer_amd import build as B
 import edge_scenes
 import multihit_ref as mr
 import oracle_lib as ol
 import pyscene
-from test_binding_header import compare_prototypes, constants, prototypes
-from test_query_abi import _kernel_body, _resource_usage
+from codegen_lib import _kernel_body, _resource_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
-NAME = "mirt_trace_rays_multi"
 INF = float("inf")
 
 
-def _strip(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-
-
-HEADER = _strip(os.path.join(ROOT, "include", "mirt_multihit.h"))
-
-
-# ---- header, signature table, library ---------------------------------------------------------------------------------------------
-def test_the_extension_header_agrees_with_the_signature_table():
-    assert [name for name, _, _ in prototypes(HEADER)] == list(multihit.MULTIHIT_SIGNATURES) == [NAME]
-    assert sorted(set(re.findall(r"\b(mirt_[a-z0-9_]+)\s*\(", HEADER))) == [NAME]
-    assert compare_prototypes(HEADER, multihit.MULTIHIT_SIGNATURES) == []
-    pointer, i32, i64, u32 = "pointer", (4, True, False), (8, True, False), (4, False, False)
-    assert prototypes(HEADER)[0] == (NAME, i32, [pointer, pointer, i64, i32, pointer, pointer, u32, pointer])
-    assert constants(HEADER) == {"MIRT_MULTIHIT_MAX_K": 8} and multihit.MIRT_MULTIHIT_MAX_K == 8
-    assert re.search(r'^#include "mirt.h"$', HEADER, flags=re.M)
-    restype, argtypes = multihit.MULTIHIT_SIGNATURES[NAME]
-    assert compare_prototypes(HEADER, {NAME: (restype, argtypes[:-1])}) == [f"{NAME}: 8 parameters, the table has 7"]
-    # the header says that the tree defines the answer and that the visiting order does not matter
+# ---- header, wrappers ----------------------------------------------------------------------------------------------------------------
+def test_the_header_says_that_the_tree_defines_the_answer_and_the_visiting_order_does_not_matter():
     text = " ".join(open(os.path.join(ROOT, "include", "mirt_multihit.h")).read().replace(" *", " ").split())
     assert "defined by the tree, not by the scene's arrays" in text and "S does not depend on the visiting order" in text
     assert "(t, class, index)" in text
-    assert "MIRT_VERSION 3" in " ".join(open(os.path.join(ROOT, "include", "mirt.h")).read().split())
-
-
-def test_the_other_headers_and_tables_do_not_know_the_extension():
-    for header in ("mirt.h", "mirt_light.h", "mirt_visibility.h", "mirt_indirect.h", "mirt_closest.h"):
-        assert NAME not in open(os.path.join(ROOT, "include", header)).read()
-    for table in (binding.SIGNATURES, lighting.LIGHT_SIGNATURES, visibility.VISIBILITY_SIGNATURES, indirect.INDIRECT_SIGNATURES,
-                  closest.CLOSEST_SIGNATURES):
-        assert NAME not in table
-
-
-def test_library_exports_the_symbol_and_the_signature_is_applied():
-    out = subprocess.run(["nm", "-D", "--defined-only", B.LIB], capture_output=True, text=True, check=True).stdout
-    assert re.search(r"\bT mirt_trace_rays_multi$", out, flags=re.M)
-    f = multihit.lib().mirt_trace_rays_multi
-    assert f.restype is C.c_int and list(f.argtypes) == multihit.MULTIHIT_SIGNATURES[NAME][1]
-    for name in ("trace_rays_multi", "count_hits"):
-        assert getattr(m, name) is getattr(multihit, name) is getattr(api, name) and name in m.__all__, name
-
-
-def test_the_multihit_module_needs_neither_torch_nor_numpy():
-    code = "import sys; import cuda_ray_tracer_amd.multihit; assert 'torch' not in sys.modules and 'numpy' not in sys.modules, sorted(sys.modules)"
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-
-
-def test_the_build_depends_on_the_extension_header_and_the_kernel():
-    deps = [os.path.normpath(d) for d in B._all_deps()]
-    assert os.path.join(ROOT, "include", "mirt_multihit.h") in deps and os.path.join(B.CSRC, "multihit.hip") in deps
-    assert "multihit.hip" in B.LIB_SOURCES
-
-
-def test_null_scene_is_an_argument_error():
-    L = multihit.lib()
-    assert L.mirt_trace_rays_multi(None, None, 0, 0, None, None, 0, None) == 3
-    assert L.mirt_trace_rays_multi(None, None, 5, 4, None, None, 0, None) == 3
-    assert b"mirt_trace_rays_multi" in m.lib().mirt_last_error()
 
 
 def test_wrappers_check_their_tensors_before_calling_the_library():

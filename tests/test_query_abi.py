@@ -3,8 +3,6 @@ No compute calls are made here (no GPU needed)."""
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 import types
 
 import numpy as np
@@ -12,7 +10,7 @@ import pytest
 
 import cuda_ray_tracer_amd as m
 from cuda_ray_tracer_amd import api
-from cuda_ray_tracer_amd import build as B
+from codegen_lib import _kernel_body, _resource_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -120,42 +118,6 @@ def test_pack_rays_and_unpack_hits_round_trip():
     assert hits.view(torch.float32)[0, 0].item() == 42.0
     h = api.Hit.from_buffer_copy(hits[3].numpy().tobytes())
     assert (h.t, h.kind, h.id, h.n.z) == (rec["t"][3], rec["kind"][3], rec["id"][3], rec["n"][3][2])
-
-
-def _resource_usage(src):
-    with tempfile.TemporaryDirectory(prefix="mirt_codegen_") as tmp:       # private: /tmp is shared between users
-        out = os.path.join(tmp, "q.s")
-        cmd = [B._hipcc()] + [c for c in B.COMMON if c != "-fPIC"] + ["-x", "hip", "-S", "--cuda-device-only", os.path.join(B.CSRC, src),
-                                                                      "-o", out, "-Rpass-analysis=kernel-resource-usage"]
-        r = subprocess.run(cmd, capture_output=True, text=True, check=True)
-        asm = open(out).read()
-    res, cur = {}, None
-    for line in r.stderr.splitlines():
-        mm = re.search(r"Function Name: (\S+)", line)
-        if mm:
-            cur = mm.group(1)
-            res[cur] = {}
-            continue
-        mm = re.search(r"remark: \s*([^:]+):\s*(\d+)\s*\[-Rpass", line)
-        if cur and mm:
-            res[cur][mm.group(1).strip()] = int(mm.group(2))
-    return res, asm
-
-
-def _kernel_body(asm, name):
-    body, inside = [], False
-    for l in asm.splitlines():
-        if l.startswith(name + ":"):
-            inside = True
-            continue
-        if inside and "s_endpgm" in l:
-            break
-        if inside:
-            t = l.split(";")[0].strip()
-            if t and not t.startswith("."):
-                body.append(t)
-    assert body, name
-    return body
 
 
 def test_query_kernel_codegen_runs_8_waves_per_simd_with_scratch_only_on_the_spill_path():

@@ -15,7 +15,7 @@ import pytest
 import cuda_ray_tracer_amd as m
 from cuda_ray_tracer_amd import api, layouts
 from cuda_ray_tracer_amd import build as B
-import test_query_abi
+import codegen_lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -244,7 +244,7 @@ def test_there_is_one_copy_of_the_flags_rule():
 
 
 def test_material_kernels_use_no_scratch():
-    res, asm = test_query_abi._resource_usage("update_shading.hip")
+    res, asm = codegen_lib._resource_usage("update_shading.hip")
     kernels = sorted(k for k in res if any(n in k for n in ("update_materials_kernel", "material_flags_kernel", "get_materials_kernel", "reduce_flags_kernel")))
     assert len(kernels) == 4, list(res)
     for k in kernels:

@@ -11,7 +11,7 @@ import pytest
 import cuda_ray_tracer_amd as m
 from cuda_ray_tracer_amd import api
 from cuda_ray_tracer_amd import build as B
-import test_query_abi
+import codegen_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("mirt_scene_get_camera", "mirt_scene_set_camera", "mirt_multi_set_camera", "mirt_scene_update_spheres",
@@ -98,7 +98,7 @@ def test_update_kernels_use_no_scratch():
     spills, no private arrays).  Nothing is asserted about fused multiply-adds: the expansions the compiler emits for IEEE `/` and
     sqrtf contain them, and the assembly cannot tell those from a contraction of the source -- what pins the arithmetic is the
     bit-for-bit comparison of device-computed with host-computed triangle records in test_gpu_update.py."""
-    res, asm = test_query_abi._resource_usage("update.hip")
+    res, asm = codegen_lib._resource_usage("update.hip")
     kernels = sorted(k for k in res if "update_spheres_kernel" in k or "update_triangles_kernel" in k)
     assert len(kernels) == 2, list(res)
     for k in kernels:

@@ -14,47 +14,13 @@ brute force  on tenthousand (spheres and planes only): every point against every
 Timed with HIP events over back-to-back repetitions totalling at least --min-seconds of device time after a warm-up, repeated
 --repeats times (median, min, max).  Prints one JSON line and, with --out, writes it to a file.
 """
-import argparse
-import json
-import math
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import cuda_ray_tracer_amd as m  # noqa: E402
-
-DEV = "cuda"
-INF = float("inf")
-
-
-def timed(fn, rows, repeats, min_seconds):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    one = max(e0.elapsed_time(e1) * 1e-3, 1e-6)
-    reps = max(1, int(math.ceil(min_seconds / one)))
-    rates = []
-    for _ in range(repeats):
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        rates.append(rows * reps / (e0.elapsed_time(e1) * 1e-3))
-    rates.sort()
-    med = rates[len(rates) // 2]
-    return dict(mpoints_per_s=round(med * 1e-6, 3), min=round(rates[0] * 1e-6, 3), max=round(rates[-1] * 1e-6, 3), repetitions=reps,
-                ms_per_call=round(1e3 * rows / med, 4))
+import bench_common as bc
+from bench_common import DEV, INF, m
 
 
 class BruteForce:
@@ -86,7 +52,7 @@ def measure(raw, rows, a, brute=None):
     hits = torch.empty((n, 6), dtype=torch.int32, device=DEV)
     feat = torch.empty((n, 8), dtype=torch.float32, device=DEV)
     res = dict(points=n)
-    res["closest"] = timed(lambda: m.closest_points(raw, rows, hits, feat), n, a.repeats, a.min_seconds)
+    res["closest"] = bc.timed(lambda: m.closest_points(raw, rows, hits, feat), n, a.repeats, a.min_seconds, "mpoints_per_s", 1e-6)
     t, kind, pid, _ = m.unpack_hits(hits)
     found = kind != 0
     res["found_fraction"] = round(float(found.float().mean()), 4)
@@ -100,7 +66,7 @@ def measure(raw, rows, a, brute=None):
         s_kind, s_pid = kind[:sub.shape[0]], pid[:sub.shape[0]].to(torch.int64)
         want = torch.where(s_kind == 3, -1 - s_pid, s_pid)
         both = (s_kind != 0) & (dist >= 0)
-        res["brute_force"] = timed(bf, sub.shape[0], a.repeats, a.min_seconds)
+        res["brute_force"] = bc.timed(bf, sub.shape[0], a.repeats, a.min_seconds, "mpoints_per_s", 1e-6)
         res["brute_force"]["points"] = sub.shape[0]
         res["brute_force"]["rows_naming_another_primitive"] = int((want != idx)[both].sum())
         res["brute_force"]["rows_found_by_one_only"] = int(((s_kind != 0) != (dist >= 0)).sum())
@@ -109,11 +75,7 @@ def measure(raw, rows, a, brute=None):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--min-seconds", type=float, default=0.5)
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
+    ap = bc.parser()
     ap.add_argument("--synthetic", type=int, default=1_000_000, help="spheres (and as many triangles) of the synthetic scene")
     ap.add_argument("--brute-rows", type=int, default=1 << 18)
     ap.add_argument("--brute-chunk", type=int, default=1 << 14)
@@ -123,18 +85,16 @@ def main():
     ap.add_argument("--out", default=None, help="also write the JSON here, e.g. profiles/closest_bench.json")
     a = ap.parse_args()
     w, h = a.width, a.height
-    result = dict(metric="closest_points_mpoints_per_s", width=w, height=h, repeats=a.repeats, min_seconds=a.min_seconds,
-                  label=a.label, results={})
+    result = dict(metric="closest_points_mpoints_per_s", **bc.settings(a), label=a.label, results={})
     for name in ("tenthousand", "redchair", "synthetic"):
         wanted = [(pts, tag) for pts in ("surface", "uniform") for tag in ("inf", "near") if a.only in (None, f"{name}/{pts}/{tag}")]
         if not wanted:
             continue
-        stl = m.syntheticScene(a.synthetic, a.synthetic) if name == "synthetic" else m.parseInput(os.path.join(ROOT, "scenes", name + ".txt"))
-        raw = m.initRawConfigFromStl(stl, 0)
-        m.build_lbvh_karas(raw)
-        box = raw.tree()[3].astype(np.float64)
-        near = 0.01 * float(np.linalg.norm(box[3:6] - box[0:3]))
-        _, _, F = m.ambient_occlusion_frame(raw, w, h, 0, directions=1)
+        stl = m.syntheticScene(a.synthetic, a.synthetic) if name == "synthetic" else m.parseInput(bc.scene_path(name))
+        raw = bc.built(stl)
+        box, diagonal = bc.box_diagonal(raw)
+        near = 0.01 * diagonal
+        F = bc.first_hit_features(raw, w, h)
         on = F[F[:, 3] != 0]
         surface = (on[:, 0:3] + on[:, 4:7] * 0.05).contiguous()
         g = torch.Generator(device=DEV).manual_seed(1234)
@@ -154,11 +114,7 @@ def main():
             result["results"][f"{name}/{pts}/{tag}"] = r
             print(f"{name}/{pts}/{tag} done", file=sys.stderr, flush=True)
         raw.close()
-    line = json.dumps(result)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(json.dumps(result, indent=1) + "\n")
-    print(line, flush=True)
+    bc.emit(result, a.out, indent=1)
 
 
 if __name__ == "__main__":

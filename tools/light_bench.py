@@ -16,47 +16,11 @@ repeated --repeats times (median, min, max).  The composition's mask is compared
 rounds the facing test's normalisations its own way, so a pair may differ where |cos| < 1e-6 and nowhere else (asserted; the
 counts are reported).  Prints one JSON line.
 """
-import argparse
-import json
-import math
-import os
-import sys
+import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import cuda_ray_tracer_amd as m  # noqa: E402
-
-DEV = "cuda"
-INF = float("inf")
-
-
-def timed(fn, rows, repeats, min_seconds):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    one = max(e0.elapsed_time(e1) * 1e-3, 1e-6)
-    reps = max(1, int(math.ceil(min_seconds / one)))
-    rates = []
-    for _ in range(repeats):
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        rates.append(rows * reps / (e0.elapsed_time(e1) * 1e-3))
-    rates.sort()
-    med = rates[len(rates) // 2]
-    return dict(mrows_per_s=round(med * 1e-6, 3), min=round(rates[0] * 1e-6, 3), max=round(rates[-1] * 1e-6, 3), repetitions=reps,
-                ms_per_call=round(1e3 * rows / med, 4))
+import bench_common as bc
+from bench_common import DEV, INF, m
 
 
 def _unit(v):
@@ -112,7 +76,7 @@ def measure(raw, F, a):
     suns, bulbs = raw.lights()
     L = len(suns) + len(bulbs)
     res = dict(rows=n, lights=L, hit_fraction=round(float((F[:, 3] != 0).float().mean()), 4))
-    res["fused"] = timed(lambda: m.direct_light(raw, F, out, mask), n, a.repeats, a.min_seconds)
+    res["fused"] = bc.timed(lambda: m.direct_light(raw, F, out, mask), n, a.repeats, a.min_seconds, "mrows_per_s", 1e-6)
     if a.fused_only:
         return res
     comp = Composition(raw, F)
@@ -132,7 +96,7 @@ def measure(raw, F, a):
     res["shadow_rays"] = walked
     res["lit_fraction_of_shadow_rays"] = round(int(((mask[:, None] >> comp.shift[None, :]) & 1).sum()) / max(1, walked), 4)
     res["fused"]["gshadow_rays_per_s"] = round(res["fused"]["mrows_per_s"] * 1e-3 * walked / n, 4)
-    res["composition"] = timed(comp, n, a.repeats, a.min_seconds)
+    res["composition"] = bc.timed(comp, n, a.repeats, a.min_seconds, "mrows_per_s", 1e-6)
     res["composition"]["gshadow_rays_per_s"] = round(res["composition"]["mrows_per_s"] * 1e-3 * walked / n, 4)
     res["fused_over_composition"] = round(res["fused"]["mrows_per_s"] / res["composition"]["mrows_per_s"], 3)
     return res
@@ -155,39 +119,31 @@ def workloads(name, suffix):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--min-seconds", type=float, default=0.5)
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
+    ap = bc.parser()
     ap.add_argument("--incoherent", type=int, default=4 << 20)
     ap.add_argument("--only", default=None, help="one workload, e.g. tenthousand+16 (for a counter pass)")
     ap.add_argument("--fused-only", action="store_true")
     a = ap.parse_args()
     w, h = a.width, a.height
-    out = dict(metric="direct_light_mrows_per_s", width=w, height=h, repeats=a.repeats, min_seconds=a.min_seconds, results={})
+    out = dict(metric="direct_light_mrows_per_s", **bc.settings(a), results={})
     extra = {}
     for name in ("tenthousand", "redchair"):
-        text = open(os.path.join(ROOT, "scenes", name + ".txt")).read()
+        text = open(bc.scene_path(name)).read()
         for suffix in ("", "+16"):
             wanted = [k for k in workloads(name, suffix) if a.only in (None, k)]
             later = not suffix and any(a.only in (None, k) for k in workloads(name, "+16"))      # (its hit points place the added bulbs)
             if not wanted and not later:
                 continue
-            raw = m.initRawConfigFromStl(m.parseText(text + (extra[name] if suffix else "")), 0)
-            m.build_lbvh_karas(raw)
+            raw = bc.built(m.parseText(text + (extra[name] if suffix else "")))
             _, _, F = m.direct_light_frame(raw, w, h, 0, want_mask=False)
             if not suffix:
                 extra[name] = added_bulbs(F)
             if name + suffix in wanted:
                 out["results"][name + suffix] = measure(raw, F, a)
             if "incoherent" + suffix in wanted:
-                rows = F[F[:, 3] != 0]
-                g = torch.Generator(device=DEV).manual_seed(1234)
-                pick = torch.randint(0, rows.shape[0], (a.incoherent,), generator=g, device=DEV)
-                out["results"]["incoherent" + suffix] = measure(raw, rows[pick].contiguous(), a)
+                out["results"]["incoherent" + suffix] = measure(raw, bc.incoherent_rows(F[F[:, 3] != 0], a.incoherent), a)
             raw.close()
-    print(json.dumps(out), flush=True)
+    bc.emit(out)
 
 
 if __name__ == "__main__":

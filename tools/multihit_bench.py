@@ -14,45 +14,10 @@ live ray's origin to its hit and shortens its tmax.  The peel's lists are compar
 Timed with HIP events over back-to-back repetitions totalling at least --min-seconds of device time after a warm-up, repeated
 --repeats times (median, min, max).  Prints one JSON line and, with --out, writes it to a file.
 """
-import argparse
-import json
-import math
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import torch  # noqa: E402
-
-import cuda_ray_tracer_amd as m  # noqa: E402
-
-DEV = "cuda"
-
-
-def timed(fn, rays, repeats, min_seconds):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    one = max(e0.elapsed_time(e1) * 1e-3, 1e-6)
-    reps = max(1, int(math.ceil(min_seconds / one)))
-    rates = []
-    for _ in range(repeats):
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        rates.append(rays * reps / (e0.elapsed_time(e1) * 1e-3))
-    rates.sort()
-    med = rates[len(rates) // 2]
-    return dict(grays_per_s=round(med * 1e-9, 4), min=round(rates[0] * 1e-9, 4), max=round(rates[-1] * 1e-9, 4), repetitions=reps,
-                ms_per_call=round(1e3 * rays / med, 4))
+import bench_common as bc
+from bench_common import DEV, m
 
 
 class Peel:
@@ -87,26 +52,17 @@ class Peel:
         return self.out
 
 
-def camera(raw, w, h, spp=0):
-    n = m.num_pixels(m.render_params(w, h, spp))
-    rays = torch.empty((n, 8), dtype=torch.float32, device=DEV)
-    m.camera_rays(raw, rays, w, h, spp)
-    return rays
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--min-seconds", type=float, default=0.5)
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
+    ap = bc.parser()
     ap.add_argument("--incoherent", type=int, default=4 << 20)
     ap.add_argument("--only", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     w, h = a.width, a.height
-    out = dict(metric="multihit_grays_per_s", device=torch.cuda.get_device_name(0), width=w, height=h, repeats=a.repeats, min_seconds=a.min_seconds,
-               results={})
+    out = dict(metric="multihit_grays_per_s", device=torch.cuda.get_device_name(0), **bc.settings(a), results={})
+
+    def timed(fn, n):
+        return bc.timed(fn, n, a.repeats, a.min_seconds, "grays_per_s", 1e-9, 4)
 
     def run(name, raw, rays):
         if a.only and a.only != name:
@@ -115,15 +71,15 @@ def main():
         res = {}
         counts = torch.empty(n, dtype=torch.int32, device=DEV)
         hits1 = torch.empty((n, 6), dtype=torch.int32, device=DEV)
-        res["closest_hit"] = timed(lambda: m.trace_rays(raw, rays, hits1), n, a.repeats, a.min_seconds)
-        res["count_only"] = timed(lambda: m.trace_rays_multi(raw, rays, None, counts), n, a.repeats, a.min_seconds)
+        res["closest_hit"] = timed(lambda: m.trace_rays(raw, rays, hits1), n)
+        res["count_only"] = timed(lambda: m.trace_rays_multi(raw, rays, None, counts), n)
         res["hits_per_ray"] = dict(mean=round(float(counts.float().mean()), 3), max=int(counts.max()),
                                    share_above_8=round(float((counts > 8).float().mean()), 4), share_none=round(float((counts == 0).float().mean()), 4))
         for k in (1, 4, 8):
             hits = torch.empty((n, k, 6), dtype=torch.int32, device=DEV)
-            res[f"k{k}"] = timed(lambda: m.trace_rays_multi(raw, rays, hits, counts), n, a.repeats, a.min_seconds)
+            res[f"k{k}"] = timed(lambda: m.trace_rays_multi(raw, rays, hits, counts), n)
             peel = Peel(raw, rays, k)
-            res[f"peel{k}"] = timed(peel, n, a.repeats, a.min_seconds)
+            res[f"peel{k}"] = timed(peel, n)
             res[f"peel{k}"]["times_k_call"] = round(res[f"peel{k}"]["ms_per_call"] / res[f"k{k}"]["ms_per_call"], 2)
             peeled = peel().view(torch.int32)
             torch.cuda.synchronize()
@@ -136,30 +92,13 @@ def main():
         out["results"][name] = res
 
     for name in ("tenthousand", "redchair"):
-        stl = m.parseInput(os.path.join(ROOT, "scenes", name + ".txt"))
-        raw = m.initRawConfigFromStl(stl, 0)
-        m.build_lbvh_karas(raw)
-        rays = camera(raw, w, h)
+        raw = bc.built(m.parseInput(bc.scene_path(name)))
+        rays = bc.camera(raw, w, h)
         run(name, raw, rays)
         if name == "tenthousand":
-            # incoherent: seeded uniform random directions from the primary hit points (tools/query_bench.py)
-            hits = torch.empty((rays.shape[0], 6), dtype=torch.int32, device=DEV)
-            m.trace_rays(raw, rays, hits)
-            t, kind, _, _ = m.unpack_hits(hits)
-            sel = torch.nonzero(kind != 0).squeeze(1)
-            d = rays[sel, 4:7]
-            d = d / torch.linalg.norm(d, dim=1, keepdim=True)
-            p = rays[sel, 0:3] + t[sel, None] * d
-            g = torch.Generator(device=DEV).manual_seed(1234)
-            pick = torch.randint(0, p.shape[0], (a.incoherent,), generator=g, device=DEV)
-            dirs = torch.randn((a.incoherent, 3), generator=g, device=DEV)
-            run("incoherent", raw, m.pack_rays(p[pick], dirs))
+            run("incoherent", raw, bc.incoherent_rays(raw, rays, a.incoherent))
         raw.close()
-    line = json.dumps(out)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    bc.emit(out, a.out)
 
 
 if __name__ == "__main__":

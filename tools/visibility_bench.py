@@ -17,47 +17,13 @@ repeated --repeats times (median, min, max).  The composition's mask is compared
 number of differing (row, direction) pairs reported: torch rounds a few of the operations its own way, so a ray that grazes a
 surface may fall on the other side.  Prints one JSON line and, with --out, writes it to a file.
 """
-import argparse
-import json
 import math
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import cuda_ray_tracer_amd as m  # noqa: E402
-
-DEV = "cuda"
-INF = float("inf")
-
-
-def timed(fn, rows, repeats, min_seconds):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    one = max(e0.elapsed_time(e1) * 1e-3, 1e-6)
-    reps = max(1, int(math.ceil(min_seconds / one)))
-    rates = []
-    for _ in range(repeats):
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        rates.append(rows * reps / (e0.elapsed_time(e1) * 1e-3))
-    rates.sort()
-    med = rates[len(rates) // 2]
-    return dict(mrows_per_s=round(med * 1e-6, 3), min=round(rates[0] * 1e-6, 3), max=round(rates[-1] * 1e-6, 3), repetitions=reps,
-                ms_per_call=round(1e3 * rows / med, 4))
+import bench_common as bc
+from bench_common import DEV, INF, m
 
 
 class Composition:
@@ -108,7 +74,7 @@ def measure(raw, F, k, radius, a):
     hit = F[:, 3] != 0
     rays_traced = int(hit.sum()) * k
     res = dict(rows=n, directions=k, radius=radius if math.isfinite(radius) else "inf", hit_fraction=round(float(hit.float().mean()), 4), rays=rays_traced)
-    res["fused"] = timed(lambda: m.hemisphere_visibility(raw, F, dirs, out, mask, rot, radius), n, a.repeats, a.min_seconds)
+    res["fused"] = bc.timed(lambda: m.hemisphere_visibility(raw, F, dirs, out, mask, rot, radius), n, a.repeats, a.min_seconds, "mrows_per_s", 1e-6)
     res["fused"]["grays_per_s"] = round(res["fused"]["mrows_per_s"] * 1e-3 * rays_traced / n, 4)
     bit = ((mask[:, None] >> torch.arange(k, dtype=torch.int64, device=DEV)[None, :]) & 1).bool()
     res["visible_fraction_of_rays"] = round(int(bit[hit].sum()) / max(1, rays_traced), 4)
@@ -126,48 +92,36 @@ def measure(raw, F, k, radius, a):
     same = (c_mask == mask) & hit
     res["max_abs_difference_of_the_sums"] = float((c_out[same] - out[same]).abs().max())      # (torch's sum has an order of its own)
     del c_out, c_mask, pairs
-    res["composition"] = timed(comp, n, a.repeats, a.min_seconds)
+    res["composition"] = bc.timed(comp, n, a.repeats, a.min_seconds, "mrows_per_s", 1e-6)
     res["composition"]["grays_per_s"] = round(res["composition"]["mrows_per_s"] * 1e-3 * rays_traced / n, 4)
     res["fused_over_composition"] = round(res["fused"]["mrows_per_s"] / res["composition"]["mrows_per_s"], 3)
     return res
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--min-seconds", type=float, default=0.5)
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
+    ap = bc.parser()
     ap.add_argument("--incoherent", type=int, default=4 << 20)
     ap.add_argument("--only", default=None, help="one workload, e.g. tenthousand/k64/near (for a counter pass)")
     ap.add_argument("--fused-only", action="store_true")
     ap.add_argument("--out", default=None, help="also write the JSON here, e.g. profiles/visibility_bench.json")
     a = ap.parse_args()
     w, h = a.width, a.height
-    result = dict(metric="hemisphere_visibility_mrows_per_s", width=w, height=h, repeats=a.repeats, min_seconds=a.min_seconds, results={})
+    result = dict(metric="hemisphere_visibility_mrows_per_s", **bc.settings(a), results={})
     for name in ("tenthousand", "redchair"):
         sets = [name] + (["incoherent"] if name == "tenthousand" else [])
         wanted = [(rows, k, tag) for rows in sets for k in (8, 64) for tag in ("near", "inf") if a.only in (None, f"{rows}/k{k}/{tag}")]
         if not wanted:
             continue
-        raw = m.initRawConfigFromStl(m.parseInput(os.path.join(ROOT, "scenes", name + ".txt")), 0)
-        m.build_lbvh_karas(raw)
-        box = raw.tree()[3].astype(np.float64)
-        near = 0.05 * float(np.linalg.norm(box[3:6] - box[0:3]))
-        _, _, F = m.ambient_occlusion_frame(raw, w, h, 0, directions=1)
-        hit_rows = F[F[:, 3] != 0]
-        g = torch.Generator(device=DEV).manual_seed(1234)
-        pick = torch.randint(0, hit_rows.shape[0], (a.incoherent,), generator=g, device=DEV)
+        raw = bc.built(m.parseInput(bc.scene_path(name)))
+        near = 0.05 * bc.box_diagonal(raw)[1]
+        F = bc.first_hit_features(raw, w, h)
+        incoherent = bc.incoherent_rows(F[F[:, 3] != 0], a.incoherent) if any(rows != name for rows, _, _ in wanted) else None
         for rows, k, tag in wanted:
-            rows_f = F if rows == name else hit_rows[pick].contiguous()
+            rows_f = F if rows == name else incoherent
             result["results"][f"{rows}/k{k}/{tag}"] = measure(raw, rows_f, k, near if tag == "near" else INF, a)
             print(f"{rows}/k{k}/{tag} done", file=sys.stderr, flush=True)
         raw.close()
-    line = json.dumps(result)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(json.dumps(result, indent=1) + "\n")
-    print(line, flush=True)
+    bc.emit(result, a.out, indent=1)
 
 
 if __name__ == "__main__":

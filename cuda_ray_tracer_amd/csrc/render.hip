@@ -81,8 +81,13 @@ static_assert(sizeof(SunLds) == 24 && offsetof(LightDev, ix) == offsetof(LightDe
 template <bool COUNT, int TABLES, bool QN, int SPECX = 0>
 __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel(const RenderArgs* __restrict__ ap, const HotArgs h)
 {
-  constexpr int SPEC = SPECX & ~(SPEC_LDS_STACK | SPEC_START_LDS);
   constexpr bool LDS_ONLY = (SPECX & SPEC_LDS_STACK) != 0;
+  // ONE_START: the shade loop issues one ray start per pass for the lanes of both its arms (below; batch_next reads it off SPEC:
+  // shade_common.h, batch_setup).  The LDS-only kernels over the quantised records take it.  The others keep a start in either arm,
+  // and with it the code they had: with one start, the kernels whose stack can spill gained spill instructions inside the
+  // traversal loop, and the LDS-only exact-record kernel lost 2.7 % on redchair.txt at 3840 x 2160 x 64.
+  constexpr bool ONE_START = LDS_ONLY && QN;
+  constexpr int SPEC = (SPECX & ~(SPEC_LDS_STACK | SPEC_START_LDS)) | (ONE_START ? SPEC_ONE_START : 0);
   constexpr bool START_LDS = (SPECX & SPEC_START_LDS) != 0;
   // CUR_MARK: inside the traversal loop's steps a lane that is not traversing holds S.cur == REF_NONE, and the steps read that
   // instead of S.trav (a bool the compiler keeps as a byte per lane: moves, a select in the pop and a mask rebuilt per step).
@@ -190,8 +195,19 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
     for (;;) {
       const bool live = !S.trav && S.g >= 0 && !(exhausted && S.batch_pending && !MIRT_HELD);
       if (__ballot(live) == 0) break;
-      if (live && S.batch_pending) batch_next<COUNT, QN, RenderArgs, SPEC>(a, S, cn);
-      if (live && !S.trav && !S.batch_pending) advance<COUNT, QN, SPEC>(a, S, cn, gid, gthreads);
+      // Both arms only set a ray up; one start_ray -- the quantised-axis set-up and the plane loop -- serves every lane that got
+      // one in this pass.  (With a start of its own in either arm the first arm, 4.7 lanes per execution on the headline frame,
+      // paid for a whole ray start that the same pass issued again a few hundred instructions later.)  A shadow ray that a plane
+      // answers leaves the lane not traversing with its batch pending: the next pass serves it.
+      if (ONE_START) {
+        bool go = false;
+        if (live && S.batch_pending) go = batch_setup<COUNT, RenderArgs, SPEC>(a, S, cn);
+        if (live && !go && !S.trav && !S.batch_pending) go = advance_setup<COUNT, SPEC>(a, S, cn, gid, gthreads);
+        if (go) start_ray<COUNT, true, QN>(a, S, cn);
+      } else {
+        if (live && S.batch_pending) batch_next<COUNT, QN, RenderArgs, SPEC>(a, S, cn);
+        if (live && !S.trav && !S.batch_pending) advance<COUNT, QN, SPEC>(a, S, cn, gid, gthreads);
+      }
     }
     if (!exhausted) {
       // lanes without a sample take new ones -- once init_k of them wait, or when the wave has nothing else to do: starting a

@@ -449,6 +449,9 @@ MIRT_DEV bool hit_needs_literal_walk(const RenderArgs& a, const Lane& S)
 //   SPEC_NOBULB  no point lights
 //   SPEC_NOPEND  no transparent material and gi 0: no refraction states, no pending-children list
 constexpr int SPEC_NOTRI = 1, SPEC_NOBULB = 2, SPEC_NOPEND = 4;
+// Not a property of the scene but of the kernel, passed along in SPEC: the kernel's shade loop issues one ray start per pass for
+// the lanes of both its arms (render.hip, ONE_START), and batch_next is batch_setup + start_ray.
+constexpr int SPEC_ONE_START = 32;
 
 template <typename Args, int SPEC = 0>
 MIRT_DEV uint32_t unlit_mask(const Args& a, const f3& pn, const f3& Hp)
@@ -467,12 +470,74 @@ MIRT_DEV uint32_t unlit_mask(const Args& a, const f3& pn, const f3& Hp)
   return m;
 }
 
+// batch_next (below) without the start, for the kernels whose shade loop issues one start_ray per pass for the lanes of both its
+// arms (SPEC_ONE_START): notes the shadow result, selects the next ray of the batch and sets it up -- o, d, inv, limit, shadow,
+// bounce.  Returns whether the lane got a ray; the caller owes it a start_ray<COUNT, true, QN>.
+// Every ray of a batch leaves the batch's origin, and a lane that gets no ray here is either past a ray of this batch (its origin
+// is S.bo already) or past none at all (no_ray in advance_core: nothing reads its ray): the copy stands once, ahead of the kinds.
+// Likewise what the reflection ray sets up is written for every lane past the last light, whether it has such a ray or not: after
+// a reflection ray d and bounce hold these values already, without one nothing reads them (no_ray again), and inv and limit of a
+// lane without a ray are dead until its next ray is set up.  (As an `else if` of its own, as in batch_next, the reflection ray's
+// copies became a nested exec region in the traversal loop's header arm once the shade loop had one start, with a branch around
+// it.)  S.trav is false already: every caller's lane is not traversing.
+template <bool COUNT, typename Args, int SPEC>
+MIRT_DEV bool batch_setup(const Args& a, Lane& S, Counters& cn)
+{
+  constexpr bool NOBULB = (SPEC & SPEC_NOBULB) != 0;
+  const int nlights = NOBULB ? a.num_suns : a.num_suns + a.num_bulbs;
+  if (S.li >= 0 && S.li < nlights) {
+    const bool occluded = (S.plane_id >= 0 && S.tplane < S.limit) || (S.refbest != REF_NONE && S.tbest < S.limit);
+    if (occluded) S.occl |= 1ull << S.li;
+  }
+  bool go = true;
+  {
+    // (the next light whose shadow ray is traced: batch_next)
+    const uint32_t unlit = (nlights <= 32) ? (uint32_t)(S.occl >> 32) : 0u;
+    const int from = S.li + 1;
+    const uint32_t rest = (from < 32) ? (unlit | ((1u << from) - 1u)) : 0xffffffffu;
+    const int nxt = (~rest != 0u) ? (int)__builtin_ctz(~rest) : 32;
+    S.li = (unlit != 0u && from < nlights) ? min(nxt, nlights) : from;
+    if (COUNT && unlit) { const int k = __popc(unlit & ~((from < 32) ? ((1u << from) - 1u) : 0xffffffffu) & ((S.li < 32) ? ((1u << S.li) - 1u) : 0xffffffffu)); cn.rays += k; cn.shadow_rays += k; }
+  }
+  S.o = S.bo;
+  S.shadow = false;
+  if (S.li < nlights) {
+    // shadow ray (batch_next has the account)
+    S.limit = INFINITY;
+    S.shadow = a.shadow_anyhit != 0 && (NOBULB || S.li < a.num_suns || !a.reach_check);
+    S.bounce = 1;
+    if (COUNT) cn.shadow_rays++;
+    if (NOBULB || S.li < a.num_suns) {
+      const auto& lt = a.suns[S.li];
+      S.d = mk3(lt.nx, lt.ny, lt.nz); S.inv = mk3(lt.ix, lt.iy, lt.iz);
+    } else {
+      const LightDev& lt = a.bulbs[S.li - a.num_suns];
+      const f3 bd = mk3(lt.x, lt.y, lt.z) - S.Hp;
+      S.d = mkray(S.bo, bd, 1).d;
+      S.inv = mk3(1.0f / S.d.x, 1.0f / S.d.y, 1.0f / S.d.z);
+      S.limit = length(bd);
+    }
+  } else {
+    // the reflection ray, or the end of the batch (S.li > nlights, or no reflection ray)
+    go = S.li == nlights && S.has_reflect;
+    S.d = S.rdir; S.bounce = S.Hbounce - 1;
+    S.inv = mk3(1.0f / S.d.x, 1.0f / S.d.y, 1.0f / S.d.z);
+    S.limit = INFINITY;
+  }
+  S.batch_pending = go;
+  return go;
+}
+
 // The ray of the batch that was in flight has finished: note a shadow result, start the next ray of the batch
 // (shadow rays of diffuseLight, draw.cu:342-374, then the reflection ray of reflectionLight, draw.cu:402-404).
 // Shadow rays consume no random numbers, so tracing them after the reflection direction was drawn changes nothing.
 template <bool COUNT, bool QN = false, typename Args = RenderArgs, int SPEC = 0>
 MIRT_DEV void batch_next(const Args& a, Lane& S, Counters& cn)
 {
+  if (SPEC & SPEC_ONE_START) {
+    if (batch_setup<COUNT, Args, SPEC>(a, S, cn)) start_ray<COUNT, true, QN>(a, S, cn);
+    return;
+  }
   constexpr bool NOBULB = (SPEC & SPEC_NOBULB) != 0;
   const int nlights = NOBULB ? a.num_suns : a.num_suns + a.num_bulbs;
   if (S.li >= 0 && S.li < nlights) {
@@ -834,6 +899,31 @@ MIRT_DEV void advance(const RenderArgs& a, Lane& S, Counters& cn, const long lon
     S.limit = INFINITY;
     start_ray<COUNT, false, QN>(a, S, cn);
   }
+}
+
+// advance without the start (SPEC_ONE_START): the ray is only set up, reciprocal included.  Returns whether the lane got one; the
+// caller owes it a start_ray<COUNT, true, QN>.
+template <bool COUNT, int SPEC>
+MIRT_DEV bool advance_setup(const RenderArgs& a, Lane& S, Counters& cn, const long long gid, const long long gthreads)
+{
+  const int micro = advance_core<COUNT, SPEC>(a, S, cn, gid, gthreads);
+  if (micro == M_DONE) {
+    // (the sample's result and its scheduling statistics: advance)
+    a.samples[S.g] = make_float4(S.L.x, S.L.y, S.L.z, S.alpha);
+    if (COUNT && a.chunk_cost) {
+      uint32_t* cc = &a.chunk_cost[S.g >> a.chunk_shift];
+      if (S.steps > *cc) atomicMax(cc, S.steps);
+    }
+    if (COUNT && a.sample_key) a.sample_key[S.g] = cost_key(S.steps);
+    S.g = -1;
+    S.trav = false;
+    return false;
+  }
+  if (micro == M_BATCH) return batch_setup<COUNT, RenderArgs, SPEC>(a, S, cn);
+  S.shadow = false;
+  S.limit = INFINITY;
+  S.inv = mk3(1.0f / S.d.x, 1.0f / S.d.y, 1.0f / S.d.z);
+  return true;
 }
 
 // Start sample `idx` on this lane: pixel, RNG stream, jitter, primary ray (draw.cu:105-123 / 162-171).

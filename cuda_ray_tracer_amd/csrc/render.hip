@@ -132,18 +132,7 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
   bool exhausted = false;                      // wave-uniform: the global counter has run past the frame
 
   Lane S;
-  S.g = -1; S.trav = false;
-  S.rng.v0 = S.rng.v1 = S.rng.v2 = S.rng.v3 = S.rng.v4 = S.rng.d = 0; S.rng.bm_flag = 0; S.rng.bm_extra = 0.0f;
-  S.L = mk3(0, 0, 0); S.alpha = 0.0f; S.steps = 0;
-  S.Hdir = mk3(0, 0, 0); S.Hp = mk3(0, 0, 0); S.Hn = mk3(0, 0, 0); S.Hcolor = mk3(0, 0, 0);
-  S.Hbounce = 0; S.Hior = 1.458f; S.Hrough = 0.0f; S.HtransNZ = false;
-  S.wt = mk3(1, 1, 1); S.wD = mk3(0, 0, 0); S.pn = mk3(0, 0, 0);
-  S.pc = 0; S.refr_bounce = 0; S.gi_n = 0; S.state = ST_PRIMARY;
-  S.bo = mk3(0, 0, 0); S.rdir = mk3(0, 0, 1); S.li = 0; S.occl = 0ull; S.batch_pending = false; S.has_reflect = false;
-  S.o = mk3(0, 0, 0); S.d = mk3(0, 0, 1); S.inv = mk3(0, 0, 1); S.bounce = 0; S.limit = INFINITY; S.shadow = false;
-  S.tplane = INFINITY; S.plane_id = -1;
-  S.qb = mk3(0, 0, 0); S.qc = mk3(0, 0, 0); S.qsx = S.qsy = S.qsz = 0;
-  S.cur = REF_NONE; S.tos = REF_NONE; S.sp = 0; S.tbest = INFINITY; S.refbest = REF_NONE;
+  lane_reset(S);
 
   lds_rng[0][tid] = make_uint4(0, 0, 0, 0);
   lds_rng[1][tid] = make_uint4(0, 0, 0, 0);
@@ -469,23 +458,7 @@ __global__ void __launch_bounds__(TRACE_BLOCK, MIRT_WAVES_PER_SIMD) trace_kernel
     }
   }
 
-  unsigned long long* const counters = COUNT ? ap->counters : nullptr;
-  if (COUNT && counters) {
-    uint32_t v[9] = {cn.samples, cn.rays, cn.shadow_rays, cn.internal_visits, cn.sphere_tests, cn.tri_tests, cn.mat_fetches, cn.max_stack, cn.traversed};
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      unsigned long long x = v[k];
-      if (k == 7) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { unsigned long long y = __shfl_xor(x, off); x = x > y ? x : y; }
-        if ((tid & 63) == 0) atomicMax(&counters[k], x);
-      } else {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-        if ((tid & 63) == 0) atomicAdd(&counters[k == 8 ? 11 : k], x);      // ([8..10]: work counter, overflow events, scratch)
-      }
-    }
-  }
+  if (COUNT) flush_counters(cn, ap->counters, tid);
 }
 #undef MIRT_HELD
 

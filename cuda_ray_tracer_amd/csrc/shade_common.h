@@ -331,8 +331,47 @@ struct Lane {
   uint32_t refbest;
 };
 
+// A lane before its first sample: no sample, no ray, not traversing.
+MIRT_DEV void lane_reset(Lane& S)
+{
+  S.g = -1; S.trav = false;
+  S.rng.v0 = S.rng.v1 = S.rng.v2 = S.rng.v3 = S.rng.v4 = S.rng.d = 0; S.rng.bm_flag = 0; S.rng.bm_extra = 0.0f;
+  S.L = mk3(0, 0, 0); S.alpha = 0.0f; S.steps = 0;
+  S.Hdir = mk3(0, 0, 0); S.Hp = mk3(0, 0, 0); S.Hn = mk3(0, 0, 0); S.Hcolor = mk3(0, 0, 0);
+  S.Hbounce = 0; S.Hior = 1.458f; S.Hrough = 0.0f; S.HtransNZ = false;
+  S.wt = mk3(1, 1, 1); S.wD = mk3(0, 0, 0); S.pn = mk3(0, 0, 0);
+  S.pc = 0; S.refr_bounce = 0; S.gi_n = 0; S.state = ST_PRIMARY;
+  S.bo = mk3(0, 0, 0); S.rdir = mk3(0, 0, 1); S.li = 0; S.occl = 0ull; S.batch_pending = false; S.has_reflect = false;
+  S.o = mk3(0, 0, 0); S.d = mk3(0, 0, 1); S.inv = mk3(0, 0, 1); S.bounce = 0; S.limit = INFINITY; S.shadow = false;
+  S.tplane = INFINITY; S.plane_id = -1;
+  S.qb = mk3(0, 0, 0); S.qc = mk3(0, 0, 0); S.qsx = S.qsy = S.qsz = 0;
+  S.cur = REF_NONE; S.tos = REF_NONE; S.sp = 0; S.tbest = INFINITY; S.refbest = REF_NONE;
+}
+
+// The end of a counting kernel: each wave sums (max_stack: takes the maximum of) its lanes' counters and adds the result to the
+// frame's.  `counters` may be null: nothing is counted then.
+MIRT_DEV void flush_counters(const Counters& cn, unsigned long long* const counters, const int tid)
+{
+  if (!counters) return;
+  uint32_t v[9] = {cn.samples, cn.rays, cn.shadow_rays, cn.internal_visits, cn.sphere_tests, cn.tri_tests, cn.mat_fetches, cn.max_stack, cn.traversed};
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    unsigned long long x = v[k];
+    if (k == 7) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) { unsigned long long y = __shfl_xor(x, off); x = x > y ? x : y; }
+      if ((tid & 63) == 0) atomicMax(&counters[k], x);
+    } else {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+      if ((tid & 63) == 0) atomicAdd(&counters[k == 8 ? 11 : k], x);      // ([8..10]: work counter, overflow events, scratch)
+    }
+  }
+}
+
 // checkPlane, draw.cu:581-615: the nearest plane hit (plane_id -1: none).  The loop of start_ray below, for the query kernel
-// (query.hip); start_ray keeps its own copy: calling this from there moved the trace kernels' register allocation.
+// (query.hip) and the wavefront trace kernel; start_ray keeps its own copy: calling this from there moved the trace kernels'
+// register allocation.
 MIRT_DEV void nearest_plane(const PlaneDev* planes_in, int num_planes, const f3& o, const f3& d, float& tplane, int& plane_id)
 {
   tplane = INFINITY;
@@ -470,6 +509,47 @@ MIRT_DEV uint32_t unlit_mask(const Args& a, const f3& pn, const f3& Hp)
   return m;
 }
 
+// The pieces of a batch's ray selection that batch_setup and batch_next (below) have in common.
+// The batch ray that was in flight, if it was a shadow ray, has finished: its result goes into S.occl.
+MIRT_DEV void note_shadow_result(Lane& S, const int nlights)
+{
+  if (S.li >= 0 && S.li < nlights) {
+    const bool occluded = (S.plane_id >= 0 && S.tplane < S.limit) || (S.refbest != REF_NONE && S.tbest < S.limit);
+    if (occluded) S.occl |= 1ull << S.li;
+  }
+}
+
+// S.li becomes the next light whose shadow ray is traced: the upper half of S.occl marks the lights the shading normal faces away
+// from (unlit_mask, set when the node was entered); their rays count as rays but visit nothing
+template <bool COUNT>
+MIRT_DEV void next_light(Lane& S, Counters& cn, const int nlights)
+{
+  const uint32_t unlit = (nlights <= 32) ? (uint32_t)(S.occl >> 32) : 0u;      // (with more lights those bits are occlusion bits)
+  const int from = S.li + 1;
+  const uint32_t rest = (from < 32) ? (unlit | ((1u << from) - 1u)) : 0xffffffffu;       // lights before `from` are done
+  const int nxt = (~rest != 0u) ? (int)__builtin_ctz(~rest) : 32;
+  S.li = (unlit != 0u && from < nlights) ? min(nxt, nlights) : from;                     // (from > nlights after the reflection ray: the batch is over)
+  if (COUNT && unlit) { const int k = __popc(unlit & ~((from < 32) ? ((1u << from) - 1u) : 0xffffffffu) & ((S.li < 32) ? ((1u << S.li) - 1u) : 0xffffffffu)); cn.rays += k; cn.shadow_rays += k; }
+}
+
+// Direction, reciprocal and -- towards a point light -- limit of the shadow ray to light S.li (draw.cu:346 / 362-363); the limit
+// of a sun's ray, INFINITY, is the caller's.
+template <bool NOBULB, typename Args>
+MIRT_DEV void shadow_ray_towards(const Args& a, Lane& S)
+{
+  if (NOBULB || S.li < a.num_suns) {
+    // direction and its reciprocal are per-light constants (host-computed, same arithmetic)
+    const auto& lt = a.suns[S.li];      // (a LightDev, or the SPEC_START_LDS kernel's LDS copy of these six words)
+    S.d = mk3(lt.nx, lt.ny, lt.nz); S.inv = mk3(lt.ix, lt.iy, lt.iz);
+  } else {
+    const LightDev& lt = a.bulbs[S.li - a.num_suns];
+    const f3 bd = mk3(lt.x, lt.y, lt.z) - S.Hp;
+    S.d = mkray(S.bo, bd, 1).d;
+    S.inv = mk3(1.0f / S.d.x, 1.0f / S.d.y, 1.0f / S.d.z);
+    S.limit = length(bd);
+  }
+}
+
 // batch_next (below) without the start, for the kernels whose shade loop issues one start_ray per pass for the lanes of both its
 // arms (SPEC_ONE_START): notes the shadow result, selects the next ray of the batch and sets it up -- o, d, inv, limit, shadow,
 // bounce.  Returns whether the lane got a ray; the caller owes it a start_ray<COUNT, true, QN>.
@@ -485,20 +565,9 @@ MIRT_DEV bool batch_setup(const Args& a, Lane& S, Counters& cn)
 {
   constexpr bool NOBULB = (SPEC & SPEC_NOBULB) != 0;
   const int nlights = NOBULB ? a.num_suns : a.num_suns + a.num_bulbs;
-  if (S.li >= 0 && S.li < nlights) {
-    const bool occluded = (S.plane_id >= 0 && S.tplane < S.limit) || (S.refbest != REF_NONE && S.tbest < S.limit);
-    if (occluded) S.occl |= 1ull << S.li;
-  }
+  note_shadow_result(S, nlights);
   bool go = true;
-  {
-    // (the next light whose shadow ray is traced: batch_next)
-    const uint32_t unlit = (nlights <= 32) ? (uint32_t)(S.occl >> 32) : 0u;
-    const int from = S.li + 1;
-    const uint32_t rest = (from < 32) ? (unlit | ((1u << from) - 1u)) : 0xffffffffu;
-    const int nxt = (~rest != 0u) ? (int)__builtin_ctz(~rest) : 32;
-    S.li = (unlit != 0u && from < nlights) ? min(nxt, nlights) : from;
-    if (COUNT && unlit) { const int k = __popc(unlit & ~((from < 32) ? ((1u << from) - 1u) : 0xffffffffu) & ((S.li < 32) ? ((1u << S.li) - 1u) : 0xffffffffu)); cn.rays += k; cn.shadow_rays += k; }
-  }
+  next_light<COUNT>(S, cn, nlights);
   S.o = S.bo;
   S.shadow = false;
   if (S.li < nlights) {
@@ -507,16 +576,7 @@ MIRT_DEV bool batch_setup(const Args& a, Lane& S, Counters& cn)
     S.shadow = a.shadow_anyhit != 0 && (NOBULB || S.li < a.num_suns || !a.reach_check);
     S.bounce = 1;
     if (COUNT) cn.shadow_rays++;
-    if (NOBULB || S.li < a.num_suns) {
-      const auto& lt = a.suns[S.li];
-      S.d = mk3(lt.nx, lt.ny, lt.nz); S.inv = mk3(lt.ix, lt.iy, lt.iz);
-    } else {
-      const LightDev& lt = a.bulbs[S.li - a.num_suns];
-      const f3 bd = mk3(lt.x, lt.y, lt.z) - S.Hp;
-      S.d = mkray(S.bo, bd, 1).d;
-      S.inv = mk3(1.0f / S.d.x, 1.0f / S.d.y, 1.0f / S.d.z);
-      S.limit = length(bd);
-    }
+    shadow_ray_towards<NOBULB>(a, S);
   } else {
     // the reflection ray, or the end of the batch (S.li > nlights, or no reflection ray)
     go = S.li == nlights && S.has_reflect;
@@ -540,45 +600,23 @@ MIRT_DEV void batch_next(const Args& a, Lane& S, Counters& cn)
   }
   constexpr bool NOBULB = (SPEC & SPEC_NOBULB) != 0;
   const int nlights = NOBULB ? a.num_suns : a.num_suns + a.num_bulbs;
-  if (S.li >= 0 && S.li < nlights) {
-    const bool occluded = (S.plane_id >= 0 && S.tplane < S.limit) || (S.refbest != REF_NONE && S.tbest < S.limit);
-    if (occluded) S.occl |= 1ull << S.li;
-  }
+  note_shadow_result(S, nlights);
   // the lanes of a wave are at different rays of their batches: each kind only sets the ray up, and all of them share
   // one start_ray (one copy of the plane loop instead of three executed one after the other)
   bool go = true;
-  // next light whose shadow ray is traced: the upper half of S.occl marks the lights the shading normal faces away from
-  // (unlit_mask, set when the node was entered); their rays count as rays but visit nothing
-  {
-    const uint32_t unlit = (nlights <= 32) ? (uint32_t)(S.occl >> 32) : 0u;      // (with more lights those bits are occlusion bits)
-    const int from = S.li + 1;
-    const uint32_t rest = (from < 32) ? (unlit | ((1u << from) - 1u)) : 0xffffffffu;       // lights before `from` are done
-    const int nxt = (~rest != 0u) ? (int)__builtin_ctz(~rest) : 32;
-    S.li = (unlit != 0u && from < nlights) ? min(nxt, nlights) : from;                     // (from > nlights after the reflection ray: the batch is over)
-    if (COUNT && unlit) { const int k = __popc(unlit & ~((from < 32) ? ((1u << from) - 1u) : 0xffffffffu) & ((S.li < 32) ? ((1u << S.li) - 1u) : 0xffffffffu)); cn.rays += k; cn.shadow_rays += k; }
-  }
+  next_light<COUNT>(S, cn, nlights);
   if (S.li < nlights) {
     // shadow ray, draw.cu:346 / 362-363
     S.o = S.bo;
     S.limit = INFINITY;
     // shadow_anyhit = 0: the ray is traced to its nearest hit like any other, exactly as hitNearest does for diffuseLight
-    // (draw.cu:347-352, 365-370); the occlusion test above reads the same boolean off the result either way
+    // (draw.cu:347-352, 365-370); note_shadow_result reads the same boolean off the result either way
     // (towards a point light, in a walk that is not the reference's own, the ray is traced to its nearest hit all the same and
     // that hit is vetted like any other -- hit_needs_literal_walk: "occluded" there means nearer than the light)
     S.shadow = a.shadow_anyhit != 0 && (NOBULB || S.li < a.num_suns || !a.reach_check);
     S.bounce = 1;
     if (COUNT) cn.shadow_rays++;
-    if (NOBULB || S.li < a.num_suns) {
-      // direction and its reciprocal are per-light constants (host-computed, same arithmetic)
-      const auto& lt = a.suns[S.li];      // (a LightDev, or the SPEC_START_LDS kernel's LDS copy of these six words)
-      S.d = mk3(lt.nx, lt.ny, lt.nz); S.inv = mk3(lt.ix, lt.iy, lt.iz);
-    } else {
-      const LightDev& lt = a.bulbs[S.li - a.num_suns];
-      const f3 bd = mk3(lt.x, lt.y, lt.z) - S.Hp;
-      S.d = mkray(S.bo, bd, 1).d;
-      S.inv = mk3(1.0f / S.d.x, 1.0f / S.d.y, 1.0f / S.d.z);
-      S.limit = length(bd);
-    }
+    shadow_ray_towards<NOBULB>(a, S);
   } else if (S.li == nlights && S.has_reflect) {
     S.o = S.bo; S.d = S.rdir; S.bounce = S.Hbounce - 1;
     S.inv = mk3(1.0f / S.d.x, 1.0f / S.d.y, 1.0f / S.d.z);
@@ -876,22 +914,29 @@ MIRT_DEV uint32_t cost_key(uint32_t steps)
   return 255u - (uint32_t)(4 * e) - frac;
 }
 
+// The sample of lane S is complete: its result, its scheduling statistics, and the lane is free.
+template <bool COUNT>
+MIRT_DEV void finish_sample(const RenderArgs& a, Lane& S)
+{
+  a.samples[S.g] = make_float4(S.L.x, S.L.y, S.L.z, S.alpha);
+  // scheduling statistic: the chunk's most expensive sample.  A plain (possibly stale, never too large) load first: most
+  // samples are not their chunk's maximum and issue no atomic (one atomic per sample was 0.76 GB of write traffic per frame)
+  if (COUNT && a.chunk_cost) {
+    uint32_t* cc = &a.chunk_cost[S.g >> a.chunk_shift];
+    if (S.steps > *cc) atomicMax(cc, S.steps);
+  }
+  if (COUNT && a.sample_key) a.sample_key[S.g] = cost_key(S.steps);
+  S.g = -1;
+  S.trav = false;
+}
+
 // Megakernel form: consume the finished trace, shade, and start the next ray of this lane (or finish the sample).
 template <bool COUNT, bool QN = false, int SPEC = 0>
 MIRT_DEV void advance(const RenderArgs& a, Lane& S, Counters& cn, const long long gid, const long long gthreads)
 {
   const int micro = advance_core<COUNT, SPEC>(a, S, cn, gid, gthreads);
   if (micro == M_DONE) {
-    a.samples[S.g] = make_float4(S.L.x, S.L.y, S.L.z, S.alpha);
-    // scheduling statistic: the chunk's most expensive sample.  A plain (possibly stale, never too large) load first: most
-    // samples are not their chunk's maximum and issue no atomic (one atomic per sample was 0.76 GB of write traffic per frame)
-    if (COUNT && a.chunk_cost) {
-      uint32_t* cc = &a.chunk_cost[S.g >> a.chunk_shift];
-      if (S.steps > *cc) atomicMax(cc, S.steps);
-    }
-    if (COUNT && a.sample_key) a.sample_key[S.g] = cost_key(S.steps);
-    S.g = -1;
-    S.trav = false;
+    finish_sample<COUNT>(a, S);
   } else if (micro == M_BATCH) {
     batch_next<COUNT, QN, RenderArgs, SPEC>(a, S, cn);
   } else {
@@ -908,15 +953,7 @@ MIRT_DEV bool advance_setup(const RenderArgs& a, Lane& S, Counters& cn, const lo
 {
   const int micro = advance_core<COUNT, SPEC>(a, S, cn, gid, gthreads);
   if (micro == M_DONE) {
-    // (the sample's result and its scheduling statistics: advance)
-    a.samples[S.g] = make_float4(S.L.x, S.L.y, S.L.z, S.alpha);
-    if (COUNT && a.chunk_cost) {
-      uint32_t* cc = &a.chunk_cost[S.g >> a.chunk_shift];
-      if (S.steps > *cc) atomicMax(cc, S.steps);
-    }
-    if (COUNT && a.sample_key) a.sample_key[S.g] = cost_key(S.steps);
-    S.g = -1;
-    S.trav = false;
+    finish_sample<COUNT>(a, S);
     return false;
   }
   if (micro == M_BATCH) return batch_setup<COUNT, RenderArgs, SPEC>(a, S, cn);

@@ -123,17 +123,7 @@ __global__ void __launch_bounds__(SBLOCK, MIRT_WF_SHADE_WAVES) wf_shade_kernel(c
   Counters cn = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 
   Lane S;
-  S.g = -1;
-  S.rng.v0 = S.rng.v1 = S.rng.v2 = S.rng.v3 = S.rng.v4 = S.rng.d = 0; S.rng.bm_flag = 0; S.rng.bm_extra = 0.0f;
-  S.L = mk3(0, 0, 0); S.alpha = 0.0f;
-  S.Hdir = mk3(0, 0, 0); S.Hp = mk3(0, 0, 0); S.Hn = mk3(0, 0, 0); S.Hcolor = mk3(0, 0, 0);
-  S.Hbounce = 0; S.Hior = 1.458f; S.Hrough = 0.0f; S.HtransNZ = false;
-  S.wt = mk3(1, 1, 1); S.wD = mk3(0, 0, 0); S.pn = mk3(0, 0, 0);
-  S.pc = 0; S.refr_bounce = 0; S.gi_n = 0; S.state = ST_PRIMARY;
-  S.bo = mk3(0, 0, 0); S.rdir = mk3(0, 0, 1); S.li = 0; S.occl = 0ull; S.batch_pending = false; S.has_reflect = false;
-  S.o = mk3(0, 0, 0); S.d = mk3(0, 0, 1); S.inv = mk3(0, 0, 1); S.bounce = 0; S.limit = INFINITY; S.shadow = false;
-  S.tplane = INFINITY; S.plane_id = -1; S.trav = false;
-  S.cur = REF_NONE; S.tos = REF_NONE; S.sp = 0; S.tbest = INFINITY; S.refbest = REF_NONE;
+  lane_reset(S);
 
   int micro = WM_FREE;
   if (valid) {
@@ -145,8 +135,7 @@ __global__ void __launch_bounds__(SBLOCK, MIRT_WF_SHADE_WAVES) wf_shade_kernel(c
   }
   unsigned long long done_local = 0;
   if (micro == M_DONE) {
-    a.samples[S.g] = make_float4(S.L.x, S.L.y, S.L.z, S.alpha);
-    S.g = -1;
+    finish_sample<false>(a, S);      // (the scheduling statistics are the single kernel's)
     micro = WM_FREE;
     ++done_local;
   }
@@ -254,12 +243,7 @@ __global__ void __launch_bounds__(SBLOCK, MIRT_WF_SHADE_WAVES) wf_shade_kernel(c
       if (t) atomicAdd(&w.ctr[3], t);
     }
   }
-  if (COUNT && a.counters) {
-    unsigned long long s0 = cn.samples, s6 = cn.mat_fetches, s1 = cn.rays, s2 = cn.shadow_rays;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_xor(s0, off); s6 += __shfl_xor(s6, off); s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
-    if (lane == 0) { if (s0) atomicAdd(&a.counters[0], s0); if (s6) atomicAdd(&a.counters[6], s6); if (s1) atomicAdd(&a.counters[1], s1); if (s2) atomicAdd(&a.counters[2], s2); }
-  }
+  if (COUNT) flush_counters(cn, a.counters, threadIdx.x);
 }
 
 template <bool COUNT>
@@ -336,15 +320,7 @@ __global__ void __launch_bounds__(WBLOCK, MIRT_WF_WAVES_PER_SIMD) wf_trace_kerne
           if (COUNT) { cn.rays++; if (shadow) cn.shadow_rays++; }
           inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
           // hitNearest's plane half (checkPlane, draw.cu:581-615)
-          tplane = INFINITY; plane_id = -1;
-          for (int i = 0; i < a.num_planes; ++i) {
-            const PlaneDev& pl = a.planes[i];
-            const f3 pnor = mk3(pl.nx, pl.ny, pl.nz);
-            const float t = dot(mk3(pl.px, pl.py, pl.pz) - o, pnor) / dot(d, pnor);
-            if (t <= 1e-6f) continue;
-            if (t < tplane && t > EPSILON) { tplane = t; plane_id = i; }
-          }
-          if (tplane >= (float)(INT_MAX - 10)) { tplane = INFINITY; plane_id = -1; }
+          nearest_plane(a.planes, a.num_planes, o, d, tplane, plane_id);
           tbest = INFINITY; refbest = REF_NONE; cur = a.root_ref; sp = 0;
           trav = (a.root_ref != REF_NONE) && !(shadow && anyhit && plane_id >= 0 && tplane < limit);
           if (COUNT && trav) cn.traversed++;
@@ -428,23 +404,7 @@ __global__ void __launch_bounds__(WBLOCK, MIRT_WF_WAVES_PER_SIMD) wf_trace_kerne
     }
   }
 
-  if (COUNT && a.counters) {
-    uint32_t v[9] = {0, cn.rays, cn.shadow_rays, cn.internal_visits, cn.sphere_tests, cn.tri_tests, 0, cn.max_stack, cn.traversed};
-#pragma unroll
-    for (int k = 1; k < 9; ++k) {
-      if (k == 6) continue;
-      unsigned long long x = v[k];
-      if (k == 7) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { unsigned long long y = __shfl_xor(x, off); x = x > y ? x : y; }
-        if (lane == 0) atomicMax(&a.counters[k], x);
-      } else {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-        if (lane == 0 && x) atomicAdd(&a.counters[k == 8 ? 11 : k], x);
-      }
-    }
-  }
+  if (COUNT) flush_counters(cn, a.counters, tid);
 }
 
 __global__ void wf_reset_kernel(uint32_t* state, int pool)
@@ -475,12 +435,9 @@ int wavefront_trace(MirtScene* sc, RenderCtx& cx, RenderArgs& a, bool count, hip
   MIRT_TRY(sc->wf_rays.grow(2 * max_rays, stream, "wf_rays"));
   if (!sc->wf_ctr) MIRT_TRY(sc->wf_ctr.alloc(8, "wf_ctr"));
   if (!sc->wf_ctr_host) MIRT_TRY(sc->wf_ctr_host.alloc(8, "wf_ctr_host"));
-  // pending-children LIFO is indexed by slot here
-  const bool need_pending = sc->any_trans || sc->d.gi != 0;
-  const int pending_slots = need_pending ? 2 * (sc->d.bounces + (sc->d.gi > 0 ? sc->d.gi : 0) + 2) : 0;
-  const size_t pending_need = (size_t)pending_slots * PENDING_WORDS * pool;
-  MIRT_TRY(cx.pending.grow(pending_need, stream, "pending"));
-  a.pending = cx.pending; a.pending_slots = pending_slots;
+  // pending-children LIFO is indexed by slot here: a.pending_slots (the plan's) entries for each slot of the pool
+  MIRT_TRY(cx.pending.grow((size_t)a.pending_slots * PENDING_WORDS * pool, stream, "pending"));
+  a.pending = cx.pending;
 
   if (!sc->wf_trace_blocks) MIRT_HIP(persistent_grid_blocks(sc->device, wf_trace_kernel<false>, WBLOCK, 4, &sc->wf_trace_blocks));
   const int trace_blocks = sc->wf_trace_blocks;

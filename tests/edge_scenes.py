@@ -52,6 +52,11 @@ def single_sphere():
     return HEADER + "color 1 1 1\nsun 1 1 1\nshininess 0.4\nsphere 0 0 -2 0.8\n"
 
 
+def no_light():
+    """No sun and no bulb: a shading node's ray batch is its reflection ray alone."""
+    return HEADER + "bounces 3\ncolor 0.4 0.5 0.6\nshininess 0.5\nplane 0 1 0 1\ncolor 1 0.3 0.2\nshininess 0.4\nsphere 0 0 -2 0.8\n"
+
+
 def single_triangle():
     return HEADER + "color 1 1 1\nsun 0 0 1\nxyz -1 -1 -2\nxyz 1 -1 -2\nxyz 0 1 -2\ntri 1 2 3\n"
 
@@ -172,5 +177,5 @@ def axis_parallel_rays(n=6):
 
 
 ALL = {"bulbs_and_planes": bulbs_and_planes, "fisheye": fisheye, "panorama": panorama, "empty": empty, "plane_only": plane_only,
-       "single_sphere": single_sphere, "single_triangle": single_triangle, "zero_bounces": zero_bounces,
+       "single_sphere": single_sphere, "no_light": no_light, "single_triangle": single_triangle, "zero_bounces": zero_bounces,
        "glass_gi_dof": one_bounce_glass_gi, "glass_spheres_bulb": glass_spheres_bulb, "axis_parallel_rays": axis_parallel_rays, "deep_stack": deep_stack}

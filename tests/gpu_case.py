@@ -76,7 +76,7 @@ def run_case(text, w, h, spp, oracle_skip_unlit=True, **options):
     tree = raw.tree() if stl.num_prims > 0 else None
     raw.close()
     o = ol.OracleScene(pyscene.parse_lines(text.split("\n")), bounds_mode=0)
-    known = {k: v for k, v in options.items() if k in ("traversal", "qnodes")}
+    known = {k: v for k, v in options.items() if k in ("traversal", "qnodes", "wavefront")}
     ref = o.render(w, h, spp, flags=mirror_flags(stl, o, oracle_skip_unlit, **known), nthreads=8)
     if tree is not None:
         on = o.nodes()

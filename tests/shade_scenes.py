@@ -1,5 +1,5 @@
 """The shading-branch scene matrix (test data, generated not stored): small scenes, each aimed at named branches of the shading
-state machine (shade_common.h advance_core / batch_next / unlit_mask, their second copy in wavefront.hip, the host switches of
+state machine (shade_common.h advance_core / batch_next / unlit_mask, wavefront.hip's own emission of a node's batch, the host switches of
 plan_call, render_plan.h) that the bundled scenes, edge_scenes.py and the fuzzer do not reach.
 
 Every entry of ALL is a Case: the scene text, the frame size, the oracle branch counters (oracle_lib.BRANCH_FIELDS) the scene was

@@ -20,7 +20,7 @@ import os
 
 from .binding import (LIB_PATH, EXPORTS, MIRT_ERR_ARG, MIRT_RENDER_COUNTERS, MIRT_HIT_NONE, MIRT_HIT_SPHERE, MIRT_HIT_TRIANGLE,      # noqa: F401
                       MIRT_HIT_PLANE, MIRT_QUERY_ANY_HIT, MIRT_DENOISE_SIGMA_C, MIRT_DENOISE_SIGMA_N, MIRT_DENOISE_SIGMA_P, MirtError, Vec3, Ray,
-                      Hit, Camera, Shading, SceneDesc, RenderParams, Stats, MultiStats, TreeNode, lib, _check)
+                      Hit, Camera, Shading, SceneDesc, RenderParams, Stats, MultiStats, TreeNode, RecordInfo, lib, _check)
 
 # The dtypes a tensor argument may have, by name: torch is imported when a call needs it (uint32 only where torch has it)
 _F32, _U8, _INT, _HIT = ("float32",), ("uint8",), ("int32", "uint32"), ("float32", "int32", "uint32")
@@ -231,6 +231,24 @@ class RawConfig(_Handle):
         _check(lib().mirt_get_tree(self._h, nodes.ctypes.data if n else None, codes.ctypes.data if n else None,
                                    refs.ctypes.data if n else None, bounds.ctypes.data))
         return nodes, codes, refs, bounds
+
+    def records(self):
+        """mirt_get_records: what the traversal kernels read, as a dict -- "info" (a RecordInfo), "nodes" float32 [N-1, 16],
+        "qnodes" uint32 [N-1, 8] or [0, 8], "wnodes" uint32 [N-1, 16] or [0, 16], "prims" float32 [units, 4], "unit_prim",
+        "tris_before" uint32, "tri_boxes" float32 [Nt, 8], "qparams" float32 [9] or [0] -- for parity tests."""
+        import numpy as np
+        n, ns, nt = self.desc.num_prims, self.desc.num_spheres, self.desc.num_triangles
+        m, units = max(n - 1, 0), ns + 3 * nt
+        info = RecordInfo()
+        a = {"nodes": np.zeros((m, 16), np.float32), "qnodes": np.zeros((m, 8), np.uint32), "wnodes": np.zeros((m, 16), np.uint32),
+             "prims": np.zeros((units, 4), np.float32), "unit_prim": np.zeros(units, np.uint32), "tris_before": np.zeros(n + 1, np.uint32),
+             "tri_boxes": np.zeros((nt, 8), np.float32), "qparams": np.zeros(9, np.float32)}
+        _check(lib().mirt_get_records(self._h, C.byref(info), *(_host_ptr(v) for v in a.values())))
+        counts = {"nodes": info.num_nodes, "qnodes": info.num_qnodes, "wnodes": info.num_wnodes, "prims": info.prim_units,
+                  "unit_prim": info.prim_units, "tris_before": info.num_tris_before, "tri_boxes": info.num_tri_boxes, "qparams": info.num_qparams}
+        out = {k: v[:counts[k]] for k, v in a.items()}
+        out["info"] = info
+        return out
 
 
 def _light_ptrs(desc, suns, bulbs):
@@ -949,4 +967,16 @@ def probe_xorwow(spp, num_streams, draws, device=0):
     import numpy as np
     out = np.zeros((num_streams, draws), dtype=np.uint32)
     _check(lib().mirt_probe_xorwow(device, spp, num_streams, draws, out.ctypes.data))
+    return out
+
+
+def probe_qbox(cases, device=0):
+    """mirt_probe_qbox: `cases` is a numpy layouts.QBOX_CASE array [n]; returns a layouts.QBOX_RESULT array [n]."""
+    import numpy as np
+    from . import layouts
+    a = _records(cases, "cases", layouts.QBOX_CASE, None)
+    if a is None or a.size == 0:
+        raise ValueError("cases must hold at least one case")
+    out = np.zeros(a.shape[0], dtype=layouts.QBOX_RESULT)
+    _check(lib().mirt_probe_qbox(device, a.shape[0], a.ctypes.data, out.ctypes.data))
     return out

@@ -100,9 +100,17 @@ class TreeNode(C.Structure):
                 ("left", C.c_uint32), ("right", C.c_uint32), ("prim_offset", C.c_uint32), ("count", C.c_uint32)]
 
 
+class RecordInfo(C.Structure):
+    """MirtRecordInfo: the element counts of mirt_get_records' regions, and what decodes a child reference."""
+    _fields_ = [(n, C.c_uint32) for n in ("num_nodes", "num_qnodes", "num_wnodes", "prim_units", "num_tris_before", "num_tri_boxes", "num_qparams",
+                                          "prim_base16", "qnode_base16", "wnode_base16", "root_ref", "root_ref_q", "root_ref_w")] + \
+               [("grid_ok", C.c_int32), ("tree_depth", C.c_int32), ("coord_max", C.c_float)]
+
+
 # The header's struct behind each class, for the test that compares them field by field
 STRUCTS = {"MirtVec3": Vec3, "MirtRay": Ray, "MirtHit": Hit, "MirtCamera": Camera, "MirtShading": Shading, "MirtSceneDesc": SceneDesc,
-           "MirtRenderParams": RenderParams, "MirtStats": Stats, "MirtMultiStats": MultiStats, "MirtTreeNode": TreeNode}
+           "MirtRenderParams": RenderParams, "MirtStats": Stats, "MirtMultiStats": MultiStats, "MirtTreeNode": TreeNode,
+           "MirtRecordInfo": RecordInfo}
 
 _int, _i64, _u32, _u64, _f, _str, _vp = C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_char_p, C.c_void_p
 _out = C.POINTER
@@ -172,8 +180,10 @@ SIGNATURES = {
     "mirt_multi_get_stats": (_int, [_vp, _int, _out(Stats)]),
     "mirt_get_stats": (_int, [_vp, _out(Stats)]),
     "mirt_get_tree": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    "mirt_get_records": (_int, [_vp, _out(RecordInfo)] + [_vp] * 8),
     "mirt_probe_math": (_int, [_int, _int, _int, _vp, _vp]),
     "mirt_probe_xorwow": (_int, [_int, _int, _int, _int, _vp]),
+    "mirt_probe_qbox": (_int, [_int, _int, _vp, _vp]),
     "mirt_write_png": (_int, [_str, _vp, _int, _int]),
 }
 EXPORTS = list(SIGNATURES)

@@ -567,6 +567,13 @@ int mirt_get_tree(MirtScene* sc, MirtTreeNode* nodes, uint32_t* codes, MirtPrimR
   return get_tree(sc, nodes, codes, refs, bounds);
 }
 
+int mirt_get_records(MirtScene* sc, MirtRecordInfo* info, void* nodes, void* qnodes, void* wnodes, void* prims, uint32_t* unit_prim,
+                     uint32_t* tris_before, float* tri_boxes, float* qparams)
+{
+  MIRT_TRY(enter_scene(sc, "mirt_get_records"));
+  return get_records(sc, info, nodes, qnodes, wnodes, prims, unit_prim, tris_before, tri_boxes, qparams);
+}
+
 int mirt_probe_math(int device, int which, int n, const float* host_in, float* host_out)
 {
   if (n <= 0 || !host_in || !host_out) { set_error("mirt_probe_math: bad argument"); return MIRT_ERR_ARG; }
@@ -577,6 +584,12 @@ int mirt_probe_xorwow(int device, int spp, int num_streams, int draws, uint32_t*
 {
   if (num_streams <= 0 || draws <= 0 || !host_out) { set_error("mirt_probe_xorwow: bad argument"); return MIRT_ERR_ARG; }
   return probe_xorwow(device, spp, num_streams, draws, host_out);
+}
+
+int mirt_probe_qbox(int device, int n, const float* host_in, uint32_t* host_out)
+{
+  if (n <= 0 || !host_in || !host_out) { set_error("mirt_probe_qbox: bad argument"); return MIRT_ERR_ARG; }
+  return probe_qbox(device, n, host_in, host_out);
 }
 
 } // extern "C"

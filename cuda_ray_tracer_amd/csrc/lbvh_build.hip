@@ -384,9 +384,7 @@ MIRT_DEV uint32_t make_ref(uint32_t node, uint32_t leaf_base, const uint32_t* __
   return 4u * node;
 }
 
-// Quantised node records (scene_dev.h): child boxes on the scene-bounds grid, rounded outwards.
-MIRT_DEV uint32_t qlo(float x, float smin, float step) { const float q = floorf((x - smin) / step) - 1.0f; return (uint32_t)fminf(fmaxf(q, 0.0f), QGRID); }
-MIRT_DEV uint32_t qhi(float x, float smin, float step) { const float q = ceilf((x - smin) / step) + 1.0f; return (uint32_t)fminf(fmaxf(q, 0.0f), QGRID); }
+// Quantised node records (scene_dev.h): child boxes on the scene-bounds grid, rounded outwards (qlo, qhi).
 __global__ void __launch_bounds__(BLOCK) pack_qnodes_kernel(int n, const uint32_t* __restrict__ bkeys, const uint32_t* __restrict__ child_l,
                                                             const uint32_t* __restrict__ child_r, const float* __restrict__ boxes,
                                                             const uint32_t* __restrict__ order, const MirtPrimRef* __restrict__ refs,
@@ -723,6 +721,39 @@ int get_tree(MirtScene* sc, MirtTreeNode* nodes, uint32_t* codes, MirtPrimRef* r
       memcpy(&bounds[i], &u, 4);
     }
   }
+  return MIRT_OK;
+}
+
+// mirt_get_records: the heap and its side tables as the traversal kernels read them.  A region the build did not make (or, after
+// a rebuild with bounds_as_shipped, no longer offers) has count 0 and is not copied.
+int get_records(MirtScene* sc, MirtRecordInfo* info, void* nodes, void* qnodes, void* wnodes, void* prims, uint32_t* unit_prim,
+                uint32_t* tris_before, float* tri_boxes, float* qparams)
+{
+  const int n = sc->N;
+  if (!sc->built) { set_error("mirt_get_records: LBVH not built"); return MIRT_ERR_STATE; }
+  MIRT_HIP(hipDeviceSynchronize());
+  const bool have_q = sc->root_ref_q != REF_NONE, have_w = sc->root_ref_w != REF_NONE;
+  MirtRecordInfo r{};
+  r.num_nodes = n > 1 ? (uint32_t)(n - 1) : 0u;
+  r.num_qnodes = have_q ? r.num_nodes : 0u;
+  r.num_wnodes = have_w ? r.num_nodes : 0u;
+  r.prim_units = n > 0 ? (uint32_t)sc->Ns + 3u * (uint32_t)sc->Nt : 0u;
+  r.num_tris_before = n > 0 ? (uint32_t)n + 1u : 0u;
+  r.num_tri_boxes = n > 0 ? (uint32_t)sc->Nt : 0u;
+  r.num_qparams = (have_q || have_w) ? 9u : 0u;
+  r.prim_base16 = sc->prim_base / 16u; r.qnode_base16 = sc->qnode_base / 16u; r.wnode_base16 = sc->wnode_base / 16u;
+  r.root_ref = sc->root_ref; r.root_ref_q = sc->root_ref_q; r.root_ref_w = sc->root_ref_w;
+  r.grid_ok = sc->grid_ok ? 1 : 0; r.tree_depth = sc->tree_depth; r.coord_max = sc->coord_max;
+  if (info) *info = r;
+  const unsigned char* heap = sc->heap;
+  if (nodes && r.num_nodes) MIRT_HIP(hipMemcpy(nodes, heap, 64 * (size_t)r.num_nodes, hipMemcpyDeviceToHost));
+  if (qnodes && r.num_qnodes) MIRT_HIP(hipMemcpy(qnodes, heap + sc->qnode_base, 32 * (size_t)r.num_qnodes, hipMemcpyDeviceToHost));
+  if (wnodes && r.num_wnodes) MIRT_HIP(hipMemcpy(wnodes, heap + sc->wnode_base, 64 * (size_t)r.num_wnodes, hipMemcpyDeviceToHost));
+  if (prims && r.prim_units) MIRT_HIP(hipMemcpy(prims, heap + sc->prim_base, 16 * (size_t)r.prim_units, hipMemcpyDeviceToHost));
+  if (unit_prim && r.prim_units) MIRT_HIP(hipMemcpy(unit_prim, sc->unit_prim, 4 * (size_t)r.prim_units, hipMemcpyDeviceToHost));
+  if (tris_before && r.num_tris_before) MIRT_HIP(hipMemcpy(tris_before, sc->tris_before, 4 * (size_t)r.num_tris_before, hipMemcpyDeviceToHost));
+  if (tri_boxes && r.num_tri_boxes) MIRT_HIP(hipMemcpy(tri_boxes, sc->tri_boxes, 32 * (size_t)r.num_tri_boxes, hipMemcpyDeviceToHost));
+  if (qparams && r.num_qparams) MIRT_HIP(hipMemcpy(qparams, sc->qparams, 4 * (size_t)r.num_qparams, hipMemcpyDeviceToHost));
   return MIRT_OK;
 }
 

@@ -570,6 +570,51 @@ __global__ void probe_math_kernel(int which, int n, const float* __restrict__ in
   out[i] = y;
 }
 
+// mirt_probe_qbox (mirt.h): one case per thread through the builder's qlo / qhi and the walk's quantised_axis, box_pair,
+// box_pair_q (the packed box as the left child, then as the right one) and box_q.  The grid's step and 2^60 / step are computed as
+// pack_qnodes_kernel computes them (lbvh_build.hip), 1 / d and the three axes as start_ray<QN> does (shade_common.h).
+__global__ void probe_qbox_kernel(int n, const float* __restrict__ in, uint32_t* __restrict__ out)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* c = in + 20 * (size_t)i;
+  const float tmin = 0.0001f;
+  float smin[3], step[3], lim[3];
+  uint32_t lo[3], hi[3], w[3];
+  for (int k = 0; k < 3; ++k) {
+    smin[k] = c[k];
+    const float range = c[3 + k] - smin[k];
+    step[k] = range > 0.0f ? range / QGRID : 1.0f;
+    lim[k] = QINV_STEPS / step[k];
+    lo[k] = qlo(c[6 + k], smin[k], step[k]);
+    hi[k] = qhi(c[9 + k], smin[k], step[k]);
+    w[k] = lo[k] | (hi[k] << 16);
+  }
+  const f3 o = mk3(c[12], c[13], c[14]), d = mk3(c[15], c[16], c[17]);
+  const float tbest = c[18];
+  const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+  f3 A, Cn, Cf;
+  uint32_t sx, sy, sz;
+  quantised_axis(smin[0], step[0], lim[0], o.x, inv.x, A.x, Cn.x, Cf.x, sx);
+  quantised_axis(smin[1], step[1], lim[1], o.y, inv.y, A.y, Cn.y, Cf.y, sy);
+  quantised_axis(smin[2], step[2], lim[2], o.z, inv.z, A.z, Cn.z, Cf.z, sz);
+  // the other child of the pair: some other box (every coordinate differs from the tested one's)
+  const uint32_t v[3] = {w[0] ^ 0x5a5aa5a5u, w[1] ^ 0x0ff0f00fu, w[2] ^ 0xa5a55a5au};
+  bool hit[4], other;
+  float te[3], te_other;
+  // the exact box as the left child of a 64-byte record (the right child: the same box)
+  const float4 q0 = make_float4(c[6], c[9], c[7], c[10]), q1 = make_float4(c[8], c[11], c[6], c[9]), q2 = make_float4(c[7], c[10], c[8], c[11]);
+  box_pair(q0, q1, q2, o.x, o.y, o.z, inv.x, inv.y, inv.z, tbest, tmin, hit[0], other, te[0], te_other);
+  box_pair_q(make_uint4(w[0], w[1], w[2], v[0]), v[1], v[2], A, Cn, Cf, sx, sy, sz, tbest, tmin, hit[1], other, te[1], te_other);
+  box_pair_q(make_uint4(v[0], v[1], v[2], w[0]), w[1], w[2], A, Cn, Cf, sx, sy, sz, tbest, tmin, other, hit[2], te_other, te[2]);
+  hit[3] = box_q(w[0], w[1], w[2], A, Cn, Cf, sx, sy, sz, tbest, tmin);
+  uint32_t* r = out + 20 * (size_t)i;
+  for (int k = 0; k < 3; ++k) { r[k] = lo[k]; r[3 + k] = hi[k]; r[14 + k] = __float_as_uint(step[k]); r[17 + k] = __float_as_uint(lim[k]); }
+  for (int k = 0; k < 4; ++k) r[6 + k] = hit[k] ? 1u : 0u;
+  for (int k = 0; k < 3; ++k) r[10 + k] = __float_as_uint(te[k]);
+  r[13] = 0u;
+}
+
 // out[i*draws + k]: k-th raw 32-bit draw of stream i.  mode 0: curand_init(1234 + i/spp.., ...) is exercised through
 // xw_init exactly as the trace kernel does: pixel = i / spp, sample = i % spp (spp > 1) or pixel = i (spp <= 1).
 __global__ void probe_xorwow_kernel(RngTablesDev t, int spp, int nstreams, int draws, uint32_t* __restrict__ out)
@@ -1165,6 +1210,19 @@ int probe_math(int device, int which, int n, const float* in, float* out)
   hipLaunchKernelGGL(probe_math_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, which, n, di, dout);
   MIRT_HIP(hipGetLastError());
   MIRT_HIP(hipMemcpy(out, dout, 4 * (size_t)n, hipMemcpyDeviceToHost));
+  return MIRT_OK;
+}
+
+int probe_qbox(int device, int n, const float* in, uint32_t* out)
+{
+  MIRT_HIP(hipSetDevice(device));
+  DevBuf<float> di;
+  DevBuf<uint32_t> dout;
+  MIRT_TRY(di.alloc(20 * (size_t)n, "di")); MIRT_TRY(dout.alloc(20 * (size_t)n, "dout"));
+  MIRT_HIP(hipMemcpy(di, in, 4 * 20 * (size_t)n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(probe_qbox_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, di, dout);
+  MIRT_HIP(hipGetLastError());
+  MIRT_HIP(hipMemcpy(out, dout, 4 * 20 * (size_t)n, hipMemcpyDeviceToHost));
   return MIRT_OK;
 }
 

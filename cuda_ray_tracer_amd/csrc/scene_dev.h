@@ -36,6 +36,9 @@ constexpr uint32_t REF_NONE = 0xf0000000u;   // no record (bits 29..28 are set i
 //   (bit 29 of word 6, REF_QPURE: both subtrees of this node hold spheres only -- NODE_SWAP_PURE of the 64-byte record)
 // Node i sits at heap offset qnode_base + 32 i: its reference is qnode_base / 16 + 2 i.
 constexpr float QGRID = 65535.0f;
+// a box plane on the scene-bounds grid, rounded outwards (the builder's pack kernels, lbvh_build.hip; mirt_probe_qbox, render.hip)
+MIRT_DEV uint32_t qlo(float x, float smin, float step) { const float q = floorf((x - smin) / step) - 1.0f; return (uint32_t)fminf(fmaxf(q, 0.0f), QGRID); }
+MIRT_DEV uint32_t qhi(float x, float smin, float step) { const float q = ceilf((x - smin) / step) + 1.0f; return (uint32_t)fminf(fmaxf(q, 0.0f), QGRID); }
 constexpr uint32_t REF_QPURE = 0x20000000u;
 // Wide quantised records (scenes with triangles, option "wide"): one 64-byte record per internal node P holding the boxes of P's
 // GRANDchildren (a child of P that is a leaf stands for itself) in the reference's visiting order -- up to four boxes of
@@ -297,6 +300,8 @@ int build_lbvh(MirtScene* sc, hipStream_t stream);
 size_t sort_low_byte_ws_words(long long n);
 int sort_low_byte(const uint32_t* keys_in, uint32_t* keys_out, uint32_t* vals_out, long long n, uint32_t* ws, hipStream_t stream);
 int get_tree(MirtScene* sc, MirtTreeNode* nodes, uint32_t* codes, MirtPrimRef* refs, float* bounds);
+int get_records(MirtScene* sc, MirtRecordInfo* info, void* nodes, void* qnodes, void* wnodes, void* prims, uint32_t* unit_prim,
+                uint32_t* tris_before, float* tri_boxes, float* qparams);
 // render.hip
 int render(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, void* d_rgba_f32, hipStream_t stream);
 int scatter_part(const MirtRenderParams* p, const void* d_part, void* d_frame, hipStream_t stream);
@@ -306,6 +311,7 @@ int trace_ms_of(RenderCtx& cx, float* ms);
 int fold_trace_time(MirtScene* sc, RenderCtx& cx);
 int probe_math(int device, int which, int n, const float* in, float* out);
 int probe_xorwow(int device, int spp, int nstreams, int draws, uint32_t* out);
+int probe_qbox(int device, int n, const float* in, uint32_t* out);
 int ensure_rng_tables(RngCache* rc, int sample_tables, long long frame_pixels, hipStream_t stream, RngTablesDev* out, bool allow_larger);
 int render_accumulate(MirtScene* sc, const MirtRenderParams* p, void* d_accum, int sample_first, int sample_count, hipStream_t stream);
 void rng_cache_free(RngCache* rc);

@@ -365,7 +365,7 @@ int mirt_scene_set_camera(MirtScene* sc, const MirtCamera* cam);
  * Primitive counts and the order of the primitives do not change; materials, planes and lights are not touched (they have
  * update calls of their own, below, which need no build).
  * State: an update marks the scene NOT BUILT: until the next mirt_build_lbvh (issued on the same stream, or after the caller
- * has ordered it behind the update), mirt_render*, mirt_trace_rays, mirt_camera_rays and mirt_get_tree return MIRT_ERR_STATE.
+ * has ordered it behind the update), mirt_render*, mirt_trace_rays, mirt_camera_rays, mirt_get_tree and mirt_get_records return MIRT_ERR_STATE.
  * Several updates may precede one build.  The build is the full one: the result is exactly the scene that mirt_scene_create +
  * mirt_build_lbvh give for the same values (the reference builds its tree from scratch; a refitted tree would be another tree).
  * count 0: MIRT_OK, nothing launched, the scene stays built.
@@ -598,6 +598,38 @@ typedef struct MirtTreeNode {      /* the reference's LBVHNode (lbvh.cuh:6-28), 
  * bounds: 6 floats (min xyz, max xyz).  Any pointer may be NULL. */
 int mirt_get_tree(MirtScene* sc, MirtTreeNode* nodes, uint32_t* codes, MirtPrimRef* refs, float* bounds);
 
+/* What the traversal kernels read from a built scene, copied back word for word (mirt_get_tree returns what they do NOT read).
+ * The counts say how many elements of each region the scene has -- 0 for a region it was built without -- and the rest is what
+ * decodes a child reference and what the host decided from the tree:
+ *   num_nodes      64-byte exact records: both child boxes as (min, max) pairs per axis (12 floats), the two child references,
+ *                  the descent-order bits, one unused word.  N - 1 of them.
+ *   num_qnodes     32-byte quantised records of a sphere-only scene: words 0..2 child 0 (min | max << 16 per axis, in grid steps
+ *                  from qparams[0..2]), words 3..5 child 1, words 6, 7 the child references.  N - 1, or 0.
+ *   num_wnodes     64-byte wide records of a scene with triangles: up to four grandchild boxes of three such words (words 0..11)
+ *                  and their references (words 12..15).  N - 1, or 0.
+ *   prim_units     16-byte units of the primitive region, in sorted (Morton) order: a sphere is one unit (cx, cy, cz, r), a
+ *                  triangle three (p0.xyz nor.x | nor.yz e1.xy | e1.z e2.xyz); unit_prim has one word per unit
+ *                  (type << 31 | index in the scene's sphere / triangle array).  Ns + 3 Nt.
+ *   num_tris_before  N + 1 (0 for an empty scene): triangles among the sorted leaves [0, j).
+ *   num_tri_boxes  Nt records of 8 floats, scene order: (xmin, xmax, ymin, ymax) (zmin, zmax, 0, 0), a triangle's exact leaf box.
+ *   num_qparams    9 when quantised or wide records were built (grid origin xyz, grid step xyz, 2^60 / grid step xyz), else 0.
+ * A reference is bit 31 leaf | bit 30 triangle | bits 0..27 the record's offset in 16-byte units from the start of the exact
+ * records: node i of the exact records is 4 i, of the quantised ones qnode_base16 + 2 i, of the wide ones wnode_base16 + 4 i, the
+ * primitive of sorted leaf j prim_base16 + j + 2 tris_before[j].  0xf0000000 is "no record": root_ref_q / root_ref_w of a scene
+ * without those records. */
+typedef struct MirtRecordInfo {
+  uint32_t num_nodes, num_qnodes, num_wnodes, prim_units, num_tris_before, num_tri_boxes, num_qparams;
+  uint32_t prim_base16, qnode_base16, wnode_base16;
+  uint32_t root_ref, root_ref_q, root_ref_w;
+  int32_t grid_ok;       /* the grid resolves the scene's coordinates: the quantised / wide records may be walked */
+  int32_t tree_depth;    /* the most internal nodes on a root-to-leaf path */
+  float coord_max;       /* largest |coordinate| of the root's two child boxes */
+} MirtRecordInfo;
+/* Host-synchronous, like mirt_get_tree, and with its errors.  Every output pointer is a host array sized for the counts above
+ * (which follow from the scene's N, Ns and Nt: size for N - 1 records of each kind); any of them may be NULL. */
+int mirt_get_records(MirtScene* sc, MirtRecordInfo* info, void* nodes, void* qnodes, void* wnodes, void* prims, uint32_t* unit_prim,
+                     uint32_t* tris_before, float* tri_boxes, float* qparams);
+
 /* Device-side probes of the arithmetic the kernels use (which: 0 logf 1 expf 2 sinf 3 cosf 4 pow(x,1/2.4)
  * 5 RGBtosRGB 6 sqrtf 7 1/x), and of the XORWOW generator. */
 int mirt_probe_math(int device, int which, int n, const float* host_in, float* host_out);
@@ -605,6 +637,16 @@ int mirt_probe_math(int device, int which, int n, const float* host_in, float* h
  * (curand_init(1234 + pixel, sample, 0), draw.cu:162); spp <= 1: pixel i (curand_init(1234, pixel, 0), draw.cu:105).
  * host_out[i * draws + k] is the k-th raw 32-bit output. */
 int mirt_probe_xorwow(int device, int spp, int num_streams, int draws, uint32_t* host_out);
+/* The box test of the quantised walk, one device thread per case, through the functions the builder and the trace kernels call
+ * (not a restatement of them).  host_in, 20 floats per case: scene bounds smin[3], smax[3]; a box lo[3], hi[3]; a ray origin o[3]
+ * and direction d[3] (taken as given, not normalised); tbest; one unused float.  The thread computes the grid step and
+ * 2^60 / step of the bounds and the box's six grid coordinates as the builder does, 1 / d and the ray's three grid axes as the start of a
+ * ray does, and then tests the box with tmin = 1e-4 in four forms: the exact box in a 64-byte record, the packed box as the left
+ * child of a 32-byte record, as its right child (the other child being some other box), and as one box of a wide record.
+ * host_out, 20 words per case: [0..2] the grid coordinates of lo, [3..5] of hi (a record packs them min | max << 16 per axis); [6..9] 1 where the form reports
+ * a hit, in the order above; [10..12] the entry parameter of the first three forms (float bits; the wide form returns none);
+ * [13] zero; [14..16] the grid step, [17..19] 2^60 / step (float bits). */
+int mirt_probe_qbox(int device, int n, const float* host_in, uint32_t* host_out);
 
 /* ---- output ----------------------------------------------------------------------------------- */
 /* Image::save, libpng.cpp:73-107: 8-bit RGBA, non-interlaced PNG (own encoder; zlib only). */

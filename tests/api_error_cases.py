@@ -264,6 +264,11 @@ def cases():
     for tag, abcd in (("three", [0, 1, 0]), ("five", [0, 1, 0, 1, 2]), ("2x2", [[0, 1], [0, 1]]), ("scalar", 1.0), ("1x4", [[0, 1, 0, 1]])):
         case(f"make_plane:abcd_{tag}", lambda abcd=abcd: m.make_plane(abcd, mat))
 
+    # ---- introspection ------------------------------------------------------------------------------------------------------
+    for tag, x in (("none", None), ("list", [0.0] * 20), ("dtype_f32", np.zeros((3, 20), np.float32)), ("2d", np.zeros((3, 1), layouts.QBOX_CASE)),
+                   ("strided", np.zeros(6, layouts.QBOX_CASE)[::2]), ("empty", np.zeros(0, layouts.QBOX_CASE))):
+        case(f"probe_qbox:cases:{tag}", lambda x=x: api.probe_qbox(x))
+
     # ---- packing ------------------------------------------------------------------------------------------------------------
     for tag, dirs in (("flat", [0.0, 0.0, -1.0]), ("two_columns", z((4, 2))), ("four_columns", z((4, 4))), ("3d", z((4, 3, 1))), ("scalar", 1.0)):
         case(f"pack_rays:dirs_{tag}", lambda dirs=dirs: m.pack_rays(z((4, 3)), dirs))

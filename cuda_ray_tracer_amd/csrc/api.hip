@@ -376,6 +376,14 @@ int mirt_trace_rays_multi(MirtScene* sc, const void* d_rays, int64_t num_rays, i
   return trace_rays_multi(sc, d_rays, num_rays, k, d_hits, d_counts, flags, (hipStream_t)stream);
 }
 
+// (include_ext/mirt_contacts.h)
+int mirt_closest_points_multi(MirtScene* sc, const void* d_points, int64_t n, int k, void* d_hits, uint32_t* d_counts, void* d_features, uint32_t flags,
+                              void* stream)
+{
+  MIRT_TRY(enter_scene(sc, "mirt_closest_points_multi"));
+  return closest_points_multi(sc, d_points, n, k, d_hits, d_counts, d_features, flags, (hipStream_t)stream);
+}
+
 size_t mirt_denoise_work_bytes(const MirtRenderParams* p) { return denoise_work_bytes(p); }
 
 int mirt_denoise(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, const void* d_features,

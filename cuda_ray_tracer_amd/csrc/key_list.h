@@ -1,0 +1,57 @@
+// A lane's sorted list of its CAP smallest 64-bit keys, in registers (multihit.hip, closest_multi.hip; DESIGN.md sections 6p, 6s).
+// A key holds a non-negative float's bits in its high word, so that one unsigned compare is the whole order.  Every index is a
+// compile-time constant once the loops are unrolled: a runtime index would move the list to scratch.
+#ifndef MIRT_KEY_LIST_H
+#define MIRT_KEY_LIST_H
+
+namespace mirt {
+
+constexpr unsigned long long KEY_NONE = ~0ull;      // above every key: a distance's bits stay below +inf's
+
+template <int CAP>
+struct KeyList {
+  unsigned long long key[CAP > 0 ? CAP : 1];
+  __device__ __forceinline__ void clear()
+  {
+#pragma unroll
+    for (int j = 0; j < CAP; ++j) key[j] = KEY_NONE;
+  }
+  __device__ __forceinline__ void insert(unsigned long long x)
+  {
+    if (CAP == 0 || !(x < key[CAP > 0 ? CAP - 1 : 0])) return;
+#pragma unroll
+    for (int j = 0; j < CAP; ++j) {
+      const bool below = x < key[j];
+      const unsigned long long lo = below ? x : key[j];
+      x = below ? key[j] : x;
+      key[j] = lo;
+    }
+  }
+  // ... with the caller's order: less(a, b) must be a strict total order on the keys that agrees with < wherever it does not look
+  // beyond the keys themselves (KEY_NONE above everything)
+  template <class Less>
+  __device__ __forceinline__ void insert(unsigned long long x, Less less)
+  {
+    if (CAP == 0 || !less(x, key[CAP > 0 ? CAP - 1 : 0])) return;
+#pragma unroll
+    for (int j = 0; j < CAP; ++j) {
+      const bool below = less(x, key[j]);
+      const unsigned long long lo = below ? x : key[j];
+      x = below ? key[j] : x;
+      key[j] = lo;
+    }
+  }
+  // the smallest key; the others move up by one
+  __device__ __forceinline__ unsigned long long pop_front()
+  {
+    const unsigned long long first = key[0];
+#pragma unroll
+    for (int j = 0; j + 1 < CAP; ++j) key[j] = key[j + 1];
+    key[CAP > 0 ? CAP - 1 : 0] = KEY_NONE;
+    return first;
+  }
+};
+
+} // namespace mirt
+
+#endif

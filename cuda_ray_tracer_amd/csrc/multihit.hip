@@ -18,6 +18,7 @@
 #include "host_scene.h"
 #include "shade_common.h"
 #include "query_walk.h"
+#include "key_list.h"
 #include "../../include/mirt_multihit.h"
 
 #include <cmath>
@@ -30,7 +31,6 @@ namespace {
 // count-only instance reaches, like trace_rays_kernel (64 VGPRs).  The list and the records' code need more registers: capacity 1
 // fits the 72 of 7 waves, capacities 4 and 8 the 80 of 6; asked for more waves they spill registers.
 constexpr int multihit_waves(int cap) { return cap == 0 ? 8 : cap == 1 ? 7 : 6; }
-constexpr unsigned long long KEY_NONE = ~0ull;      // above every key: t's bits stay below +inf's
 constexpr uint32_t KEY_PRIM = 0x80000000u;
 
 struct MultiArgs {
@@ -45,37 +45,6 @@ struct MultiArgs {
   uint32_t root_ref;              // the exact records' root (REF_NONE: no primitive)
   uint32_t prim_base16;
   int lds_depth;                  // stack entries kept in LDS (<= QUERY_STACK_LDS)
-};
-
-// the sorted list of a lane's CAP smallest keys; every index is a compile-time constant once the loops are unrolled
-template <int CAP>
-struct KeyList {
-  unsigned long long key[CAP > 0 ? CAP : 1];
-  __device__ __forceinline__ void clear()
-  {
-#pragma unroll
-    for (int j = 0; j < CAP; ++j) key[j] = KEY_NONE;
-  }
-  __device__ __forceinline__ void insert(unsigned long long x)
-  {
-    if (CAP == 0 || !(x < key[CAP > 0 ? CAP - 1 : 0])) return;
-#pragma unroll
-    for (int j = 0; j < CAP; ++j) {
-      const bool below = x < key[j];
-      const unsigned long long lo = below ? x : key[j];
-      x = below ? key[j] : x;
-      key[j] = lo;
-    }
-  }
-  // the smallest key; the others move up by one
-  __device__ __forceinline__ unsigned long long pop_front()
-  {
-    const unsigned long long first = key[0];
-#pragma unroll
-    for (int j = 0; j + 1 < CAP; ++j) key[j] = key[j + 1];
-    key[CAP > 0 ? CAP - 1 : 0] = KEY_NONE;
-    return first;
-  }
 };
 
 template <int CAP>

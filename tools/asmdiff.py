@@ -91,6 +91,9 @@ def main(argv):
     parent = os.path.abspath(argv[1])
     sources = argv[2:] or [s for s in B.LIB_SOURCES if s.endswith(".hip")]
     sources = [os.path.basename(s) for s in sources]
+    for s in [s for s in sources if not os.path.exists(os.path.join(parent, CSRC_REL, s))]:
+        print(f"{s}: only in the new tree")      # (a new source moves no kernel of the parent's)
+        sources.remove(s)
     moved = 0
     with tempfile.TemporaryDirectory() as tp, tempfile.TemporaryDirectory() as tn, concurrent.futures.ThreadPoolExecutor(max_workers=16) as pool:
         jobs = {s: (pool.submit(compile_s, parent, s, os.path.join(tp, s + ".s")), pool.submit(compile_s, os.path.abspath(ROOT), s, os.path.join(tn, s + ".s"))) for s in sources}

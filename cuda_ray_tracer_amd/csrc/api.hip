@@ -13,6 +13,14 @@
 
 using namespace mirt;
 
+int mirt::hip_fail(hipError_t e, const char* what, const char* file, int line)
+{
+  char buf[512];
+  snprintf(buf, sizeof(buf), "HIP error in %s at line %d: %s (%s)", file, line, hipGetErrorString(e), what);
+  set_error(buf);
+  return MIRT_ERR_HIP;
+}
+
 namespace {
 
 template <typename T>

@@ -1,35 +1,57 @@
 // LBVH build on the device: replaces build_lbvh_karas (lbvh_builder.cu:401-521) and
 // build_morton_codes_and_sort_primitives (lbvh_utils.cu:77-129).
 //
-//   prim_bounds_kernel   scene bounds = union of primitive boxes (what parse.cpp:147-155,193-200 computes on the
+// The kernels by step of build_lbvh (the steps: bottom of the file; grids, workspace layout, host decisions: build_plan.h):
+//   scene_bounds         prim_bounds_kernel: union of the primitive boxes (what parse.cpp:147-155,193-200 computes on the
 //                        host and then drops -- reference bug #1; here the bounds are real)
-//   morton_kernel        30-bit codes (lbvh_utils.cu:10-75)
-//   radix_pass_kernel    stable LSD radix sort, 4 passes x 8 bits, wave64 ballot ranking (replaces thrust::sort_by_key)
-//   karras_kernel        Karras 2012 hierarchy with the reference's index tie-break (lbvh_builder.cu:76-322)
-//   tri_scan_*           exclusive scan of the triangle flags in sorted order: where each sorted leaf's record goes in the
-//                        heap, and which subtrees hold spheres only
-//   refit_pack_kernel    bottom-up boxes (lbvh_builder.cu:324-387, with the missing release/acquire added) and
-//                        64-byte two-child node records for the traversal kernel
-//   scatter_prims_kernel primitive records into the heap in sorted order (neighbours in space are neighbours in memory)
+//   sort_by_morton       morton_kernel: 30-bit codes (lbvh_utils.cu:10-75); radix_sort_pass x 4 = radix_pass_kernel<false> (count),
+//                        row_scan_kernel, radix_pass_kernel<true> (scatter): stable LSD radix sort, 8 bits a pass, wave64 ballot
+//                        ranking (replaces thrust::sort_by_key).  sort_low_byte is one such pass, for render.hip
+//   hierarchy_and_depth  karras_kernel: Karras 2012 hierarchy with the reference's index tie-break (lbvh_builder.cu:76-322);
+//                        tree_depth_kernel: the most internal nodes on a root-to-leaf path
+//   place_primitives     tri_scan_kernel<false>, scan_sums_kernel, tri_scan_kernel<true>: exclusive scan of the triangle flags in
+//                        sorted order (where each sorted leaf's record goes in the heap, which subtrees hold spheres only);
+//                        scatter_prims_kernel: the records into the heap in that order (neighbours in space, neighbours in memory)
+//   refit_and_pack       refit_pack_kernel: bottom-up boxes (lbvh_builder.cu:324-387, with the missing release/acquire added)
+//                        and 64-byte two-child node records for the traversal kernel
+//   pack_quantised       pack_qnodes_kernel, pack_wnodes_kernel: the 32-byte and the wide records on the scene-bounds grid
 #include "scene_dev.h"
-#include "host_scene.h"
 
-#include <cstdio>
-#include <cstring>
+#include <algorithm>
+#include <utility>
 
 namespace mirt {
 
-int hip_fail(hipError_t e, const char* what, const char* file, int line)
-{
-  char buf[512];
-  snprintf(buf, sizeof(buf), "HIP error in %s at line %d: %s (%s)", file, line, hipGetErrorString(e), what);
-  set_error(buf);
-  return MIRT_ERR_HIP;
-}
-
 namespace {
 
-constexpr int BLOCK = 256;
+constexpr int BLOCK = BUILD_BLOCK;
+
+// One-dimensional launches of BLOCK threads: `blocks` of them, or as many as `items` need at one item per thread.
+template <class... P, class... A>
+void launch_blocks(void (*kernel)(P...), int blocks, hipStream_t stream, A&&... args)
+{
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BLOCK), 0, stream, static_cast<P>(args)...);
+}
+template <class K, class... A>
+void launch_items(K kernel, long long items, hipStream_t stream, A&&... args) { launch_blocks(kernel, item_blocks(items), stream, args...); }
+
+// exclusive scan of one value per thread over the block; `total` (nullable) receives the sum
+MIRT_DEV uint32_t block_exclusive_scan(uint32_t v, uint32_t* sh /* [BLOCK] */, uint32_t* total)
+{
+  const int tid = threadIdx.x;
+  sh[tid] = v;
+  __syncthreads();
+  for (int o = 1; o < BLOCK; o <<= 1) {
+    const uint32_t x = (tid >= o) ? sh[tid - o] : 0;
+    __syncthreads();
+    sh[tid] += x;
+    __syncthreads();
+  }
+  const uint32_t incl = sh[tid];
+  if (total) *total = sh[BLOCK - 1];
+  __syncthreads();
+  return incl - v;
+}
 
 struct Box { float xmin, xmax, ymin, ymax, zmin, zmax; };
 
@@ -56,10 +78,6 @@ MIRT_DEV Box prim_box(uint32_t type, uint32_t id, const float4* __restrict__ sph
   }
   return b;
 }
-
-// order-preserving float <-> uint map so that atomicMin/atomicMax on uints realise float min/max
-MIRT_DEV uint32_t f2key(float f) { uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-MIRT_DEV float key2f(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 __global__ void __launch_bounds__(BLOCK) prim_bounds_kernel(const MirtPrimRef* __restrict__ refs, const float4* __restrict__ spheres,
                                                             const float4* __restrict__ tri_verts, int n, uint32_t* __restrict__ keys)
@@ -139,10 +157,8 @@ __global__ void __launch_bounds__(BLOCK) morton_kernel(const MirtPrimRef* __rest
   vals[i] = (uint32_t)i;
 }
 
-// ---- stable LSD radix sort -------------------------------------------------------------------------
-constexpr int SORT_ITEMS = 8;
-constexpr int SORT_TILE = BLOCK * SORT_ITEMS;   // 2048 keys per workgroup; each wave owns 512 consecutive keys
-
+// ---- stable LSD radix sort (SORT_TILE keys per workgroup, build_plan.h) ------------------------------
+static_assert(RADIX == BLOCK, "one thread per digit");
 template <bool SCATTER>
 __global__ void __launch_bounds__(BLOCK) radix_pass_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
                                                            uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
@@ -187,17 +203,7 @@ __global__ void __launch_bounds__(BLOCK) radix_pass_kernel(const uint32_t* __res
     return;
   }
   // exclusive scan of the 256 digit totals (every block repeats it: 256 values)
-  const uint32_t mytot = totals[tid];
-  dbase[tid] = mytot;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const uint32_t v = (tid >= o) ? dbase[tid - o] : 0;
-    __syncthreads();
-    dbase[tid] += v;
-    __syncthreads();
-  }
-  const uint32_t off = (dbase[tid] - mytot) + offsets[(size_t)tid * nblocks + blockIdx.x];
-  __syncthreads();
+  const uint32_t off = block_exclusive_scan(totals[tid], dbase, nullptr) + offsets[(size_t)tid * nblocks + blockIdx.x];
   wcnt[0][tid] = off; wcnt[1][tid] = off + c0; wcnt[2][tid] = off + c0 + c1; wcnt[3][tid] = off + c0 + c1 + c2;
   __syncthreads();
 #pragma unroll
@@ -223,17 +229,9 @@ __global__ void __launch_bounds__(BLOCK) row_scan_kernel(uint32_t* __restrict__ 
   const int lo = tid * chunk, hi = min(lo + chunk, nblocks);
   uint32_t s = 0;
   for (int i = lo; i < hi; ++i) s += row[i];
-  sums[tid] = s;
-  __syncthreads();
-  for (int off = 1; off < BLOCK; off <<= 1) {
-    const uint32_t v = (tid >= off) ? sums[tid - off] : 0;
-    __syncthreads();
-    sums[tid] += v;
-    __syncthreads();
-  }
-  uint32_t run = sums[tid] - s;
+  uint32_t run = block_exclusive_scan(s, sums, nullptr);
+  if (tid == BLOCK - 1) totals[blockIdx.x] = run + s;
   for (int i = lo; i < hi; ++i) { const uint32_t v = row[i]; row[i] = run; run += v; }
-  if (tid == BLOCK - 1) totals[blockIdx.x] = sums[tid];
 }
 
 // ---- Karras hierarchy ------------------------------------------------------------------------------
@@ -308,27 +306,7 @@ __global__ void __launch_bounds__(BLOCK) karras_kernel(const uint32_t* __restric
 
 // ---- where the primitive records go: exclusive scan of the triangle flags over the sorted leaves ------------------------
 // Sorted leaf j's record starts at unit j + 2 * tris_before[j] of the primitive region (a sphere is one 16-byte unit, a
-// triangle three), and leaves [f, l] hold spheres only iff tris_before[l + 1] == tris_before[f].
-constexpr int SCAN_ITEMS = 8;
-constexpr int SCAN_TILE = BLOCK * SCAN_ITEMS;
-
-MIRT_DEV uint32_t block_exclusive_scan(uint32_t v, uint32_t* sh /* [BLOCK] */, uint32_t* total)
-{
-  const int tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (int o = 1; o < BLOCK; o <<= 1) {
-    const uint32_t x = (tid >= o) ? sh[tid - o] : 0;
-    __syncthreads();
-    sh[tid] += x;
-    __syncthreads();
-  }
-  const uint32_t incl = sh[tid];
-  if (total) *total = sh[BLOCK - 1];
-  __syncthreads();
-  return incl - v;
-}
-
+// triangle three), and leaves [f, l] hold spheres only iff tris_before[l + 1] == tris_before[f].  SCAN_TILE leaves per workgroup.
 template <bool WRITE>
 __global__ void __launch_bounds__(BLOCK) tri_scan_kernel(int n, const uint32_t* __restrict__ order, const MirtPrimRef* __restrict__ refs,
                                                          uint32_t* __restrict__ block_sums, uint32_t* __restrict__ tris_before)
@@ -384,7 +362,32 @@ MIRT_DEV uint32_t make_ref(uint32_t node, uint32_t leaf_base, const uint32_t* __
   return 4u * node;
 }
 
-// Quantised node records (scene_dev.h): child boxes on the scene-bounds grid, rounded outwards (qlo, qhi).
+// The grid of the quantised records: QGRID steps across the scene bounds on every axis (a flat axis: step 1).
+struct QuantGrid { float smin[3], step[3]; };
+MIRT_DEV QuantGrid quant_grid(const uint32_t* __restrict__ bkeys)
+{
+  QuantGrid g;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    g.smin[k] = key2f(bkeys[k]);
+    const float range = key2f(bkeys[3 + k]) - g.smin[k];
+    g.step[k] = range > 0.0f ? range / QGRID : 1.0f;
+  }
+  return g;
+}
+// what the walk needs of it (RenderArgs::qparams): origin, step, 2^60 / step
+MIRT_DEV void write_qparams(float* __restrict__ qparams, const QuantGrid& g)
+{
+  for (int k = 0; k < 3; ++k) { qparams[k] = g.smin[k]; qparams[3 + k] = g.step[k]; qparams[6 + k] = QINV_STEPS / g.step[k]; }
+}
+// a box (xmin, xmax, ymin, ymax, zmin, zmax) as three words (lo | hi << 16), rounded outwards (qlo, qhi: scene_dev.h)
+MIRT_DEV void pack_box_words(const float* __restrict__ box, const QuantGrid& g, uint32_t* w3)
+{
+#pragma unroll
+  for (int k = 0; k < 3; ++k) w3[k] = qlo(box[2 * k], g.smin[k], g.step[k]) | (qhi(box[2 * k + 1], g.smin[k], g.step[k]) << 16);
+}
+
+// Quantised node records (scene_dev.h): both child boxes on the grid, then the two references.
 __global__ void __launch_bounds__(BLOCK) pack_qnodes_kernel(int n, const uint32_t* __restrict__ bkeys, const uint32_t* __restrict__ child_l,
                                                             const uint32_t* __restrict__ child_r, const float* __restrict__ boxes,
                                                             const uint32_t* __restrict__ order, const MirtPrimRef* __restrict__ refs,
@@ -392,14 +395,8 @@ __global__ void __launch_bounds__(BLOCK) pack_qnodes_kernel(int n, const uint32_
                                                             uint4* __restrict__ qnodes, float* __restrict__ qparams, uint32_t qbase16, uint32_t prim_base16)
 {
   const int p = blockIdx.x * BLOCK + threadIdx.x;
-  float smin[3], step[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    smin[k] = key2f(bkeys[k]);
-    const float range = key2f(bkeys[3 + k]) - smin[k];
-    step[k] = range > 0.0f ? range / QGRID : 1.0f;
-  }
-  if (p == 0) { for (int k = 0; k < 3; ++k) { qparams[k] = smin[k]; qparams[3 + k] = step[k]; qparams[6 + k] = QINV_STEPS / step[k]; } }
+  const QuantGrid g = quant_grid(bkeys);
+  if (p == 0) write_qparams(qparams, g);
   if (p >= n - 1) return;
   const uint32_t leaf_base = (uint32_t)(n - 1);
   const uint32_t c[2] = {child_l[p], child_r[p]};
@@ -407,9 +404,7 @@ __global__ void __launch_bounds__(BLOCK) pack_qnodes_kernel(int n, const uint32_
   bool pure[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    const float* b = boxes + 6 * (size_t)c[s];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) w[3 * s + k] = qlo(b[2 * k], smin[k], step[k]) | (qhi(b[2 * k + 1], smin[k], step[k]) << 16);
+    pack_box_words(boxes + 6 * (size_t)c[s], g, w + 3 * s);
     const uint32_t r = make_ref(c[s], leaf_base, order, refs, tris_before, range, prim_base16, &pure[s]);
     w[6 + s] = c[s] >= leaf_base ? r : (qbase16 + 2u * c[s]);
   }
@@ -427,14 +422,8 @@ __global__ void __launch_bounds__(BLOCK) pack_wnodes_kernel(int n, const uint32_
 {
   const int p = blockIdx.x * BLOCK + threadIdx.x;
   if (p >= n - 1) return;
-  float smin[3], step[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    smin[k] = key2f(bkeys[k]);
-    const float range = key2f(bkeys[3 + k]) - smin[k];
-    step[k] = range > 0.0f ? range / QGRID : 1.0f;
-  }
-  if (p == 0) { for (int k = 0; k < 3; ++k) { qparams[k] = smin[k]; qparams[3 + k] = step[k]; qparams[6 + k] = QINV_STEPS / step[k]; } }
+  const QuantGrid g = quant_grid(bkeys);
+  if (p == 0) write_qparams(qparams, g);
   const uint32_t leaf_base = (uint32_t)(n - 1);
   uint32_t kids[4];
   int nk = 0;
@@ -446,8 +435,7 @@ __global__ void __launch_bounds__(BLOCK) pack_wnodes_kernel(int n, const uint32_
   uint32_t w[16];
   for (int i = 0; i < 4; ++i) {
     if (i < nk) {
-      const float* b = boxes + 6 * (size_t)kids[i];
-      for (int k = 0; k < 3; ++k) w[3 * i + k] = qlo(b[2 * k], smin[k], step[k]) | (qhi(b[2 * k + 1], smin[k], step[k]) << 16);
+      pack_box_words(boxes + 6 * (size_t)kids[i], g, w + 3 * i);
       bool pure;
       const uint32_t r = make_ref(kids[i], leaf_base, order, refs, tris_before, range, prim_base16, &pure);
       w[12 + i] = kids[i] >= leaf_base ? r : (wbase16 + 4u * kids[i]);
@@ -497,6 +485,24 @@ __global__ void __launch_bounds__(BLOCK) tree_depth_kernel(int n, const int* __r
   if ((threadIdx.x & 63) == 0 && d > 0) atomicMax(depth, d);
 }
 
+// The refit hand-off's box traffic (refit_pack_kernel, below): every word of a box stored write-through -- a relaxed
+// agent-scope atomic store -- and every word loaded past the L1 -- a relaxed agent-scope atomic load.
+MIRT_DEV void store_wt(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+MIRT_DEV float load_bypass(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+MIRT_DEV void store_box_wt(float* p, const Box& b)
+{
+  store_wt(p + 0, b.xmin); store_wt(p + 1, b.xmax); store_wt(p + 2, b.ymin); store_wt(p + 3, b.ymax); store_wt(p + 4, b.zmin); store_wt(p + 5, b.zmax);
+}
+MIRT_DEV Box load_box_bypass(const float* p)
+{
+  return {load_bypass(p + 0), load_bypass(p + 1), load_bypass(p + 2), load_bypass(p + 3), load_bypass(p + 4), load_bypass(p + 5)};
+}
+// AABB(AABB, AABB), interval.cuh:83-88 (the left child's operand first)
+MIRT_DEV Box box_union(const Box& a, const Box& c)
+{
+  return {fminf(a.xmin, c.xmin), fmaxf(a.xmax, c.xmax), fminf(a.ymin, c.ymin), fmaxf(a.ymax, c.ymax), fminf(a.zmin, c.zmin), fmaxf(a.zmax, c.zmax)};
+}
+
 // set_aabb_kernel_adapted, lbvh_builder.cu:324-387.  One thread per leaf; the second thread to arrive at a parent
 // merges the children.  The box stores are published before the arrival counter is bumped, see below (the reference
 // has no fence there).  The merging thread also writes the parent's packed traversal record.
@@ -521,59 +527,154 @@ __global__ void __launch_bounds__(BLOCK) refit_pack_kernel(int n, const uint32_t
   // (agent-scope atomic) store and drained with s_waitcnt vmcnt(0) before the arrival counter is bumped; the second arriver
   // learns from the value its own add returned that the sibling's box is out, and reads it with L1-bypassing loads.
   // No cache-wide release/acquire fences: they cost microseconds per tree level.
-  float* bp = boxes + 6 * (size_t)cur;
-  __hip_atomic_store(bp + 0, b.xmin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(bp + 1, b.xmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(bp + 2, b.ymin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(bp + 3, b.ymax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(bp + 4, b.zmin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(bp + 5, b.zmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  store_box_wt(boxes + 6 * (size_t)cur, b);
   int p = parent[cur];
   while (p != -1 && p < n - 1) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const uint32_t prev = __hip_atomic_fetch_add(&arrived[p], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (prev == 0) break;
     const uint32_t lc = child_l[p], rc = child_r[p];
-    const float* a = boxes + 6 * (size_t)lc;
-    const float* c = boxes + 6 * (size_t)rc;
-    const float a0 = __hip_atomic_load(a + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), a1 = __hip_atomic_load(a + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const float a2 = __hip_atomic_load(a + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), a3 = __hip_atomic_load(a + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const float a4 = __hip_atomic_load(a + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), a5 = __hip_atomic_load(a + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const float c0 = __hip_atomic_load(c + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c1 = __hip_atomic_load(c + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const float c2 = __hip_atomic_load(c + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c3 = __hip_atomic_load(c + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const float c4 = __hip_atomic_load(c + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c5 = __hip_atomic_load(c + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const Box a = load_box_bypass(boxes + 6 * (size_t)lc), c = load_box_bypass(boxes + 6 * (size_t)rc);
     // traversal record: both child boxes as (min, max) pairs per axis (the slab test works on pairs) + child references
     float4* rec = nodes + 4 * (size_t)p;
-    rec[0] = make_float4(a0, a1, a2, a3);
-    rec[1] = make_float4(a4, a5, c0, c1);
-    rec[2] = make_float4(c2, c3, c4, c5);
+    rec[0] = make_float4(a.xmin, a.xmax, a.ymin, a.ymax);
+    rec[1] = make_float4(a.zmin, a.zmax, c.xmin, c.xmax);
+    rec[2] = make_float4(c.ymin, c.ymax, c.zmin, c.zmax);
     bool pure_l, pure_r;
     const uint32_t ref_l = make_ref(lc, leaf_base, order, refs, tris_before, range, prim_base16, &pure_l);
     const uint32_t ref_r = make_ref(rc, leaf_base, order, refs, tris_before, range, prim_base16, &pure_r);
     rec[3] = make_float4(__uint_as_float(ref_l), __uint_as_float(ref_r),
                          __uint_as_float(NODE_SWAP_ANY | ((pure_l && pure_r) ? NODE_SWAP_PURE : 0u)), 0.0f);
-    // AABB(AABB, AABB), interval.cuh:83-88
-    float* pb = boxes + 6 * (size_t)p;
-    __hip_atomic_store(pb + 0, fminf(a0, c0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(pb + 1, fmaxf(a1, c1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(pb + 2, fminf(a2, c2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(pb + 3, fmaxf(a3, c3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(pb + 4, fminf(a4, c4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(pb + 5, fmaxf(a5, c5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    store_box_wt(boxes + 6 * (size_t)p, box_union(a, c));
     cur = (uint32_t)p;
     p = parent[cur];
   }
 }
 
+// One stable pass over the 8 key bits from `shift`: count per tile, scan every digit's row of counts, scatter.  vals_in == null:
+// the values are the positions.  The pass's histogram and totals lie in ws where `at` says (BuildLayout, build_plan.h).
+void radix_sort_pass(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out, uint32_t* ws, const BuildLayout& at,
+                     int n, int shift, hipStream_t stream)
+{
+  const int sblocks = sort_blocks(n);
+  uint32_t *hist = ws + at.hist, *totals = ws + at.totals;
+  launch_blocks(radix_pass_kernel<false>, sblocks, stream, keys_in, vals_in, keys_out, vals_out, hist, hist, totals, n, shift, sblocks);
+  launch_blocks(row_scan_kernel, RADIX, stream, hist, totals, sblocks);
+  launch_blocks(radix_pass_kernel<true>, sblocks, stream, keys_in, vals_in, keys_out, vals_out, hist, hist, totals, n, shift, sblocks);
+}
+
 } // namespace
 
 // One stable radix pass over the low byte of the keys (render.hip orders a frame's samples by cost class with it): keys_out /
-// vals_out receive the keys and -- vals_in == null -- their original positions in ascending key order.  ws: 256 * nblocks + 256 words.
-size_t sort_low_byte_ws_words(long long n) { return 256 * (size_t)((n + SORT_TILE - 1) / SORT_TILE) + 256; }
+// vals_out receive the keys and their original positions in ascending key order.  ws: sort_low_byte_ws_words(n) words.
 int sort_low_byte(const uint32_t* keys_in, uint32_t* keys_out, uint32_t* vals_out, long long n, uint32_t* ws, hipStream_t stream)
 {
-  const int sblocks = (int)((n + SORT_TILE - 1) / SORT_TILE);
-  uint32_t *hist = ws, *totals = ws + 256 * (size_t)sblocks;
-  hipLaunchKernelGGL(radix_pass_kernel<false>, dim3(sblocks), dim3(BLOCK), 0, stream, keys_in, (const uint32_t*)nullptr, keys_out, vals_out, hist, hist, totals, (int)n, 0, sblocks);
-  hipLaunchKernelGGL(row_scan_kernel, dim3(256), dim3(BLOCK), 0, stream, hist, totals, sblocks);
-  hipLaunchKernelGGL(radix_pass_kernel<true>, dim3(sblocks), dim3(BLOCK), 0, stream, keys_in, (const uint32_t*)nullptr, keys_out, vals_out, hist, hist, totals, (int)n, 0, sblocks);
+  radix_sort_pass(keys_in, nullptr, keys_out, vals_out, ws, build_layout(n, true), (int)n, 0, stream);
   MIRT_HIP(hipGetLastError());
   return MIRT_OK;
 }
+
+// ---- the steps of a build of n >= 1 primitives, in stream order ---------------------------------------
+namespace {
+
+struct Build {
+  MirtScene* sc; int n; hipStream_t stream;
+  uint32_t* ws; BuildLayout at;      // sc->build_ws and what lies where in it
+  int scene_bounds() const, sort_by_morton() const, hierarchy_and_depth() const, read_back_scene_facts() const;
+  void place_primitives() const, refit_and_pack() const, pack_quantised() const;
+};
+
+int Build::scene_bounds() const
+{
+  const bool shipped = sc->opt.bounds_as_shipped != 0;
+  MIRT_HIP(hipMemcpyAsync(sc->bounds_keys, shipped ? BOUNDS_KEYS_SHIPPED : BOUNDS_KEYS_EMPTY, sizeof(BOUNDS_KEYS_EMPTY), hipMemcpyHostToDevice, stream));
+  // (a grid-stride kernel: one set of atomics per block, at most 512 of them)
+  if (!shipped) launch_blocks(prim_bounds_kernel, std::min(item_blocks(n), 512), stream, sc->refs_in, sc->spheres, sc->tri_verts, n, sc->bounds_keys);
+  return MIRT_OK;
+}
+
+// Morton codes, then four stable passes: an even number, so codes and order end where they started, in k0 / v0
+int Build::sort_by_morton() const
+{
+  uint32_t *ki = ws + at.k0, *vi = ws + at.v0, *ko = ws + at.k1, *vo = ws + at.v1;
+  launch_items(morton_kernel, n, stream, sc->refs_in, sc->spheres, sc->tri_verts, n, sc->bounds_keys, ki, vi);
+  for (int pass = 0; pass < 4; ++pass) {
+    radix_sort_pass(ki, vi, ko, vo, ws, at, n, 8 * pass, stream);
+    std::swap(ki, ko); std::swap(vi, vo);
+  }
+  MIRT_HIP(hipMemcpyAsync(sc->codes, ki, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, stream));
+  MIRT_HIP(hipMemcpyAsync(sc->order, vi, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, stream));
+  return MIRT_OK;
+}
+
+// the hierarchy, the refit's arrival counters zeroed, and the tree's depth for the render plan (every build: a rebuild changes the topology)
+int Build::hierarchy_and_depth() const
+{
+  if (n == 1) { MIRT_HIP(hipMemsetAsync(sc->parent, 0xff, sizeof(int), stream)); return MIRT_OK; }
+  MIRT_HIP(hipMemsetAsync(ws + at.arrived, 0, sizeof(uint32_t) * (n - 1), stream));
+  MIRT_HIP(hipMemsetAsync(sc->parent, 0xff, sizeof(int) * (2 * (size_t)n - 1), stream));
+  launch_items(karras_kernel, n - 1, stream, sc->codes, n, sc->child_l, sc->child_r, sc->parent, sc->range);
+  MIRT_HIP(hipMemsetAsync(sc->depth_dev, 0, sizeof(uint32_t), stream));
+  launch_items(tree_depth_kernel, n, stream, n, sc->parent, sc->depth_dev);
+  return MIRT_OK;
+}
+
+// heap placement of the sorted leaves (the sort is over: the block sums live in its k1, BuildLayout)
+void Build::place_primitives() const
+{
+  const int sblocks = scan_blocks(n);
+  uint32_t* const block_sums = ws + at.block_sums;
+  launch_blocks(tri_scan_kernel<false>, sblocks, stream, n, sc->order, sc->refs_in, block_sums, sc->tris_before);
+  launch_blocks(scan_sums_kernel, 1, stream, block_sums, sblocks);
+  launch_blocks(tri_scan_kernel<true>, sblocks, stream, n, sc->order, sc->refs_in, block_sums, sc->tris_before);
+  launch_items(scatter_prims_kernel, n, stream, n, sc->order, sc->refs_in, sc->tris_before, sc->spheres, sc->tris,
+               reinterpret_cast<float4*>(sc->heap + sc->prim_base), sc->unit_prim);
+}
+
+void Build::refit_and_pack() const
+{
+  launch_items(refit_pack_kernel, n, stream, n, sc->order, sc->refs_in, sc->spheres, sc->tri_verts, sc->child_l, sc->child_r, sc->parent,
+               ws + at.arrived, sc->boxes, sc->nodes, sc->tris_before, sc->range, sc->prim_base / 16u, sc->tri_boxes);
+}
+
+// the quantised records the scene has room for (none for a single primitive, none on the shipped reference's empty bounds)
+void Build::pack_quantised() const
+{
+  const bool offered = n > 1 && !sc->opt.bounds_as_shipped;
+  sc->root_ref_q = sc->root_ref_w = REF_NONE;
+  if (sc->qnode_base && offered) {
+    launch_items(pack_qnodes_kernel, n - 1, stream, n, sc->bounds_keys, sc->child_l, sc->child_r, sc->boxes, sc->order, sc->refs_in, sc->tris_before,
+                 sc->range, reinterpret_cast<uint4*>(sc->heap + sc->qnode_base), sc->qparams, sc->qnode_base / 16u, sc->prim_base / 16u);
+    sc->root_ref_q = sc->qnode_base / 16u;
+  }
+  if (sc->wnode_base && offered) {
+    launch_items(pack_wnodes_kernel, n - 1, stream, n, sc->bounds_keys, sc->child_l, sc->child_r, sc->boxes, sc->order, sc->refs_in, sc->tris_before,
+                 sc->range, reinterpret_cast<uint4*>(sc->heap + sc->wnode_base), sc->qparams, sc->wnode_base / 16u, sc->prim_base / 16u);
+    sc->root_ref_w = sc->wnode_base / 16u;
+  }
+}
+
+// after the synchronise: the tree's depth, what the root record says about the scene box (scene_box_facts), the root reference
+int Build::read_back_scene_facts() const
+{
+  sc->coord_max = 0.0f;
+  sc->grid_ok = false;
+  sc->tree_depth = 0;      // (a single primitive: no internal node)
+  if (n > 1) {
+    uint32_t depth = 0;
+    MIRT_HIP(hipMemcpy(&depth, sc->depth_dev, sizeof(depth), hipMemcpyDeviceToHost));
+    sc->tree_depth = (int)depth;
+    float rec[12];
+    MIRT_HIP(hipMemcpy(rec, sc->nodes, sizeof(rec), hipMemcpyDeviceToHost));
+    const SceneBoxFacts f = scene_box_facts(rec);
+    sc->coord_max = f.coord_max;
+    sc->grid_ok = f.grid_ok;
+  }
+  sc->root_ref = tree_root_ref(n, sc->Nt != 0, sc->prim_base / 16u);
+  return MIRT_OK;
+}
+
+} // namespace
 
 int build_lbvh(MirtScene* sc, hipStream_t stream)
 {
@@ -584,176 +685,22 @@ int build_lbvh(MirtScene* sc, hipStream_t stream)
   if (n == 0) { sc->built = true; sc->build_ms = 0.0f; sc->tree_depth = 0; return MIRT_OK; }   // main.cu:44: build skipped when there are no primitives
 
   // sort / refit workspace: one allocation, made before the timed region and kept with the scene (a rebuild reuses it)
-  const int sblocks = (n + SORT_TILE - 1) / SORT_TILE;
-  const size_t wwords = 4 * (size_t)n + 256 * (size_t)sblocks + 256 + (size_t)(n > 1 ? n - 1 : 0);
-  if (sc->build_ws.cap() < wwords) MIRT_TRY(sc->build_ws.alloc(wwords, "build_ws"));
+  const BuildLayout at = build_layout(n);
+  if (sc->build_ws.cap() < at.total) MIRT_TRY(sc->build_ws.alloc(at.total, "build_ws"));
+  const Build b{sc, n, stream, sc->build_ws, at};
   MIRT_HIP(hipEventRecord(sc->ev0, stream));
-  // scene bounds
-  const int nblk = (n + BLOCK - 1) / BLOCK;
-  if (!sc->opt.bounds_as_shipped) {
-    static const uint32_t init_keys[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-    MIRT_HIP(hipMemcpyAsync(sc->bounds_keys, init_keys, sizeof(init_keys), hipMemcpyHostToDevice, stream));
-    const int bgrid = nblk < 512 ? nblk : 512;
-    hipLaunchKernelGGL(prim_bounds_kernel, dim3(bgrid), dim3(BLOCK), 0, stream, sc->refs_in, sc->spheres, sc->tri_verts, n, sc->bounds_keys);
-  } else {
-    // the shipped reference never stores the bounds it accumulates (parse.cpp:28): min = +inf, max = -inf, every code 0
-    static const uint32_t shipped_keys[6] = {0xff800000u, 0xff800000u, 0xff800000u, 0x007fffffu, 0x007fffffu, 0x007fffffu};
-    MIRT_HIP(hipMemcpyAsync(sc->bounds_keys, shipped_keys, sizeof(shipped_keys), hipMemcpyHostToDevice, stream));
-  }
-
-  // morton codes + stable sort
-  uint32_t* const ws = sc->build_ws;
-  uint32_t *k0 = ws, *v0 = ws + (size_t)n, *k1 = ws + 2 * (size_t)n, *v1 = ws + 3 * (size_t)n;
-  uint32_t *hist = ws + 4 * (size_t)n, *totals = hist + 256 * (size_t)sblocks;
-  hipLaunchKernelGGL(morton_kernel, dim3(nblk), dim3(BLOCK), 0, stream, sc->refs_in, sc->spheres, sc->tri_verts, n, sc->bounds_keys, k0, v0);
-  uint32_t *ki = k0, *vi = v0, *ko = k1, *vo = v1;
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = pass * 8;
-    hipLaunchKernelGGL(radix_pass_kernel<false>, dim3(sblocks), dim3(BLOCK), 0, stream, ki, vi, ko, vo, hist, hist, totals, n, shift, sblocks);
-    hipLaunchKernelGGL(row_scan_kernel, dim3(256), dim3(BLOCK), 0, stream, hist, totals, sblocks);
-    hipLaunchKernelGGL(radix_pass_kernel<true>, dim3(sblocks), dim3(BLOCK), 0, stream, ki, vi, ko, vo, hist, hist, totals, n, shift, sblocks);
-    uint32_t* t = ki; ki = ko; ko = t; t = vi; vi = vo; vo = t;
-  }
-  // after 4 passes the result is back in k0/v0
-  MIRT_HIP(hipMemcpyAsync(sc->codes, ki, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, stream));
-  MIRT_HIP(hipMemcpyAsync(sc->order, vi, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, stream));
-
-  uint32_t* arrived = totals + 256;
-  if (n > 1) {
-    MIRT_HIP(hipMemsetAsync(arrived, 0, sizeof(uint32_t) * (n - 1), stream));
-    MIRT_HIP(hipMemsetAsync(sc->parent, 0xff, sizeof(int) * (2 * (size_t)n - 1), stream));
-    const int kblk = (n - 1 + BLOCK - 1) / BLOCK;
-    hipLaunchKernelGGL(karras_kernel, dim3(kblk), dim3(BLOCK), 0, stream, sc->codes, n, sc->child_l, sc->child_r, sc->parent, sc->range);
-    // the tree's depth, for the render plan (every build: a rebuild changes the topology)
-    MIRT_HIP(hipMemsetAsync(sc->depth_dev, 0, sizeof(uint32_t), stream));
-    hipLaunchKernelGGL(tree_depth_kernel, dim3(nblk), dim3(BLOCK), 0, stream, n, sc->parent, sc->depth_dev);
-  } else {
-    MIRT_HIP(hipMemsetAsync(sc->parent, 0xff, sizeof(int), stream));
-  }
-  // heap placement of the sorted leaves (the sort workspace is free again: the block sums live in it)
-  const int scan_blocks = (n + SCAN_TILE - 1) / SCAN_TILE;
-  uint32_t* const block_sums = k1;
-  hipLaunchKernelGGL(tri_scan_kernel<false>, dim3(scan_blocks), dim3(BLOCK), 0, stream, n, sc->order, sc->refs_in, block_sums, sc->tris_before);
-  hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(BLOCK), 0, stream, block_sums, scan_blocks);
-  hipLaunchKernelGGL(tri_scan_kernel<true>, dim3(scan_blocks), dim3(BLOCK), 0, stream, n, sc->order, sc->refs_in, block_sums, sc->tris_before);
-  hipLaunchKernelGGL(scatter_prims_kernel, dim3(nblk), dim3(BLOCK), 0, stream, n, sc->order, sc->refs_in, sc->tris_before, sc->spheres, sc->tris,
-                     reinterpret_cast<float4*>(sc->heap + sc->prim_base), sc->unit_prim);
-  hipLaunchKernelGGL(refit_pack_kernel, dim3(nblk), dim3(BLOCK), 0, stream, n, sc->order, sc->refs_in, sc->spheres, sc->tri_verts,
-                     sc->child_l, sc->child_r, sc->parent, arrived, sc->boxes, sc->nodes, sc->tris_before, sc->range, sc->prim_base / 16u, sc->tri_boxes);
-  sc->root_ref_q = REF_NONE;
-  if (sc->qnode_base && n > 1 && !sc->opt.bounds_as_shipped) {
-    const int kblk = (n - 1 + BLOCK - 1) / BLOCK;
-    hipLaunchKernelGGL(pack_qnodes_kernel, dim3(kblk), dim3(BLOCK), 0, stream, n, sc->bounds_keys, sc->child_l, sc->child_r, sc->boxes,
-                       sc->order, sc->refs_in, sc->tris_before, sc->range, reinterpret_cast<uint4*>(sc->heap + sc->qnode_base), sc->qparams, sc->qnode_base / 16u, sc->prim_base / 16u);
-    sc->root_ref_q = sc->qnode_base / 16u;
-  }
-  sc->root_ref_w = REF_NONE;
-  if (sc->wnode_base && n > 1 && !sc->opt.bounds_as_shipped) {
-    const int kblk = (n - 1 + BLOCK - 1) / BLOCK;
-    hipLaunchKernelGGL(pack_wnodes_kernel, dim3(kblk), dim3(BLOCK), 0, stream, n, sc->bounds_keys, sc->child_l, sc->child_r, sc->boxes,
-                       sc->order, sc->refs_in, sc->tris_before, sc->range, reinterpret_cast<uint4*>(sc->heap + sc->wnode_base),
-                       sc->qparams, sc->wnode_base / 16u, sc->prim_base / 16u);
-    sc->root_ref_w = sc->wnode_base / 16u;
-  }
+  MIRT_TRY(b.scene_bounds());
+  MIRT_TRY(b.sort_by_morton());
+  MIRT_TRY(b.hierarchy_and_depth());
+  b.place_primitives();
+  b.refit_and_pack();
+  b.pack_quantised();
   MIRT_HIP(hipGetLastError());
   MIRT_HIP(hipEventRecord(sc->ev1, stream));
   MIRT_HIP(hipStreamSynchronize(stream));   // lbvh_builder.cu:475
   MIRT_HIP(hipEventElapsedTime(&sc->build_ms, sc->ev0, sc->ev1));
-  // the scene box, from the root record's two child boxes: its largest coordinate magnitude (RenderArgs::reach_slack), and whether
-  // the grid of the quantised records resolves the scene's coordinates (grid_ok: on every axis they stay below 64 extents, i.e.
-  // ulp(coordinate) below a quarter of a grid step).  Only then do the outward-rounded quantised boxes cover what float rounding
-  // does to a primitive's own box planes and to a sphere's hit distance against them; a scene that fails
-  // the test -- one that sits far from the world origin compared with its size -- is walked over the exact records.
-  sc->coord_max = 0.0f;
-  sc->grid_ok = false;
-  sc->tree_depth = 0;      // (a single primitive: no internal node)
-  if (n > 1) {
-    uint32_t depth = 0;
-    MIRT_HIP(hipMemcpy(&depth, sc->depth_dev, sizeof(depth), hipMemcpyDeviceToHost));
-    sc->tree_depth = (int)depth;
-    float rec[12];      // left x, y | left z, right x | right y, z  (min, max pairs)
-    MIRT_HIP(hipMemcpy(rec, sc->nodes, sizeof(rec), hipMemcpyDeviceToHost));
-    for (float v : rec) sc->coord_max = fmaxf(sc->coord_max, fabsf(v));
-    sc->grid_ok = true;
-    for (int k = 0; k < 3; ++k) {
-      const float lo = fminf(rec[2 * k], rec[6 + 2 * k]), hi = fmaxf(rec[2 * k + 1], rec[6 + 2 * k + 1]);
-      if (!(fmaxf(fabsf(lo), fabsf(hi)) <= 64.0f * (hi - lo))) sc->grid_ok = false;
-    }
-  }
-  // root: node 0, unless the whole scene is a single primitive
-  sc->root_ref = (n == 1) ? (REF_LEAF | (sc->Nt ? REF_TRI : 0u) | (sc->prim_base / 16u)) : 0u;
+  MIRT_TRY(b.read_back_scene_facts());
   sc->built = true;
-  return MIRT_OK;
-}
-
-int get_tree(MirtScene* sc, MirtTreeNode* nodes, uint32_t* codes, MirtPrimRef* refs, float* bounds)
-{
-  const int n = sc->N;
-  if (!sc->built) { set_error("mirt_get_tree: LBVH not built"); return MIRT_ERR_STATE; }
-  if (n == 0) return MIRT_OK;
-  MIRT_HIP(hipDeviceSynchronize());
-  std::vector<uint32_t> order(n), cl(n > 1 ? n - 1 : 0), cr(n > 1 ? n - 1 : 0);
-  std::vector<MirtPrimRef> rin(n);
-  std::vector<float> boxes(6 * (2 * (size_t)n - 1));
-  MIRT_HIP(hipMemcpy(order.data(), sc->order, 4 * (size_t)n, hipMemcpyDeviceToHost));
-  MIRT_HIP(hipMemcpy(rin.data(), sc->refs_in, sizeof(MirtPrimRef) * (size_t)n, hipMemcpyDeviceToHost));
-  MIRT_HIP(hipMemcpy(boxes.data(), sc->boxes, 4 * boxes.size(), hipMemcpyDeviceToHost));
-  if (n > 1) {
-    MIRT_HIP(hipMemcpy(cl.data(), sc->child_l, 4 * (size_t)(n - 1), hipMemcpyDeviceToHost));
-    MIRT_HIP(hipMemcpy(cr.data(), sc->child_r, 4 * (size_t)(n - 1), hipMemcpyDeviceToHost));
-  }
-  if (codes) MIRT_HIP(hipMemcpy(codes, sc->codes, 4 * (size_t)n, hipMemcpyDeviceToHost));
-  if (refs) for (int i = 0; i < n; ++i) refs[i] = rin[order[i]];
-  if (nodes) {
-    for (int i = 0; i < 2 * n - 1; ++i) {
-      MirtTreeNode& t = nodes[i];
-      const float* b = &boxes[6 * (size_t)i];
-      t.xmin = b[0]; t.xmax = b[1]; t.ymin = b[2]; t.ymax = b[3]; t.zmin = b[4]; t.zmax = b[5];
-      if (i < n - 1) { t.left = cl[i]; t.right = cr[i]; t.prim_offset = 0; t.count = 0; }
-      else { t.left = 0; t.right = 0; t.prim_offset = (uint32_t)(i - (n - 1)); t.count = 1; }
-    }
-  }
-  if (bounds) {
-    uint32_t k[6];
-    MIRT_HIP(hipMemcpy(k, sc->bounds_keys, sizeof(k), hipMemcpyDeviceToHost));
-    for (int i = 0; i < 6; ++i) {
-      uint32_t u = (k[i] & 0x80000000u) ? (k[i] & 0x7fffffffu) : ~k[i];
-      memcpy(&bounds[i], &u, 4);
-    }
-  }
-  return MIRT_OK;
-}
-
-// mirt_get_records: the heap and its side tables as the traversal kernels read them.  A region the build did not make (or, after
-// a rebuild with bounds_as_shipped, no longer offers) has count 0 and is not copied.
-int get_records(MirtScene* sc, MirtRecordInfo* info, void* nodes, void* qnodes, void* wnodes, void* prims, uint32_t* unit_prim,
-                uint32_t* tris_before, float* tri_boxes, float* qparams)
-{
-  const int n = sc->N;
-  if (!sc->built) { set_error("mirt_get_records: LBVH not built"); return MIRT_ERR_STATE; }
-  MIRT_HIP(hipDeviceSynchronize());
-  const bool have_q = sc->root_ref_q != REF_NONE, have_w = sc->root_ref_w != REF_NONE;
-  MirtRecordInfo r{};
-  r.num_nodes = n > 1 ? (uint32_t)(n - 1) : 0u;
-  r.num_qnodes = have_q ? r.num_nodes : 0u;
-  r.num_wnodes = have_w ? r.num_nodes : 0u;
-  r.prim_units = n > 0 ? (uint32_t)sc->Ns + 3u * (uint32_t)sc->Nt : 0u;
-  r.num_tris_before = n > 0 ? (uint32_t)n + 1u : 0u;
-  r.num_tri_boxes = n > 0 ? (uint32_t)sc->Nt : 0u;
-  r.num_qparams = (have_q || have_w) ? 9u : 0u;
-  r.prim_base16 = sc->prim_base / 16u; r.qnode_base16 = sc->qnode_base / 16u; r.wnode_base16 = sc->wnode_base / 16u;
-  r.root_ref = sc->root_ref; r.root_ref_q = sc->root_ref_q; r.root_ref_w = sc->root_ref_w;
-  r.grid_ok = sc->grid_ok ? 1 : 0; r.tree_depth = sc->tree_depth; r.coord_max = sc->coord_max;
-  if (info) *info = r;
-  const unsigned char* heap = sc->heap;
-  if (nodes && r.num_nodes) MIRT_HIP(hipMemcpy(nodes, heap, 64 * (size_t)r.num_nodes, hipMemcpyDeviceToHost));
-  if (qnodes && r.num_qnodes) MIRT_HIP(hipMemcpy(qnodes, heap + sc->qnode_base, 32 * (size_t)r.num_qnodes, hipMemcpyDeviceToHost));
-  if (wnodes && r.num_wnodes) MIRT_HIP(hipMemcpy(wnodes, heap + sc->wnode_base, 64 * (size_t)r.num_wnodes, hipMemcpyDeviceToHost));
-  if (prims && r.prim_units) MIRT_HIP(hipMemcpy(prims, heap + sc->prim_base, 16 * (size_t)r.prim_units, hipMemcpyDeviceToHost));
-  if (unit_prim && r.prim_units) MIRT_HIP(hipMemcpy(unit_prim, sc->unit_prim, 4 * (size_t)r.prim_units, hipMemcpyDeviceToHost));
-  if (tris_before && r.num_tris_before) MIRT_HIP(hipMemcpy(tris_before, sc->tris_before, 4 * (size_t)r.num_tris_before, hipMemcpyDeviceToHost));
-  if (tri_boxes && r.num_tri_boxes) MIRT_HIP(hipMemcpy(tri_boxes, sc->tri_boxes, 32 * (size_t)r.num_tri_boxes, hipMemcpyDeviceToHost));
-  if (qparams && r.num_qparams) MIRT_HIP(hipMemcpy(qparams, sc->qparams, 4 * (size_t)r.num_qparams, hipMemcpyDeviceToHost));
   return MIRT_OK;
 }
 

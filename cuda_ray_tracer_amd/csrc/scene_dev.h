@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/mirt.h"
+#include "build_plan.h"
 #include "dev_mem.h"
 #include "device_common.h"
 #include "query_launch.h"
@@ -15,16 +16,12 @@
 
 namespace mirt {
 
-// child reference inside a packed node / the root reference: names a record of the heap [nodes | primitives]
+// child reference inside a packed node / the root reference (REF_*, build_plan.h): names a record of the heap [nodes | primitives]
 //   bit 31 = leaf (a primitive record); bit 30 = primitive type (0 sphere, 1 triangle);
 //   bits 0..27 = the record's offset in the heap in 16-byte units (node i: 4 i; the primitive of sorted leaf j:
 //   prim_base/16 + j + 2 * (triangles among leaves [0, j))), so that the traversal step gets a record's byte offset with
 //   one shift.  Primitive records are stored in sorted (Morton) order: the offset of a leaf grows with its sorted index,
 //   which is what breaks exact ties in the hit distance the way the reference's left-first walk does.
-constexpr uint32_t REF_LEAF = 0x80000000u;
-constexpr uint32_t REF_TRI = 0x40000000u;
-constexpr uint32_t REF_OFFMASK = 0x0fffffffu;  // the record's offset in the heap, in 16-byte units: `ref << 4` is its byte offset (the shift drops the flags)
-constexpr uint32_t REF_NONE = 0xf0000000u;   // no record (bits 29..28 are set in no real reference; offset bits 0)
 // Quantised node records (option "qnodes"): 32 bytes instead of 64, i.e. two 16-byte requests per node visit instead of four
 // and half the bytes -- the address units bound the trace kernel on the bundled scenes, memory on the 2 M-primitive one.  Both
 // child boxes as 12 x uint16 on the scene-bounds grid (65535 steps per axis, rounded outwards by one more step), then the two
@@ -295,10 +292,8 @@ struct MirtScene {
 };
 
 namespace mirt {
-// (hip_fail, lbvh_build.hip: dev_mem.h declares it)
-// lbvh_build.hip
+// lbvh_build.hip (sort_low_byte_ws_words: build_plan.h)
 int build_lbvh(MirtScene* sc, hipStream_t stream);
-size_t sort_low_byte_ws_words(long long n);
 int sort_low_byte(const uint32_t* keys_in, uint32_t* keys_out, uint32_t* vals_out, long long n, uint32_t* ws, hipStream_t stream);
 int get_tree(MirtScene* sc, MirtTreeNode* nodes, uint32_t* codes, MirtPrimRef* refs, float* bounds);
 int get_records(MirtScene* sc, MirtRecordInfo* info, void* nodes, void* qnodes, void* wnodes, void* prims, uint32_t* unit_prim,

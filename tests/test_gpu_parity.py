@@ -264,6 +264,26 @@ def test_synthetic_scene_build_and_render_match_oracle(ns, nt):
     o.close()
 
 
+@pytest.mark.parametrize("ns,nt", [(1024, 1025)])
+def test_synthetic_scene_tree_matches_oracle_at_the_tile_edge(ns, nt):
+    """The tree alone, no render: 2049 primitives are one full sort / scan tile (2048 items) and a second workgroup with one item."""
+    stl = m.syntheticScene(ns, nt, seed=1234)
+    raw = m.initRawConfigFromStl(stl, 0)
+    m.build_lbvh_karas(raw)
+    o = ol.OracleScene(ol.ArrayScene(stl), bounds_mode=0)
+    nodes, codes, refs, bounds = raw.tree()
+    assert len(codes) == ns + nt and np.array_equal(codes, o.codes())
+    orefs = o.refs()
+    assert np.array_equal(refs["type"], orefs["type"]) and np.array_equal(refs["id"], orefs["id"])
+    on = o.nodes()
+    for f in ("left", "right"):
+        assert np.array_equal(nodes[f], on[f]), f
+    for f in ("xmin", "xmax", "ymin", "ymax", "zmin", "zmax"):
+        assert np.array_equal(nodes[f].view(np.uint32), on[f].view(np.uint32)), f
+    raw.close()
+    o.close()
+
+
 @pytest.mark.parametrize("name,w,h,spp", [("tenthousand", 96, 54, 16), ("redchair", 64, 36, 32), ("spiral", 96, 54, 1), ("tri", 256, 256, 0)])
 def test_wavefront_path_matches_oracle(name, w, h, spp, gpu_scenes, oracle_scenes):
     """The trace/shade kernel pair (option "wavefront") must give the same pixels and the same counters."""

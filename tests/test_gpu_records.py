@@ -46,12 +46,17 @@ TEXTS = {
     "far_from_origin": edge_scenes.far_from_origin(),
 }
 
+# (spheres, triangles): mixed primitives, duplicate Morton codes.  A block is 256 threads and the sort and placement-scan tiles are
+# 2048 items: 257, 2048 and 2049 primitives are the smallest scenes with a second block, a full tile, and a second workgroup whose
+# offsets and carry come from the first while its own tile is partly filled.
+SYNTHETIC = {"synthetic": (1500, 1500), "synthetic_257": (128, 129), "synthetic_2048": (1024, 1024), "synthetic_2049": (1024, 1025)}
+
 
 def load(name):
     if name in ("tri", "redchair", "spiral"):
         return m.parseInput(os.path.join(SCENES, name + ".txt"))
-    if name == "synthetic":
-        return m.syntheticScene(1500, 1500)      # mixed primitives, duplicate Morton codes
+    if name in SYNTHETIC:
+        return m.syntheticScene(*SYNTHETIC[name])
     return m.parseText(TEXTS[name])
 
 
@@ -245,7 +250,7 @@ def check_scene(stl, raw, spheres=None, shipped=False):
     return info
 
 
-@pytest.mark.parametrize("name", ["tri", "redchair", "spiral", "synthetic"] + sorted(TEXTS))
+@pytest.mark.parametrize("name", ["tri", "redchair", "spiral"] + list(SYNTHETIC) + sorted(TEXTS))
 def test_every_record_is_what_the_tree_says(name):
     stl = load(name)
     raw = m.initRawConfigFromStl(stl, 0)
@@ -257,7 +262,7 @@ def test_every_record_is_what_the_tree_says(name):
         info = check_scene(stl, raw)
         if name == "far_from_origin":
             assert info.grid_ok == 0 and info.num_qnodes == stl.num_prims - 1
-        elif stl.num_prims > 1 and name != "synthetic":
+        elif stl.num_prims > 1 and name not in SYNTHETIC:
             assert info.grid_ok == 1
         assert (info.num_qnodes > 0) == (stl.num_triangles == 0 and stl.num_prims > 1)
         assert (info.num_wnodes > 0) == (stl.num_triangles > 0 and stl.num_prims > 1)

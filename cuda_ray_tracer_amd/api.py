@@ -20,7 +20,7 @@ import os
 
 from .binding import (LIB_PATH, EXPORTS, MIRT_ERR_ARG, MIRT_RENDER_COUNTERS, MIRT_HIT_NONE, MIRT_HIT_SPHERE, MIRT_HIT_TRIANGLE,      # noqa: F401
                       MIRT_HIT_PLANE, MIRT_QUERY_ANY_HIT, MIRT_DENOISE_SIGMA_C, MIRT_DENOISE_SIGMA_N, MIRT_DENOISE_SIGMA_P, MirtError, Vec3, Ray,
-                      Hit, Camera, Shading, SceneDesc, RenderParams, Stats, MultiStats, TreeNode, RecordInfo, lib, _check)
+                      Hit, Camera, Shading, SceneDesc, RenderParams, Stats, MultiStats, TreeNode, RecordInfo, SampleOrderInfo, lib, _check)
 
 # The dtypes a tensor argument may have, by name: torch is imported when a call needs it (uint32 only where torch has it)
 _F32, _U8, _INT, _HIT = ("float32",), ("uint8",), ("int32", "uint32"), ("float32", "int32", "uint32")
@@ -249,6 +249,20 @@ class RawConfig(_Handle):
         out = {k: v[:counts[k]] for k, v in a.items()}
         out["info"] = info
         return out
+
+    def sample_order(self):
+        """mirt_get_sample_order: the by-sample hand-out table (sched = 2) as a dict -- "total_samples" and "last_launch_samples",
+        "order" uint32 [total_samples] (every launch's segment a permutation of its own sample indices), "keys" and "sorted_keys"
+        uint32 [last_launch_samples], the cost keys of the last launch measured by sample and in hand-out order -- for parity
+        tests.  Waits for a measurement in flight; MirtError (MIRT_ERR_STATE) when the scene has no table."""
+        import numpy as np
+        info = SampleOrderInfo()
+        _check(lib().mirt_get_sample_order(self._h, C.byref(info), None, None, None))
+        order = np.zeros(info.total_samples, np.uint32)
+        keys, sorted_keys = np.zeros(info.last_launch_samples, np.uint32), np.zeros(info.last_launch_samples, np.uint32)
+        _check(lib().mirt_get_sample_order(self._h, C.byref(info), _host_ptr(order), _host_ptr(keys), _host_ptr(sorted_keys)))
+        return {"total_samples": info.total_samples, "last_launch_samples": info.last_launch_samples, "order": order, "keys": keys,
+                "sorted_keys": sorted_keys}
 
 
 def _light_ptrs(desc, suns, bulbs):
@@ -981,4 +995,37 @@ def probe_qbox(cases, device=0):
         raise ValueError("cases must hold at least one case")
     out = np.zeros(a.shape[0], dtype=layouts.QBOX_RESULT)
     _check(lib().mirt_probe_qbox(device, a.shape[0], a.ctypes.data, out.ctypes.data))
+    return out
+
+
+def _probe_words(a, name):
+    """`a` as the uint32 [n >= 1] array a probe takes."""
+    import numpy as np
+    a = _records(a, name, np.dtype(np.uint32), None)
+    if a is None or a.size == 0:
+        raise ValueError(f"{name} must hold at least one element")
+    return a
+
+
+def probe_sort(mode, keys, device=0):
+    """mirt_probe_sort: the build's four-pass sort (mode 0) or the one-byte pass of the sample hand-out (mode 1) over `keys`
+    (numpy uint32 [n]); returns (keys_out, vals_out), the sorted keys and where each stood."""
+    import numpy as np
+    if mode not in (0, 1):
+        raise ValueError(f"mode is {mode!r}; expected 0 (the build's sort) or 1 (the low-byte pass)")
+    a = _probe_words(keys, "keys")
+    keys_out, vals_out = np.zeros_like(a), np.zeros_like(a)
+    _check(lib().mirt_probe_sort(device, mode, a.shape[0], a.ctypes.data, keys_out.ctypes.data, vals_out.ctypes.data))
+    return keys_out, vals_out
+
+
+def probe_sched(which, x, device=0):
+    """mirt_probe_sched: the cost key of every step count in `x` (which 0), or the chunk order of the chunk costs `x` (which 1);
+    `x` is numpy uint32 [n], and so is the result."""
+    import numpy as np
+    if which not in (0, 1):
+        raise ValueError(f"which is {which!r}; expected 0 (cost keys) or 1 (the chunk order)")
+    a = _probe_words(x, "x")
+    out = np.zeros_like(a)
+    _check(lib().mirt_probe_sched(device, which, a.shape[0], a.ctypes.data, out.ctypes.data))
     return out

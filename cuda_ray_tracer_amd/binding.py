@@ -107,10 +107,15 @@ class RecordInfo(C.Structure):
                [("grid_ok", C.c_int32), ("tree_depth", C.c_int32), ("coord_max", C.c_float)]
 
 
+class SampleOrderInfo(C.Structure):
+    """MirtSampleOrderInfo: the lengths of mirt_get_sample_order's arrays."""
+    _fields_ = [("total_samples", C.c_int64), ("last_launch_samples", C.c_int64)]
+
+
 # The header's struct behind each class, for the test that compares them field by field
 STRUCTS = {"MirtVec3": Vec3, "MirtRay": Ray, "MirtHit": Hit, "MirtCamera": Camera, "MirtShading": Shading, "MirtSceneDesc": SceneDesc,
            "MirtRenderParams": RenderParams, "MirtStats": Stats, "MirtMultiStats": MultiStats, "MirtTreeNode": TreeNode,
-           "MirtRecordInfo": RecordInfo}
+           "MirtRecordInfo": RecordInfo, "MirtSampleOrderInfo": SampleOrderInfo}
 
 _int, _i64, _u32, _u64, _f, _str, _vp = C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_char_p, C.c_void_p
 _out = C.POINTER
@@ -184,6 +189,9 @@ SIGNATURES = {
     "mirt_probe_math": (_int, [_int, _int, _int, _vp, _vp]),
     "mirt_probe_xorwow": (_int, [_int, _int, _int, _int, _vp]),
     "mirt_probe_qbox": (_int, [_int, _int, _vp, _vp]),
+    "mirt_probe_sort": (_int, [_int, _int, _int, _vp, _vp, _vp]),
+    "mirt_probe_sched": (_int, [_int, _int, _int, _vp, _vp]),
+    "mirt_get_sample_order": (_int, [_vp, _out(SampleOrderInfo), _vp, _vp, _vp]),
     "mirt_write_png": (_int, [_str, _vp, _int, _int]),
 }
 EXPORTS = list(SIGNATURES)

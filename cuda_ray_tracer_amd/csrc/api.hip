@@ -608,4 +608,22 @@ int mirt_probe_qbox(int device, int n, const float* host_in, uint32_t* host_out)
   return probe_qbox(device, n, host_in, host_out);
 }
 
+int mirt_probe_sort(int device, int mode, int n, const uint32_t* host_keys, uint32_t* host_keys_out, uint32_t* host_vals_out)
+{
+  if (n <= 0 || (mode != 0 && mode != 1) || !host_keys || !host_keys_out || !host_vals_out) { set_error("mirt_probe_sort: bad argument"); return MIRT_ERR_ARG; }
+  return probe_sort(device, mode, n, host_keys, host_keys_out, host_vals_out);
+}
+
+int mirt_probe_sched(int device, int which, int n, const uint32_t* host_in, uint32_t* host_out)
+{
+  if (n <= 0 || (which != 0 && which != 1) || !host_in || !host_out) { set_error("mirt_probe_sched: bad argument"); return MIRT_ERR_ARG; }
+  return probe_sched(device, which, n, host_in, host_out);
+}
+
+int mirt_get_sample_order(MirtScene* sc, MirtSampleOrderInfo* info, uint32_t* order, uint32_t* keys, uint32_t* sorted_keys)
+{
+  MIRT_TRY(enter_scene(sc, "mirt_get_sample_order"));
+  return get_sample_order(sc, info, order, keys, sorted_keys);
+}
+
 } // extern "C"

@@ -563,6 +563,17 @@ void radix_sort_pass(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t*
   launch_blocks(radix_pass_kernel<true>, sblocks, stream, keys_in, vals_in, keys_out, vals_out, hist, hist, totals, n, shift, sblocks);
 }
 
+// The whole sort: four stable passes over the n keys in k0 with their values in v0 (BuildLayout) -- an even number, so keys and
+// values end where they started, in k0 / v0
+void radix_sort_keys(uint32_t* ws, const BuildLayout& at, int n, hipStream_t stream)
+{
+  uint32_t *ki = ws + at.k0, *vi = ws + at.v0, *ko = ws + at.k1, *vo = ws + at.v1;
+  for (int pass = 0; pass < 4; ++pass) {
+    radix_sort_pass(ki, vi, ko, vo, ws, at, n, 8 * pass, stream);
+    std::swap(ki, ko); std::swap(vi, vo);
+  }
+}
+
 } // namespace
 
 // One stable radix pass over the low byte of the keys (render.hip orders a frame's samples by cost class with it): keys_out /
@@ -593,17 +604,14 @@ int Build::scene_bounds() const
   return MIRT_OK;
 }
 
-// Morton codes, then four stable passes: an even number, so codes and order end where they started, in k0 / v0
+// Morton codes and positions into k0 / v0, the sort, and its result out of k0 / v0
 int Build::sort_by_morton() const
 {
-  uint32_t *ki = ws + at.k0, *vi = ws + at.v0, *ko = ws + at.k1, *vo = ws + at.v1;
-  launch_items(morton_kernel, n, stream, sc->refs_in, sc->spheres, sc->tri_verts, n, sc->bounds_keys, ki, vi);
-  for (int pass = 0; pass < 4; ++pass) {
-    radix_sort_pass(ki, vi, ko, vo, ws, at, n, 8 * pass, stream);
-    std::swap(ki, ko); std::swap(vi, vo);
-  }
-  MIRT_HIP(hipMemcpyAsync(sc->codes, ki, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, stream));
-  MIRT_HIP(hipMemcpyAsync(sc->order, vi, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, stream));
+  uint32_t *codes = ws + at.k0, *order = ws + at.v0;
+  launch_items(morton_kernel, n, stream, sc->refs_in, sc->spheres, sc->tri_verts, n, sc->bounds_keys, codes, order);
+  radix_sort_keys(ws, at, n, stream);
+  MIRT_HIP(hipMemcpyAsync(sc->codes, codes, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, stream));
+  MIRT_HIP(hipMemcpyAsync(sc->order, order, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, stream));
   return MIRT_OK;
 }
 
@@ -675,6 +683,36 @@ int Build::read_back_scene_facts() const
 }
 
 } // namespace
+
+// mirt_probe_sort: the sort kernels on keys of the caller's choosing, on the null stream.  Mode 0: the build's sort, through
+// radix_sort_keys as sort_by_morton calls it, the values being the positions 0 .. n-1.  Mode 1: sort_low_byte as render.hip calls it.
+int probe_sort(int device, int mode, int n, const uint32_t* keys, uint32_t* keys_out, uint32_t* vals_out)
+{
+  MIRT_HIP(hipSetDevice(device));
+  const size_t bytes = sizeof(uint32_t) * (size_t)n;
+  if (mode == 0) {
+    const BuildLayout at = build_layout(n);
+    DevBuf<uint32_t> ws;
+    MIRT_TRY(ws.alloc(at.total, "ws"));
+    std::vector<uint32_t> positions((size_t)n);
+    for (int i = 0; i < n; ++i) positions[i] = (uint32_t)i;
+    MIRT_HIP(hipMemcpy(ws + at.k0, keys, bytes, hipMemcpyHostToDevice));
+    MIRT_HIP(hipMemcpy(ws + at.v0, positions.data(), bytes, hipMemcpyHostToDevice));
+    radix_sort_keys(ws, at, n, nullptr);
+    MIRT_HIP(hipGetLastError());
+    MIRT_HIP(hipMemcpy(keys_out, ws + at.k0, bytes, hipMemcpyDeviceToHost));
+    MIRT_HIP(hipMemcpy(vals_out, ws + at.v0, bytes, hipMemcpyDeviceToHost));
+    return MIRT_OK;
+  }
+  DevBuf<uint32_t> ki, ko, vo, ws;
+  MIRT_TRY(ki.alloc((size_t)n, "keys_in")); MIRT_TRY(ko.alloc((size_t)n, "keys_out")); MIRT_TRY(vo.alloc((size_t)n, "vals_out"));
+  MIRT_TRY(ws.alloc(sort_low_byte_ws_words(n), "ws"));
+  MIRT_HIP(hipMemcpy(ki, keys, bytes, hipMemcpyHostToDevice));
+  MIRT_TRY(sort_low_byte(ki, ko, vo, n, ws, nullptr));
+  MIRT_HIP(hipMemcpy(keys_out, ko, bytes, hipMemcpyDeviceToHost));
+  MIRT_HIP(hipMemcpy(vals_out, vo, bytes, hipMemcpyDeviceToHost));
+  return MIRT_OK;
+}
 
 int build_lbvh(MirtScene* sc, hipStream_t stream)
 {

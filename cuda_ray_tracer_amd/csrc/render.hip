@@ -676,6 +676,13 @@ __global__ void __launch_bounds__(SORT_BINS) order_kernel(const uint32_t* __rest
   }
 }
 
+// mirt_probe_sched which = 0: cost_key itself, one value per thread
+__global__ void probe_cost_key_kernel(int n, const uint32_t* __restrict__ in, uint32_t* __restrict__ out)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = cost_key(in[i]);
+}
+
 int64_t local_pixels(const MirtRenderParams* p)
 {
   if (p->width <= 0 || p->height <= 0 || p->stripe_rows <= 0 || p->num_parts <= 0 || p->part < 0 || p->part >= p->num_parts) return -1;
@@ -975,6 +982,22 @@ static int sample_table_finish(MirtScene* sc, hipStream_t stream)
   return MIRT_OK;
 }
 
+// mirt_get_sample_order: the table as the next call of its shape would read it, and the keys of the last launch measured.  A
+// measurement in flight is waited for.  (The table outlives camera, geometry and shading updates, as the hand-out does.)
+int get_sample_order(MirtScene* sc, MirtSampleOrderInfo* info, uint32_t* order, uint32_t* keys, uint32_t* sorted_keys)
+{
+  if (sc->so_busy) { MIRT_HIP(hipEventSynchronize(sc->so_ev)); sc->so_busy = false; }
+  if (sc->so_key < 0 || !sc->so_order.get()) {
+    set_error("mirt_get_sample_order: the scene has no sample order (the first call of a shape measures one under sched = 2)");
+    return MIRT_ERR_STATE;
+  }
+  if (info) { info->total_samples = sc->so_total; info->last_launch_samples = sc->so_last; }
+  if (order) MIRT_HIP(hipMemcpy(order, sc->so_order, 4 * (size_t)sc->so_total, hipMemcpyDeviceToHost));
+  if (keys) MIRT_HIP(hipMemcpy(keys, sc->so_keys, 4 * (size_t)sc->so_last, hipMemcpyDeviceToHost));
+  if (sorted_keys) MIRT_HIP(hipMemcpy(sorted_keys, sc->so_keys2, 4 * (size_t)sc->so_last, hipMemcpyDeviceToHost));
+  return MIRT_OK;
+}
+
 // one instantiation per form of the random-number tables (device_common.h, xw_init), per node format and per specialisation:
 // 2 (counting) x 2 (tables) x 8 = 32 kernels, and the LDS-only stack (SPEC_LDS_STACK) for the five of the eight that walk a
 // binary tree: 20 more; the form with the ray-start block (SPEC_START_LDS) of the sphere-only one among those: 4 more
@@ -1126,7 +1149,10 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
     if (slab == pl.nslabs - 1) MIRT_HIP(hipEventRecord(cx.ev2, stream));
     rc = resolve_slab(c, cx, p0, pn);
     // this launch's part of the cost-ordered sample table, for later calls of this shape (the key buffer is reused by the next slab)
-    if (rc == MIRT_OK && measure_samples) rc = sort_low_byte(sc->so_keys, sc->so_keys2, sc->so_order + (size_t)p0 * sample_count, pn * sample_count, sc->so_ws, stream);
+    if (rc == MIRT_OK && measure_samples) {
+      rc = sort_low_byte(sc->so_keys, sc->so_keys2, sc->so_order + (size_t)p0 * sample_count, pn * sample_count, sc->so_ws, stream);
+      sc->so_last = pn * sample_count;      // (what so_keys / so_keys2 hold from here on: mirt_get_sample_order)
+    }
     if (rc != MIRT_OK) return rc;
   }
   if (measure_samples) rc = sample_table_finish(sc, stream);
@@ -1223,6 +1249,21 @@ int probe_qbox(int device, int n, const float* in, uint32_t* out)
   hipLaunchKernelGGL(probe_qbox_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, di, dout);
   MIRT_HIP(hipGetLastError());
   MIRT_HIP(hipMemcpy(out, dout, 4 * 20 * (size_t)n, hipMemcpyDeviceToHost));
+  return MIRT_OK;
+}
+
+// which = 0: cost_key of every element.  which = 1: order_kernel over n chunk costs, launched as chunk_order_finish launches it.
+int probe_sched(int device, int which, int n, const uint32_t* in, uint32_t* out)
+{
+  MIRT_HIP(hipSetDevice(device));
+  DevBuf<uint32_t> di, dout;
+  MIRT_TRY(di.alloc((size_t)n, "di")); MIRT_TRY(dout.alloc((size_t)n, "dout"));
+  MIRT_HIP(hipMemcpy(di, in, 4 * (size_t)n, hipMemcpyHostToDevice));
+  MIRT_HIP(hipMemset(dout, 0xff, 4 * (size_t)n));      // (a position the kernel leaves out reads as no index)
+  if (which == 0) hipLaunchKernelGGL(probe_cost_key_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, di, dout);
+  else hipLaunchKernelGGL(order_kernel, dim3(1), dim3(SORT_BINS), 0, 0, di, (uint32_t)n, dout);
+  MIRT_HIP(hipGetLastError());
+  MIRT_HIP(hipMemcpy(out, dout, 4 * (size_t)n, hipMemcpyDeviceToHost));
   return MIRT_OK;
 }
 

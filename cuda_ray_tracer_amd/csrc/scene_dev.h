@@ -260,6 +260,7 @@ struct MirtScene {
   // sched = 2: the frame's samples in order of decreasing cost class, measured once per frame size (shared by the contexts)
   mirt::DevBuf<uint32_t> so_order, so_keys, so_keys2, so_ws;      // [call's samples], [slab's samples] x 2, the sort's workspace
   long long so_key = -1, so_pending_key = -1, so_total = -1; mirt::Event so_ev; bool so_busy = false;
+  long long so_last = 0;                   // samples of the last launch measured: what so_keys / so_keys2 hold (mirt_get_sample_order)
   // rng tables cache
   mirt::RngCache rng;
   // LBVH build timing
@@ -295,6 +296,7 @@ namespace mirt {
 // lbvh_build.hip (sort_low_byte_ws_words: build_plan.h)
 int build_lbvh(MirtScene* sc, hipStream_t stream);
 int sort_low_byte(const uint32_t* keys_in, uint32_t* keys_out, uint32_t* vals_out, long long n, uint32_t* ws, hipStream_t stream);
+int probe_sort(int device, int mode, int n, const uint32_t* keys, uint32_t* keys_out, uint32_t* vals_out);
 int get_tree(MirtScene* sc, MirtTreeNode* nodes, uint32_t* codes, MirtPrimRef* refs, float* bounds);
 int get_records(MirtScene* sc, MirtRecordInfo* info, void* nodes, void* qnodes, void* wnodes, void* prims, uint32_t* unit_prim,
                 uint32_t* tris_before, float* tri_boxes, float* qparams);
@@ -308,6 +310,8 @@ int fold_trace_time(MirtScene* sc, RenderCtx& cx);
 int probe_math(int device, int which, int n, const float* in, float* out);
 int probe_xorwow(int device, int spp, int nstreams, int draws, uint32_t* out);
 int probe_qbox(int device, int n, const float* in, uint32_t* out);
+int probe_sched(int device, int which, int n, const uint32_t* in, uint32_t* out);
+int get_sample_order(MirtScene* sc, MirtSampleOrderInfo* info, uint32_t* order, uint32_t* keys, uint32_t* sorted_keys);
 int ensure_rng_tables(RngCache* rc, int sample_tables, long long frame_pixels, hipStream_t stream, RngTablesDev* out, bool allow_larger);
 int render_accumulate(MirtScene* sc, const MirtRenderParams* p, void* d_accum, int sample_first, int sample_count, hipStream_t stream);
 void rng_cache_free(RngCache* rc);

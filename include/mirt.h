@@ -647,6 +647,28 @@ int mirt_probe_xorwow(int device, int spp, int num_streams, int draws, uint32_t*
  * a hit, in the order above; [10..12] the entry parameter of the first three forms (float bits; the wide form returns none);
  * [13] zero; [14..16] the grid step, [17..19] 2^60 / step (float bits). */
 int mirt_probe_qbox(int device, int n, const float* host_in, uint32_t* host_out);
+/* The radix-sort kernels on n keys of the caller's choosing (callers detect this call and the two below by their symbols;
+ * MIRT_VERSION stays 3).  mode 0: the sort of a build -- four stable passes over all 32 bits, the values being the positions
+ * 0..n-1 -- through the function mirt_build_lbvh calls.  mode 1: the one stable pass over the low byte that orders a frame's samples
+ * by cost class, as the render calls it.  host_keys_out receives the whole keys in sorted order, host_vals_out where each stood in
+ * host_keys: the stable argsort of the keys (mode 0) or of their low bytes (mode 1).  Host-synchronous; n <= 0, another mode or
+ * a NULL pointer is MIRT_ERR_ARG. */
+int mirt_probe_sort(int device, int mode, int n, const uint32_t* host_keys, uint32_t* host_keys_out, uint32_t* host_vals_out);
+/* What the hand-out orders are made from.  which 0: host_out[i] = the cost key of a sample that took host_in[i] traversal steps
+ * (255 for none, else 255 - 4 floor(log2 s) - the two bits below the leading one), through the device function the trace kernels
+ * call.  which 1: host_in holds n chunk costs, host_out receives the chunk order of scene option "sched" = 1 -- a permutation of 0..n-1
+ * by cost bin, most expensive bin first (bin = 1023 - cost / 8, costs of 8192 and more in bin 0), made by the kernel and the launch
+ * shape the render uses.  Host-synchronous; n <= 0, another `which` or a NULL pointer is MIRT_ERR_ARG. */
+int mirt_probe_sched(int device, int which, int n, const uint32_t* host_in, uint32_t* host_out);
+/* The by-sample hand-out table of scene option "sched" = 2, as the next call of the measured shape reads it.  total_samples: the samples
+ * of the call that measured it, the length of `order`; every launch of that call owns a consecutive segment of `order`, a permutation
+ * of the launch's own sample indices (position k of the hand-out -> sample), most expensive cost class first, frame order within a class.
+ * last_launch_samples: the samples of that call's last launch, the length of `keys` (its samples' cost keys, by sample) and of
+ * `sorted_keys` (the same keys in hand-out order).  Host-synchronous: a measurement in flight is waited for.  Any output pointer
+ * may be NULL (ask for `info` first to size the others).  MIRT_ERR_STATE when no call has measured a table on this scene; the table
+ * outlives camera, geometry and shading updates, like the hand-out itself. */
+typedef struct MirtSampleOrderInfo { int64_t total_samples, last_launch_samples; } MirtSampleOrderInfo;
+int mirt_get_sample_order(MirtScene* sc, MirtSampleOrderInfo* info, uint32_t* order, uint32_t* keys, uint32_t* sorted_keys);
 
 /* ---- output ----------------------------------------------------------------------------------- */
 /* Image::save, libpng.cpp:73-107: 8-bit RGBA, non-interlaced PNG (own encoder; zlib only). */

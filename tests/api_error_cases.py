@@ -268,6 +268,14 @@ def cases():
     for tag, x in (("none", None), ("list", [0.0] * 20), ("dtype_f32", np.zeros((3, 20), np.float32)), ("2d", np.zeros((3, 1), layouts.QBOX_CASE)),
                    ("strided", np.zeros(6, layouts.QBOX_CASE)[::2]), ("empty", np.zeros(0, layouts.QBOX_CASE))):
         case(f"probe_qbox:cases:{tag}", lambda x=x: api.probe_qbox(x))
+    words = np.arange(6, dtype=np.uint32)
+    for fn, probe, name in (("probe_sort", api.probe_sort, "keys"), ("probe_sched", api.probe_sched, "x")):
+        for tag, x in (("none", None), ("list", [1, 2, 3]), ("tensor", z(6, dtype=i32)), ("dtype_i32", words.astype(np.int32)), ("dtype_u64", words.astype(np.uint64)),
+                       ("dtype_f32", words.astype(np.float32)), ("2d", words.reshape(3, 2)), ("strided", words[::2]), ("empty", words[:0])):
+            case(f"{fn}:{name}:{tag}", lambda probe=probe, x=x: probe(0, x))
+        for sel in (2, -1, None):
+            case(f"{fn}:selector_{sel}", lambda probe=probe, sel=sel: probe(sel, words))
+        case(f"{fn}:selector_before_{name}", lambda probe=probe: probe(7, None))
 
     # ---- packing ------------------------------------------------------------------------------------------------------------
     for tag, dirs in (("flat", [0.0, 0.0, -1.0]), ("two_columns", z((4, 2))), ("four_columns", z((4, 4))), ("3d", z((4, 3, 1))), ("scalar", 1.0)):

@@ -172,7 +172,7 @@ def compare_dtypes(header, dtypes):
 # ---- the shipped binding agrees ----------------------------------------------------------------------------------------------
 def test_the_parser_sees_the_whole_header():
     names = sorted(set(re.findall(r"\b(mirt_[a-z0-9_]+)\s*\(", HEADER)))
-    assert sorted(name for name, _, _ in prototypes(HEADER)) == names and len(names) == 66
+    assert sorted(name for name, _, _ in prototypes(HEADER)) == names and len(names) == 69
     parsed = structs(HEADER)
     assert set(parsed) >= set(binding.STRUCTS) | set(DTYPES) | {"MirtRGB", "MirtSun", "MirtBulb"}
     assert parsed["MirtVec3"] == [("x", (4, True, True)), ("y", (4, True, True)), ("z", (4, True, True))]
@@ -189,7 +189,7 @@ def test_every_prototype_has_its_signature_and_every_signature_its_prototype():
 
 def test_every_struct_class_has_the_headers_fields():
     assert sorted(binding.STRUCTS) == sorted(["MirtVec3", "MirtRay", "MirtHit", "MirtCamera", "MirtShading", "MirtSceneDesc", "MirtRenderParams",
-                                              "MirtStats", "MirtMultiStats", "MirtTreeNode", "MirtRecordInfo"])
+                                              "MirtStats", "MirtMultiStats", "MirtTreeNode", "MirtRecordInfo", "MirtSampleOrderInfo"])
     assert compare_structs(HEADER, binding.STRUCTS) == []
     assert (C.sizeof(binding.Ray), C.sizeof(binding.Hit), C.sizeof(binding.Camera), C.sizeof(binding.Shading)) == (32, 24, 64, 12)
 

@@ -935,6 +935,8 @@ from .closest import closest_points, pack_points      # noqa: E402,F401
 from .multihit import trace_rays_multi, count_hits      # noqa: E402,F401
 # Contact queries (include_ext/mirt_contacts.h): contacts.py holds that header's signature and calls
 from .contacts import closest_points_multi, count_within      # noqa: E402,F401
+# Sphere casts (include_ext/mirt_spherecast.h): spherecast.py holds that header's signature and calls
+from .spherecast import cast_spheres, pack_casts      # noqa: E402,F401
 
 
 def pack_rays(origins, dirs, tmax=float("inf")):

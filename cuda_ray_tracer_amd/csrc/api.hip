@@ -392,6 +392,13 @@ int mirt_closest_points_multi(MirtScene* sc, const void* d_points, int64_t n, in
   return closest_points_multi(sc, d_points, n, k, d_hits, d_counts, d_features, flags, (hipStream_t)stream);
 }
 
+// (include_ext/mirt_spherecast.h)
+int mirt_cast_spheres(MirtScene* sc, const void* d_casts, int64_t n, void* d_hits, void* d_features, uint32_t flags, void* stream)
+{
+  MIRT_TRY(enter_scene(sc, "mirt_cast_spheres"));
+  return cast_spheres(sc, d_casts, n, d_hits, d_features, flags, (hipStream_t)stream);
+}
+
 size_t mirt_denoise_work_bytes(const MirtRenderParams* p) { return denoise_work_bytes(p); }
 
 int mirt_denoise(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, const void* d_features,

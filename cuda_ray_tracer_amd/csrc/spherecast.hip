@@ -1,0 +1,326 @@
+// Sphere casts on a built scene (include_ext/mirt_spherecast.h: mirt_cast_spheres): for each row the first
+// contact of a ball of radius r whose centre travels along a ray -- the admitted candidate with the smallest (t, kind, id), which
+// the header defines over the scene's arrays, so the order of the visits is free.  Like the other queries it reads the scene only
+// and touches no render context, counter, hand-out table or RNG table.
+//
+// sphere_cast_kernel<ANY>  one lane = one row (grid-stride over the batch).  The planes from scalar loads, then a stack walk over the
+//                          exact 64-byte node records: a slab test of the centre ray against both children's boxes grown by
+//                          r + sigma, over [0, best + tau], the child with the nearer entry first, the other pushed.  best starts
+//                          at the row's tmax and shrinks with every admitted candidate; sigma and tau are the header's slacks.
+//                          The loop keeps (t, ref) only; the winner's point and normal are made after it, by the header's
+//                          operations.  ANY (MIRT_CAST_ANY_HIT): the walk ends at the first admitted candidate.  The stack is the
+//                          query kernels': [entry][lane] in LDS, deeper entries in the lane's private array.
+#include "scene_dev.h"
+#include "host_scene.h"
+#include "shade_common.h"
+#include "query_walk.h"
+#include "point_query.h"
+#include "../../include_ext/mirt_spherecast.h"
+
+#include <cmath>
+
+namespace mirt {
+namespace {
+
+// the compiler's report decides: at 5 waves per SIMD both instances take the 96 VGPRs there are and spill
+// nothing; at 6 (80 VGPRs) they spill 11 and 12 registers, at 8 (64) about 30
+constexpr int SWAVES_PER_SIMD = 5;
+constexpr float SLACK = 3.814697265625e-06f;         // 2^-18 (mirt_spherecast.h, "Pruning")
+constexpr float TAU = 9.5367431640625e-07f;          // 2^-20
+
+struct CastArgs {
+  const float4* casts;            // (o, tmax), (d, r)
+  uint32_t* hits;                 // MirtHit: 6 words
+  float4* features;               // nullable: (P, 1), (n, 0)
+  long long n;
+  const float4* nodes;            // record heap (scene_dev.h)
+  const uint32_t* unit_prim;
+  const float4* tri_verts;        // file order: p0, p1, p2 of every triangle
+  const PlaneDev* planes; int num_planes;
+  uint32_t root_ref;              // the exact records' root (REF_NONE: no primitive)
+  uint32_t prim_base16;
+  float coord_max;                // largest coordinate magnitude of the scene box
+  int lds_depth;                  // stack entries kept in LDS (<= QUERY_STACK_LDS)
+};
+
+// the moving ball: the centre's ray (o, d normalised) and the radius
+struct Ball { f3 o, d; float r; };
+
+// ---- the header's operations, candidate by candidate: each returns t, or a NaN (or +inf) for no contact ----------------------------
+// the centre ray against the ball (p, R), closest-approach form: a the parameter of the closest approach, h2 = R^2 - |w|^2
+MIRT_DEV void approach(const f3& p, float R, const Ball& k, float& a, float& h2)
+{
+  const f3 m = p - k.o;
+  a = dot(m, k.d);
+  const f3 w = m - k.d * a;
+  h2 = R * R - dot(w, w);
+}
+MIRT_DEV float ball_entry(const f3& p, float R, const Ball& k)
+{
+  float a, h2;
+  approach(p, R, k, a, h2);
+  return h2 >= 0.0f ? a - sqrtf(h2) : NAN;
+}
+MIRT_DEV float ball_exit(const f3& p, float R, const Ball& k)
+{
+  float a, h2;
+  approach(p, R, k, a, h2);
+  return a + sqrtf(h2 < 0.0f ? 0.0f : h2);
+}
+
+MIRT_DEV float sphere_cast(const float4& s, const Ball& k)
+{
+  const f3 c = mk3(s.x, s.y, s.z);
+  const float g = length(k.o - c) - s.w;
+  if (fabsf(g) <= k.r) return 0.0f;
+  return g > 0.0f ? ball_entry(c, s.w + k.r, k) : ball_exit(c, s.w - k.r, k);
+}
+
+// the plane rule for a unit normal N: a plane's normalize(nor), a triangle's nor
+MIRT_DEV float plane_cast(const f3& N, const f3& point, const Ball& k)
+{
+  const float s = dot(N, k.o - point);
+  if (fabsf(s) <= k.r) return 0.0f;
+  const float dn = dot(N, k.d);
+  if (s > 0.0f && dn < 0.0f) return (k.r - s) / dn;
+  if (s < 0.0f && dn > 0.0f) return (-k.r - s) / dn;
+  return NAN;
+}
+
+// mirt_closest.h's region walk for q falls through to its last case (closest_on_triangle's tests, in its order)
+MIRT_DEV bool in_face_region(const f3& a, const f3& b, const f3& c, const f3& q)
+{
+  const f3 ab = b - a, ac = c - a, ap = q - a;
+  const float d1 = dot(ab, ap), d2 = dot(ac, ap);
+  if (d1 <= 0.0f && d2 <= 0.0f) return false;
+  const f3 bp = q - b;
+  const float d3 = dot(ab, bp), d4 = dot(ac, bp);
+  if (d3 >= 0.0f && d4 <= d3) return false;
+  const float vc = d1 * d4 - d3 * d2;
+  if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) return false;
+  const f3 cp = q - c;
+  const float d5 = dot(ab, cp), d6 = dot(ac, cp);
+  if (d6 >= 0.0f && d5 <= d6) return false;
+  const float vb = d5 * d2 - d1 * d6;
+  if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) return false;
+  const float va = d3 * d6 - d5 * d4;
+  const float e = d4 - d3, f = d5 - d6;
+  return !(va <= 0.0f && e >= 0.0f && f >= 0.0f);
+}
+
+// the edge (p, q): the centre ray against the cylinder of radius r about its line, valid between its end points
+MIRT_DEV float edge_cast(const f3& p, const f3& q, const Ball& k)
+{
+  const f3 e = q - p;
+  const float ee = dot(e, e);
+  const f3 m = k.o - p;
+  const float u = dot(m, e) / ee, kk = dot(k.d, e) / ee;
+  const f3 mp = m - e * u, dp = k.d - e * kk;
+  const float A = dot(dp, dp);
+  const float t0 = -dot(mp, dp) / A;
+  const f3 wv = mp + dp * t0;
+  const float h2 = k.r * k.r - dot(wv, wv);
+  const float t = t0 - sqrtf(h2 / A);
+  const float at = u + t * kk;
+  return (ee != 0.0f && A != 0.0f && h2 >= 0.0f && at >= 0.0f && at <= 1.0f) ? t : NAN;
+}
+
+// (the smallest piece with t >= 0: a NaN never counts)
+MIRT_DEV void take_piece(float& t, float piece) { t = (piece >= 0.0f && piece < t) ? piece : t; }
+
+MIRT_DEV float triangle_cast(const f3& a, const f3& b, const f3& c, const f3& nor, const Ball& k)
+{
+  if (length(k.o - closest_on_triangle(a, b, c, k.o)) <= k.r) return 0.0f;
+  float t = INFINITY;
+  const float tf = plane_cast(nor, a, k);
+  // (a record normal of (0, 0, 0) -- a cross product shorter than 1e-6 -- names no plane: such a triangle has no face piece)
+  if (dot(nor, nor) > 0.0f && in_face_region(a, b, c, k.o + k.d * tf)) take_piece(t, tf);
+  take_piece(t, ball_entry(a, k.r, k));
+  take_piece(t, ball_entry(b, k.r, k));
+  take_piece(t, ball_entry(c, k.r, k));
+  take_piece(t, edge_cast(a, b, k));
+  take_piece(t, edge_cast(a, c, k));
+  take_piece(t, edge_cast(b, c, k));
+  return t;
+}
+
+// the centre ray's interval in the box [x0, x1] x [y0, y1] x [z0, z1] grown by `grow`, from parameter 0 on: fminf / fmaxf drop a
+// NaN (0 * inf: the centre on a face of a slab it runs along), so such an axis does not decide
+MIRT_DEV void box_interval(float x0, float x1, float y0, float y1, float z0, float z1, const f3& o, const f3& inv, float grow, float& enter, float& leave)
+{
+  const float ax = ((x0 - grow) - o.x) * inv.x, bx = ((x1 + grow) - o.x) * inv.x;
+  const float ay = ((y0 - grow) - o.y) * inv.y, by = ((y1 + grow) - o.y) * inv.y;
+  const float az = ((z0 - grow) - o.z) * inv.z, bz = ((z1 + grow) - o.z) * inv.z;
+  enter = fmaxf(fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz)), 0.0f);
+  leave = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
+}
+
+template <bool ANY>
+__global__ void __launch_bounds__(QUERY_BLOCK, SWAVES_PER_SIMD) sphere_cast_kernel(const CastArgs a)
+{
+  __shared__ uint32_t lds_stack[QUERY_STACK_LDS * QUERY_BLOCK];
+  uint32_t spill[STACK_TOTAL];             // (entries lds_depth.. of the lane's stack: the rarely taken spill path)
+  const int tid = threadIdx.x;
+  const long long stride = (long long)gridDim.x * QUERY_BLOCK;
+  const unsigned char* const heap = reinterpret_cast<const unsigned char*>(a.nodes);
+  const ConstPlanes planes = const_planes(a.planes);
+  for (long long i = (long long)blockIdx.x * QUERY_BLOCK + tid; i < a.n; i += stride) {
+    const float4 r0 = a.casts[2 * i], r1 = a.casts[2 * i + 1];
+    Ball k;
+    k.o = mk3(r0.x, r0.y, r0.z);
+    k.d = normalize(mk3(r1.x, r1.y, r1.z));
+    k.r = r1.w;
+    const float tmax = r0.w;
+    // (x - x is 0 for a finite x and NaN for an infinity or a NaN)
+    const bool live = ray_is_live(tmax, k.d) && k.r >= 0.0f && (k.r - k.r) == 0.0f && finite3(r0);
+    float best = tmax;               // the smallest admitted t so far; without a winner, tmax
+    uint32_t refbest = REF_NONE;     // the winner, a primitive record of the heap ...
+    int plane_id = -1;               // ... or a plane
+    if (live) {
+      for (int j = 0; j < a.num_planes; ++j) {
+        const f3 N = normalize(mk3(planes[j].nx, planes[j].ny, planes[j].nz));
+        const float t = plane_cast(N, mk3(planes[j].px, planes[j].py, planes[j].pz), k);
+        if (t >= 0.0f && t < best) { best = t; plane_id = j; }      // (an equal t: the lower index stays)
+      }
+    }
+    // (a cast for any contact that a plane already answers needs no walk)
+    if (live && a.root_ref != REF_NONE && !(ANY && plane_id >= 0)) {
+      const f3 inv = mk3(1.0f / k.d.x, 1.0f / k.d.y, 1.0f / k.d.z);
+      const float sigma = ((fmaxf(fmaxf(fabsf(k.o.x), fabsf(k.o.y)), fabsf(k.o.z)) + a.coord_max) + k.r) * SLACK;
+      const float grow = k.r + sigma;
+      float bound = best + best * TAU;     // a box the centre enters later than this holds nothing that wins or ties
+      uint32_t cur = a.root_ref;
+      int sp = 0;
+      for (;;) {
+        const float4* rec = reinterpret_cast<const float4*>(heap + (cur << 4));
+        bool pop;
+        if (cur & REF_LEAF) {
+          float t;
+          uint32_t id = 0u;
+          if (cur & REF_TRI) {
+            id = a.unit_prim[(cur & REF_OFFMASK) - a.prim_base16] & 0x7fffffffu;
+            const float4* v = a.tri_verts + 3 * (size_t)id;
+            const float4 va = v[0], vb = v[1], vc = v[2];
+            const float4 q0 = rec[0], q1 = rec[1];
+            t = triangle_cast(mk3(va.x, va.y, va.z), mk3(vb.x, vb.y, vb.z), mk3(vc.x, vc.y, vc.z), mk3(q0.w, q1.x, q1.y), k);
+          } else {
+            t = sphere_cast(rec[0], k);
+          }
+          bool better = t >= 0.0f && t < best;
+          if (t == best && (plane_id >= 0 || refbest != REF_NONE)) {
+            // a tie with the winner: (kind, id) decides -- a primitive before a plane, a sphere before a triangle, the lower index
+            if (plane_id >= 0 || (cur & REF_TRI) != (refbest & REF_TRI)) {
+              better = plane_id >= 0 || !(cur & REF_TRI);
+            } else {
+              if (!(cur & REF_TRI)) id = a.unit_prim[(cur & REF_OFFMASK) - a.prim_base16] & 0x7fffffffu;
+              better = id < (a.unit_prim[(refbest & REF_OFFMASK) - a.prim_base16] & 0x7fffffffu);
+            }
+          }
+          if (better) {
+            best = t; refbest = cur; plane_id = -1;
+            bound = best + best * TAU;
+            if (ANY) break;
+          }
+          pop = true;
+        } else {
+          const float4 b0 = rec[0], b1 = rec[1], b2 = rec[2];
+          const uint2 ch = *reinterpret_cast<const uint2*>(rec + 3);
+          float el, ll, er, lr;
+          box_interval(b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, k.o, inv, grow, el, ll);
+          box_interval(b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, k.o, inv, grow, er, lr);
+          const bool hl = !(el > fminf(ll, bound)), hr = !(er > fminf(lr, bound));
+          const bool right_first = er < el;      // the child with the nearer entry first
+          if (hl && hr) {
+            // (stack_push and stack_pop of query_walk.h, written out as closest.hip does: DESIGN.md section 6q)
+            const uint32_t later = right_first ? ch.x : ch.y;
+            if (sp < a.lds_depth) lds_stack[sp * QUERY_BLOCK + tid] = later;
+            else spill[(sp - a.lds_depth) & (STACK_TOTAL - 1)] = later;
+            ++sp;
+          }
+          cur = (hl && hr) ? (right_first ? ch.y : ch.x) : (hl ? ch.x : ch.y);
+          pop = !(hl || hr);
+        }
+        if (pop) {
+          if (sp == 0) break;
+          --sp;
+          cur = sp < a.lds_depth ? lds_stack[sp * QUERY_BLOCK + tid] : spill[(sp - a.lds_depth) & (STACK_TOTAL - 1)];
+        }
+      }
+    }
+    // the winner's record: the centre at contact, the candidate's closest point to it, the push-out direction
+    float t = -1.0f;
+    uint32_t kind = MIRT_HIT_NONE, id = 0u;
+    f3 P = mk3(0.0f, 0.0f, 0.0f), n = P;
+    const bool hit = plane_id >= 0 || refbest != REF_NONE;
+    if (hit) {
+      t = best;
+      const f3 Cw = k.o + k.d * t;
+      if (plane_id >= 0) {
+        const f3 N = normalize(mk3(planes[plane_id].nx, planes[plane_id].ny, planes[plane_id].nz));
+        const float s = dot(N, Cw - mk3(planes[plane_id].px, planes[plane_id].py, planes[plane_id].pz));
+        P = Cw - N * s;
+        kind = MIRT_HIT_PLANE; id = (uint32_t)plane_id;
+      } else {
+        id = a.unit_prim[(refbest & REF_OFFMASK) - a.prim_base16] & 0x7fffffffu;
+        if (refbest & REF_TRI) {
+          P = triangle_point(a.tri_verts, id, Cw);
+          kind = MIRT_HIT_TRIANGLE;
+        } else {
+          const float4 s = a.nodes[refbest & REF_OFFMASK];
+          const f3 c = mk3(s.x, s.y, s.z);
+          P = c + normalize(Cw - c) * s.w;
+          kind = MIRT_HIT_SPHERE;
+        }
+      }
+      n = normalize(Cw - P);
+    }
+    store_hit(a.hits + 6 * i, t, kind, id, n);
+    if (a.features) {
+      a.features[2 * i] = make_float4(P.x, P.y, P.z, hit ? 1.0f : 0.0f);
+      a.features[2 * i + 1] = make_float4(n.x, n.y, n.z, 0.0f);
+    }
+  }
+}
+
+template <bool ANY>
+int launch(MirtScene* sc, const CastArgs& q, int64_t n, hipStream_t stream)
+{
+  const int grid = query_grid_blocks(sc, sphere_cast_kernel<ANY>, SWAVES_PER_SIMD, &sc->spherecast_blocks[ANY ? 1 : 0]);
+  hipLaunchKernelGGL(sphere_cast_kernel<ANY>, dim3(row_launch(n, grid)), dim3(QUERY_BLOCK), 0, stream, q);
+  MIRT_HIP(hipGetLastError());
+  return MIRT_OK;
+}
+
+} // namespace
+
+int cast_spheres(MirtScene* sc, const void* d_casts, int64_t n, void* d_hits, void* d_features, uint32_t flags, hipStream_t stream)
+{
+  const char* const who = "mirt_cast_spheres";
+  if (flags & ~MIRT_CAST_ANY_HIT) { set_error(std::string(who) + ": unknown flag bits"); return MIRT_ERR_ARG; }
+  if (n < 0) { set_error(std::string(who) + ": negative n"); return MIRT_ERR_ARG; }
+  if (n > 0 && (!d_casts || !d_hits)) { set_error(std::string(who) + ": null buffer"); return MIRT_ERR_ARG; }
+  if (!is_aligned(16, (const char*)d_casts, (const char*)d_features) || !is_aligned(4, (const char*)d_hits)) {
+    set_error(std::string(who) + ": d_casts and d_features must be 16-byte aligned, d_hits 4-byte aligned"); return MIRT_ERR_ARG;
+  }
+  const size_t rows = (size_t)n;
+  if (n > 0 && (overlaps(d_hits, 24 * rows, d_casts, 32 * rows) ||
+                (d_features && (overlaps(d_features, 32 * rows, d_casts, 32 * rows) || overlaps(d_features, 32 * rows, d_hits, 24 * rows))))) {
+    set_error(std::string(who) + ": d_hits and d_features must not overlap d_casts or each other"); return MIRT_ERR_ARG;
+  }
+  if (!sc->built) { set_error(std::string(who) + ": call mirt_build_lbvh first"); return MIRT_ERR_STATE; }      // (also with n == 0: the header)
+  if (n == 0) return MIRT_OK;
+  CastArgs q;
+  q.casts = reinterpret_cast<const float4*>(d_casts);
+  q.hits = reinterpret_cast<uint32_t*>(d_hits);
+  q.features = reinterpret_cast<float4*>(d_features);
+  q.n = n;
+  q.nodes = sc->nodes; q.unit_prim = sc->unit_prim;
+  q.tri_verts = sc->tri_verts;
+  q.planes = sc->planes; q.num_planes = sc->d.num_planes;
+  q.root_ref = sc->root_ref; q.prim_base16 = sc->prim_base / 16u;
+  q.coord_max = sc->coord_max;
+  q.lds_depth = query_lds_depth(sc);
+  return (flags & MIRT_CAST_ANY_HIT) ? launch<true>(sc, q, n, stream) : launch<false>(sc, q, n, stream);
+}
+
+} // namespace mirt

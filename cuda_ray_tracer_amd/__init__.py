@@ -2,7 +2,8 @@
 
 Host side: binding.py (include/mirt.h restated for ctypes) and api.py (the calls over it); lighting.py (include/mirt_light.h);
 visibility.py (include/mirt_visibility.h); indirect.py (include/mirt_indirect.h); closest.py (include/mirt_closest.h);
-multihit.py (include/mirt_multihit.h); contacts.py (include_ext/mirt_contacts.h); spherecast.py (include_ext/mirt_spherecast.h).
+multihit.py (include/mirt_multihit.h); contacts.py (include_ext/mirt_contacts.h); spherecast.py (include_ext/mirt_spherecast.h);
+overlap.py (include_ext/mirt_overlap.h).
 Device side: csrc/*.hip, built by build.py into _build/libmirt.so.
 """
 from .api import (MirtError, StlConfig, RawConfig, parseInput, parseText, syntheticScene, initRawConfigFromStl,
@@ -15,7 +16,8 @@ from .api import (MirtError, StlConfig, RawConfig, parseInput, parseText, synthe
                   get_sphere_materials, get_triangle_materials, direct_light, pack_features, direct_light_frame,
                   hemisphere_visibility, cosine_directions, rotations, ambient_occlusion_frame,
                   indirect_light, indirect_light_frame, closest_points, pack_points, trace_rays_multi, count_hits,
-                  closest_points_multi, count_within, cast_spheres, pack_casts)
+                  closest_points_multi, count_within, cast_spheres, pack_casts,
+                  overlap_boxes, count_overlaps, pack_boxes, voxel_rows, occupancy_grid)
 
 __all__ = ["MirtError", "StlConfig", "RawConfig", "parseInput", "parseText", "syntheticScene", "initRawConfigFromStl",
            "copyConfigDataToDevice", "freeRawConfigDeviceMemory", "build_lbvh_karas", "render", "render_params",
@@ -27,4 +29,5 @@ __all__ = ["MirtError", "StlConfig", "RawConfig", "parseInput", "parseText", "sy
            "get_triangle_materials", "direct_light", "pack_features", "direct_light_frame",
            "hemisphere_visibility", "cosine_directions", "rotations", "ambient_occlusion_frame",
            "indirect_light", "indirect_light_frame", "closest_points", "pack_points", "trace_rays_multi", "count_hits",
-           "closest_points_multi", "count_within", "cast_spheres", "pack_casts"]
+           "closest_points_multi", "count_within", "cast_spheres", "pack_casts",
+           "overlap_boxes", "count_overlaps", "pack_boxes", "voxel_rows", "occupancy_grid"]

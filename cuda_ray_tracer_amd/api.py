@@ -937,6 +937,8 @@ from .multihit import trace_rays_multi, count_hits      # noqa: E402,F401
 from .contacts import closest_points_multi, count_within      # noqa: E402,F401
 # Sphere casts (include_ext/mirt_spherecast.h): spherecast.py holds that header's signature and calls
 from .spherecast import cast_spheres, pack_casts      # noqa: E402,F401
+# Box overlaps (include_ext/mirt_overlap.h): overlap.py holds that header's signature and calls
+from .overlap import overlap_boxes, count_overlaps, pack_boxes, voxel_rows, occupancy_grid      # noqa: E402,F401
 
 
 def pack_rays(origins, dirs, tmax=float("inf")):

@@ -399,6 +399,14 @@ int mirt_cast_spheres(MirtScene* sc, const void* d_casts, int64_t n, void* d_hit
   return cast_spheres(sc, d_casts, n, d_hits, d_features, flags, (hipStream_t)stream);
 }
 
+// (include_ext/mirt_overlap.h)
+int mirt_overlap_boxes(MirtScene* sc, const void* d_boxes, int64_t n, int k, void* d_hits, uint32_t* d_counts, void* d_features, uint32_t flags,
+                       void* stream)
+{
+  MIRT_TRY(enter_scene(sc, "mirt_overlap_boxes"));
+  return overlap_boxes(sc, d_boxes, n, k, d_hits, d_counts, d_features, flags, (hipStream_t)stream);
+}
+
 size_t mirt_denoise_work_bytes(const MirtRenderParams* p) { return denoise_work_bytes(p); }
 
 int mirt_denoise(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, const void* d_features,

@@ -39,7 +39,6 @@ namespace {
 // count-only instance reaches within 64 VGPRs; the list takes two registers per key (DESIGN.md section 6s has the compiler's report).
 constexpr int contacts_waves(int cap) { return cap == 0 ? 8 : cap == 1 ? 7 : cap == 4 ? 6 : 5; }
 constexpr float SLACK = 3.814697265625e-06f;         // 2^-18 (mirt_closest.h, "Pruning")
-constexpr uint32_t KEY_ID = 0x3fffffffu;             // a key's low word: kind << 30 | id, or at capacity 1 a sphere's unit (both below 2^28: REF_OFFMASK)
 
 struct ContactsArgs {
   const float4* points;           // (q, R)
@@ -59,11 +58,6 @@ struct ContactsArgs {
   float coord_max;                // largest coordinate magnitude of the scene box
   int lds_depth;                  // stack entries kept in LDS (<= QUERY_STACK_LDS)
 };
-
-MIRT_DEV unsigned long long contact_key(float dist, uint32_t kind, uint32_t id)
-{
-  return ((unsigned long long)__float_as_uint(dist) << 32) | (kind << 30) | id;
-}
 
 template <int CAP>
 __global__ void __launch_bounds__(QUERY_BLOCK, contacts_waves(CAP)) contacts_kernel(const ContactsArgs a)

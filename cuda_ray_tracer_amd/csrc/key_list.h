@@ -1,4 +1,4 @@
-// A lane's sorted list of its CAP smallest 64-bit keys, in registers (multihit.hip, closest_multi.hip; DESIGN.md sections 6p, 6s).
+// A lane's sorted list of its CAP smallest 64-bit keys, in registers (multihit.hip, closest_multi.hip, overlap.hip; DESIGN.md sections 6p, 6s, 6w).
 // A key holds a non-negative float's bits in its high word, so that one unsigned compare is the whole order.  Every index is a
 // compile-time constant once the loops are unrolled: a runtime index would move the list to scratch.
 #ifndef MIRT_KEY_LIST_H
@@ -7,6 +7,15 @@
 namespace mirt {
 
 constexpr unsigned long long KEY_NONE = ~0ull;      // above every key: a distance's bits stay below +inf's
+
+// The contact key (closest_multi.hip, overlap.hip): a non-negative distance's bits high, kind << 30 | id low, so that one unsigned
+// compare is the (dist, kind, id) order of mirt_contacts.h.  The low word's id part -- at closest_multi.hip's capacity 1 a sphere's
+// unit -- stays below 2^28 (REF_OFFMASK).
+constexpr unsigned KEY_ID = 0x3fffffffu;
+__device__ __forceinline__ unsigned long long contact_key(float dist, unsigned kind, unsigned id)
+{
+  return ((unsigned long long)__float_as_uint(dist) << 32) | (kind << 30) | id;
+}
 
 template <int CAP>
 struct KeyList {

@@ -1,4 +1,4 @@
-"""What the query benches share (query_bench, light_bench, visibility_bench, indirect_bench, closest_bench, multihit_bench, contacts_bench):
+"""What the query benches share (query_bench, light_bench, visibility_bench, indirect_bench, closest_bench, multihit_bench, contacts_bench, spherecast_bench, overlap_bench):
 the timing loop, the scenes, the rays and rows they start from, and the JSON line they end with.  Imported by them, not run."""
 import argparse
 import json

@@ -939,6 +939,8 @@ from .contacts import closest_points_multi, count_within      # noqa: E402,F401
 from .spherecast import cast_spheres, pack_casts      # noqa: E402,F401
 # Box overlaps (include_ext/mirt_overlap.h): overlap.py holds that header's signature and calls
 from .overlap import overlap_boxes, count_overlaps, pack_boxes, voxel_rows, occupancy_grid      # noqa: E402,F401
+# Overlap lists (include_ext/mirt_overlap_list.h): overlap_list.py holds that header's signatures and calls
+from .overlap_list import list_offsets, list_offsets_work_bytes, overlap_list, overlap_lists, unpack_words, voxel_lists      # noqa: E402,F401
 
 
 def pack_rays(origins, dirs, tmax=float("inf")):

@@ -407,6 +407,21 @@ int mirt_overlap_boxes(MirtScene* sc, const void* d_boxes, int64_t n, int k, voi
   return overlap_boxes(sc, d_boxes, n, k, d_hits, d_counts, d_features, flags, (hipStream_t)stream);
 }
 
+// (include_ext/mirt_overlap_list.h)
+int64_t mirt_list_offsets_work_bytes(int64_t n) { return list_offsets_work_bytes(n); }
+
+int mirt_list_offsets(MirtScene* sc, const uint32_t* d_counts, int64_t n, int64_t* d_offsets, void* d_work, void* stream)
+{
+  MIRT_TRY(enter_scene(sc, "mirt_list_offsets"));
+  return list_offsets(sc, d_counts, n, d_offsets, d_work, (hipStream_t)stream);
+}
+
+int mirt_overlap_list(MirtScene* sc, const void* d_boxes, int64_t n, const int64_t* d_offsets, uint32_t* d_words, int64_t capacity, void* stream)
+{
+  MIRT_TRY(enter_scene(sc, "mirt_overlap_list"));
+  return overlap_list(sc, d_boxes, n, d_offsets, d_words, capacity, (hipStream_t)stream);
+}
+
 size_t mirt_denoise_work_bytes(const MirtRenderParams* p) { return denoise_work_bytes(p); }
 
 int mirt_denoise(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, const void* d_features,

@@ -10,12 +10,14 @@
 //   hierarchy_and_depth  karras_kernel: Karras 2012 hierarchy with the reference's index tie-break (lbvh_builder.cu:76-322);
 //                        tree_depth_kernel: the most internal nodes on a root-to-leaf path
 //   place_primitives     tri_scan_kernel<false>, scan_sums_kernel, tri_scan_kernel<true>: exclusive scan of the triangle flags in
-//                        sorted order (where each sorted leaf's record goes in the heap, which subtrees hold spheres only);
+//                        sorted order (where each sorted leaf's record goes in the heap, which subtrees hold spheres only;
+//                        the block scan itself: block_scan.h, shared with overlap_list.hip);
 //                        scatter_prims_kernel: the records into the heap in that order (neighbours in space, neighbours in memory)
 //   refit_and_pack       refit_pack_kernel: bottom-up boxes (lbvh_builder.cu:324-387, with the missing release/acquire added)
 //                        and 64-byte two-child node records for the traversal kernel
 //   pack_quantised       pack_qnodes_kernel, pack_wnodes_kernel: the 32-byte and the wide records on the scene-bounds grid
 #include "scene_dev.h"
+#include "block_scan.h"
 
 #include <algorithm>
 #include <utility>
@@ -34,24 +36,6 @@ void launch_blocks(void (*kernel)(P...), int blocks, hipStream_t stream, A&&... 
 }
 template <class K, class... A>
 void launch_items(K kernel, long long items, hipStream_t stream, A&&... args) { launch_blocks(kernel, item_blocks(items), stream, args...); }
-
-// exclusive scan of one value per thread over the block; `total` (nullable) receives the sum
-MIRT_DEV uint32_t block_exclusive_scan(uint32_t v, uint32_t* sh /* [BLOCK] */, uint32_t* total)
-{
-  const int tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (int o = 1; o < BLOCK; o <<= 1) {
-    const uint32_t x = (tid >= o) ? sh[tid - o] : 0;
-    __syncthreads();
-    sh[tid] += x;
-    __syncthreads();
-  }
-  const uint32_t incl = sh[tid];
-  if (total) *total = sh[BLOCK - 1];
-  __syncthreads();
-  return incl - v;
-}
 
 struct Box { float xmin, xmax, ymin, ymax, zmin, zmax; };
 
@@ -203,7 +187,7 @@ __global__ void __launch_bounds__(BLOCK) radix_pass_kernel(const uint32_t* __res
     return;
   }
   // exclusive scan of the 256 digit totals (every block repeats it: 256 values)
-  const uint32_t off = block_exclusive_scan(totals[tid], dbase, nullptr) + offsets[(size_t)tid * nblocks + blockIdx.x];
+  const uint32_t off = block_exclusive_scan<BLOCK>(totals[tid], dbase, nullptr) + offsets[(size_t)tid * nblocks + blockIdx.x];
   wcnt[0][tid] = off; wcnt[1][tid] = off + c0; wcnt[2][tid] = off + c0 + c1; wcnt[3][tid] = off + c0 + c1 + c2;
   __syncthreads();
 #pragma unroll
@@ -229,7 +213,7 @@ __global__ void __launch_bounds__(BLOCK) row_scan_kernel(uint32_t* __restrict__ 
   const int lo = tid * chunk, hi = min(lo + chunk, nblocks);
   uint32_t s = 0;
   for (int i = lo; i < hi; ++i) s += row[i];
-  uint32_t run = block_exclusive_scan(s, sums, nullptr);
+  uint32_t run = block_exclusive_scan<BLOCK>(s, sums, nullptr);
   if (tid == BLOCK - 1) totals[blockIdx.x] = run + s;
   for (int i = lo; i < hi; ++i) { const uint32_t v = row[i]; row[i] = run; run += v; }
 }
@@ -321,7 +305,7 @@ __global__ void __launch_bounds__(BLOCK) tri_scan_kernel(int n, const uint32_t* 
     s += f[k];
   }
   uint32_t total;
-  uint32_t run = block_exclusive_scan(s, sh, &total);
+  uint32_t run = block_exclusive_scan<BLOCK>(s, sh, &total);
   if (!WRITE) { if (threadIdx.x == 0) block_sums[blockIdx.x] = total; return; }
   run += block_sums[blockIdx.x];                // exclusive prefix of the blocks before this one
 #pragma unroll
@@ -341,7 +325,7 @@ __global__ void __launch_bounds__(BLOCK) scan_sums_kernel(uint32_t* __restrict__
     const int i = b0 + threadIdx.x;
     const uint32_t v = (i < nb) ? block_sums[i] : 0u;
     uint32_t total;
-    const uint32_t ex = block_exclusive_scan(v, sh, &total);
+    const uint32_t ex = block_exclusive_scan<BLOCK>(v, sh, &total);
     if (i < nb) block_sums[i] = carry + ex;
     carry += total;
   }

@@ -27,7 +27,7 @@ inline GroupLaunch group_launch(long long n, int lanes_per_row, int cached_block
   return g;
 }
 
-// A kernel with one lane per row (query.hip, closest.hip, closest_multi.hip, spherecast.hip, overlap.hip, multihit.hip): as many blocks as n rows need, at most cached_blocks.
+// A kernel with one lane per row (query.hip, closest.hip, closest_multi.hip, spherecast.hip, overlap.hip, overlap_list.hip, multihit.hip): as many blocks as n rows need, at most cached_blocks.
 inline int row_launch(long long n, int cached_blocks)
 {
   const long long want = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;

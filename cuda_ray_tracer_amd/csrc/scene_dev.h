@@ -277,6 +277,7 @@ struct MirtScene {
   int contacts_blocks[4] = {0, 0, 0, 0};   // ... and of the contact kernel's instances (closest_multi.hip: capacity 0, 1, 4, 8)
   int spherecast_blocks[2] = {0, 0};       // ... and of the sphere-cast kernel's instances (spherecast.hip: first contact, any contact)
   int overlap_blocks[5] = {0, 0, 0, 0, 0}; // ... and of the box-overlap kernel's instances (overlap.hip: count, any, capacity 1, 4, 8)
+  int overlap_list_blocks = 0;             // ... and of the overlap-list fill kernel (overlap_list.hip)
   bool updated = false;                    // geometry updated in place since the last build (update.hip): mirt_camera_rays waits for the build like every other call
   // Shading values updated in place (update_shading.hip).  The three facts above are prim_flags | host_flags (MAT_* bits,
   // material_flags.h), by source: the primitives' materials -- after a material update known only to the device, until
@@ -348,6 +349,10 @@ int cast_spheres(MirtScene* sc, const void* d_casts, int64_t n, void* d_hits, vo
 // overlap.hip
 int overlap_boxes(MirtScene* sc, const void* d_boxes, int64_t n, int k, void* d_hits, uint32_t* d_counts, void* d_features, uint32_t flags,
                   hipStream_t stream);
+// overlap_list.hip
+int64_t list_offsets_work_bytes(int64_t n);
+int list_offsets(MirtScene* sc, const uint32_t* d_counts, int64_t n, int64_t* d_offsets, void* d_work, hipStream_t stream);
+int overlap_list(MirtScene* sc, const void* d_boxes, int64_t n, const int64_t* d_offsets, uint32_t* d_words, int64_t capacity, hipStream_t stream);
 // multihit.hip
 int trace_rays_multi(MirtScene* sc, const void* d_rays, int64_t num_rays, int k, void* d_hits, uint32_t* d_counts, uint32_t flags, hipStream_t stream);
 // denoise.hip
@@ -400,7 +405,7 @@ hipError_t persistent_grid_blocks(int device, K kernel, int block, int per_cu_fa
   return hipSuccess;
 }
 
-// The query kernels' host side (query.hip, light.hip, visibility.hip, indirect.hip, closest.hip, closest_multi.hip, spherecast.hip, overlap.hip, multihit.hip; launch arithmetic: query_launch.h).
+// The query kernels' host side (query.hip, light.hip, visibility.hip, indirect.hip, closest.hip, closest_multi.hip, spherecast.hip, overlap.hip, overlap_list.hip, multihit.hip; launch arithmetic: query_launch.h).
 // Stack entries their walk keeps in LDS: the compiled size, unless the option names a smaller one (tests force the spill path).
 inline int query_lds_depth(const MirtScene* sc)
 {

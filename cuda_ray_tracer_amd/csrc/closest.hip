@@ -26,7 +26,6 @@ namespace {
 
 // the query kernels' budget: 64 VGPRs, 8 waves per SIMD; QUERY_STACK_LDS x 4 B x 64 lanes = 5 KiB of LDS per wave
 constexpr int CWAVES_PER_SIMD = 8;
-constexpr float SLACK = 3.814697265625e-06f;         // 2^-18 (mirt_closest.h, "Pruning")
 
 struct ClosestArgs {
   const float4* points;           // (q, R)
@@ -68,7 +67,7 @@ __global__ void __launch_bounds__(QUERY_BLOCK, CWAVES_PER_SIMD) closest_points_k
       }
     }
     if (live && a.root_ref != REF_NONE) {
-      const float sigma = (fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z)) + a.coord_max) * SLACK;
+      const float sigma = row_sigma(largest_abs(q), a.coord_max);
       float reach = best + sigma;
       float bound2 = reach * reach;      // a box farther than this (squared) holds nothing that wins or ties
       uint32_t cur = a.root_ref;
@@ -87,15 +86,8 @@ __global__ void __launch_bounds__(QUERY_BLOCK, CWAVES_PER_SIMD) closest_points_k
             dist = fabsf(length(q - mk3(s.x, s.y, s.z)) - s.w);
           }
           bool better = dist < best;
-          if (dist == best && (plane_id >= 0 || refbest != REF_NONE)) {
-            // a tie with the winner: (kind, id) decides -- a primitive before a plane, a sphere before a triangle, the lower index
-            if (plane_id >= 0 || (cur & REF_TRI) != (refbest & REF_TRI)) {
-              better = plane_id >= 0 || !(cur & REF_TRI);
-            } else {
-              if (!(cur & REF_TRI)) id = a.unit_prim[(cur & REF_OFFMASK) - a.prim_base16] & 0x7fffffffu;
-              better = id < (a.unit_prim[(refbest & REF_OFFMASK) - a.prim_base16] & 0x7fffffffu);
-            }
-          }
+          // (a tie with the winner: (kind, id) decides)
+          if (dist == best && (plane_id >= 0 || refbest != REF_NONE)) better = wins_tie(cur, id, plane_id, refbest, a.unit_prim, a.prim_base16);
           if (better) {
             best = dist; refbest = cur; plane_id = -1;
             reach = best + sigma;
@@ -126,7 +118,9 @@ __global__ void __launch_bounds__(QUERY_BLOCK, CWAVES_PER_SIMD) closest_points_k
         }
       }
     }
-    // the winner's record: its point and normal by the header's operations (the loop kept the distance only)
+    // the winner's record: its point and normal by the header's operations (the loop kept the distance only).  The three formulas
+    // are closest_multi.hip's and overlap.hip's, written out here too: through one function they move 938 of this kernel's 1039
+    // instruction lines
     float t = -1.0f;
     uint32_t kind = MIRT_HIT_NONE, id = 0u;
     f3 P = mk3(0.0f, 0.0f, 0.0f), n = P;
@@ -175,36 +169,16 @@ __global__ void __launch_bounds__(QUERY_BLOCK, CWAVES_PER_SIMD) closest_points_k
 
 int closest_points(MirtScene* sc, const void* d_points, int64_t n, void* d_hits, void* d_features, uint32_t flags, hipStream_t stream)
 {
-  const char* const who = "mirt_closest_points";
-  if (flags != 0u) { set_error(std::string(who) + ": unknown flag bits"); return MIRT_ERR_ARG; }
-  if (n < 0) { set_error(std::string(who) + ": negative n"); return MIRT_ERR_ARG; }
-  if (n > 0 && (!d_points || !d_hits)) { set_error(std::string(who) + ": null buffer"); return MIRT_ERR_ARG; }
-  if (!is_aligned(16, (const char*)d_points, (const char*)d_features) || !is_aligned(4, (const char*)d_hits)) {
-    set_error(std::string(who) + ": d_points and d_features must be 16-byte aligned, d_hits 4-byte aligned"); return MIRT_ERR_ARG;
-  }
-  const size_t rows = (size_t)n;
-  if (n > 0 && (overlaps(d_hits, 24 * rows, d_points, 16 * rows) ||
-                (d_features && (overlaps(d_features, 32 * rows, d_points, 16 * rows) || overlaps(d_features, 32 * rows, d_hits, 24 * rows))))) {
-    set_error(std::string(who) + ": d_hits and d_features must not overlap d_points or each other"); return MIRT_ERR_ARG;
-  }
-  if (!sc->built) { set_error(std::string(who) + ": call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
-  if (n == 0) return MIRT_OK;
-  const int grid = query_grid_blocks(sc, closest_points_kernel, CWAVES_PER_SIMD, &sc->closest_blocks);
+  bool go = false;
+  const int rc = check_closest_points(d_points, n, d_hits, d_features, flags, sc->built, &go);
+  if (rc != MIRT_OK || !go) return rc;
   ClosestArgs q;
   q.points = reinterpret_cast<const float4*>(d_points);
   q.hits = reinterpret_cast<uint32_t*>(d_hits);
   q.features = reinterpret_cast<float4*>(d_features);
   q.n = n;
-  q.nodes = sc->nodes; q.unit_prim = sc->unit_prim;
-  q.tri_verts = sc->tri_verts;
-  q.planes = sc->planes; q.num_planes = sc->d.num_planes;
-  q.root_ref = sc->root_ref; q.prim_base16 = sc->prim_base / 16u;
-  q.coord_max = sc->coord_max;
-  q.lds_depth = query_lds_depth(sc);
-  const int blocks = row_launch(n, grid);
-  hipLaunchKernelGGL(closest_points_kernel, dim3(blocks), dim3(QUERY_BLOCK), 0, stream, q);
-  MIRT_HIP(hipGetLastError());
-  return MIRT_OK;
+  fill_scene_args(q, sc);
+  return launch_rows(sc, closest_points_kernel, CWAVES_PER_SIMD, &sc->closest_blocks, n, q, stream);
 }
 
 } // namespace mirt

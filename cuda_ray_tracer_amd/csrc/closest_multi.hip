@@ -38,7 +38,6 @@ namespace {
 // Waves per SIMD an instance is compiled for: 8 is what the LDS stack allows (20 KiB per block, 8 blocks per CU) and what the
 // count-only instance reaches within 64 VGPRs; the list takes two registers per key (DESIGN.md section 6s has the compiler's report).
 constexpr int contacts_waves(int cap) { return cap == 0 ? 8 : cap == 1 ? 7 : cap == 4 ? 6 : 5; }
-constexpr float SLACK = 3.814697265625e-06f;         // 2^-18 (mirt_closest.h, "Pruning")
 
 struct ContactsArgs {
   const float4* points;           // (q, R)
@@ -105,7 +104,7 @@ __global__ void __launch_bounds__(QUERY_BLOCK, contacts_waves(CAP)) contacts_ker
       }
     }
     if (live && a.root_ref != REF_NONE) {
-      const float sigma = (fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z)) + a.coord_max) * SLACK;
+      const float sigma = row_sigma(largest_abs(q), a.coord_max);
       float reach = B + sigma;
       float bound2 = reach * reach;      // a box farther than this (squared) holds nothing that enters the answer
       uint32_t cur = a.root_ref;
@@ -160,7 +159,9 @@ __global__ void __launch_bounds__(QUERY_BLOCK, contacts_waves(CAP)) contacts_ker
     }
     if (a.counts) a.counts[i] = count;
     if (CAP > 0) {
-      // the k records, nearest first: each key's point and normal by mirt_closest.h's operations (the loop kept the distance only)
+      // the k records, nearest first: each key's point and normal by mirt_closest.h's operations (the loop kept the distance only).
+      // overlap.hip has the same loop, written out in both: as one function it moves capacity 1, 4 and 8 here (995, 606 and 1262
+      // instruction lines), and capacity 8 was then up to 1.6 % slower, more than the parent's run spread
       for (int j = a.k; j < CAP; ++j) best.pop_front();      // (the keys of 0 in front of a list with k below CAP)
       uint32_t* h = a.hits + 6 * (i * a.k);
       float4* f = a.features ? a.features + 2 * (i * a.k) : nullptr;
@@ -205,44 +206,14 @@ __global__ void __launch_bounds__(QUERY_BLOCK, contacts_waves(CAP)) contacts_ker
   }
 }
 
-template <int CAP>
-int launch(MirtScene* sc, const ContactsArgs& q, int* cache, hipStream_t stream)
-{
-  const int grid = query_grid_blocks(sc, contacts_kernel<CAP>, contacts_waves(CAP), cache);
-  const int blocks = row_launch(q.n, grid);
-  hipLaunchKernelGGL(contacts_kernel<CAP>, dim3(blocks), dim3(QUERY_BLOCK), 0, stream, q);
-  MIRT_HIP(hipGetLastError());
-  return MIRT_OK;
-}
-
 } // namespace
 
 int closest_points_multi(MirtScene* sc, const void* d_points, int64_t n, int k, void* d_hits, uint32_t* d_counts, void* d_features, uint32_t flags,
                          hipStream_t stream)
 {
-  const char* const who = "mirt_closest_points_multi";
-  if (flags != 0u) { set_error(std::string(who) + ": unknown flag bits"); return MIRT_ERR_ARG; }
-  if (n < 0) { set_error(std::string(who) + ": negative n"); return MIRT_ERR_ARG; }
-  if (k < 0 || k > MIRT_CONTACTS_MAX_K) { set_error(std::string(who) + ": k must be 0 to MIRT_CONTACTS_MAX_K (8)"); return MIRT_ERR_ARG; }
-  if (n > 0 && (!d_points || (k > 0 && !d_hits) || (k == 0 && !d_counts))) {
-    set_error(std::string(who) + ": null buffer (d_points; d_hits unless k is 0; d_counts when k is 0)"); return MIRT_ERR_ARG;
-  }
-  if (!is_aligned(16, (const char*)d_points, (const char*)d_features) || !is_aligned(4, (const char*)d_hits, (const char*)d_counts)) {
-    set_error(std::string(who) + ": d_points and d_features must be 16-byte aligned, d_hits and d_counts 4-byte aligned"); return MIRT_ERR_ARG;
-  }
-  // (a range of no bytes -- k == 0, or a null pointer -- overlaps nothing)
-  const size_t rows = (size_t)n;
-  const void* const ptr[4] = {d_points, d_hits, d_counts, d_features};
-  const size_t bytes[4] = {16 * rows, d_hits ? 24 * rows * (size_t)k : 0, d_counts ? 4 * rows : 0, d_features ? 32 * rows * (size_t)k : 0};
-  for (int x = 0; x < 4; ++x) {
-    for (int y = x + 1; y < 4; ++y) {
-      if (bytes[x] && bytes[y] && overlaps(ptr[x], bytes[x], ptr[y], bytes[y])) {
-        set_error(std::string(who) + ": d_points, d_hits, d_counts and d_features must not overlap each other"); return MIRT_ERR_ARG;
-      }
-    }
-  }
-  if (!sc->built) { set_error(std::string(who) + ": call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
-  if (n == 0) return MIRT_OK;
+  bool go = false;
+  const int rc = check_closest_points_multi(d_points, n, k, d_hits, d_counts, d_features, flags, sc->built, &go);
+  if (rc != MIRT_OK || !go) return rc;
   ContactsArgs q;
   q.points = reinterpret_cast<const float4*>(d_points);
   q.hits = reinterpret_cast<uint32_t*>(d_hits);
@@ -250,17 +221,13 @@ int closest_points_multi(MirtScene* sc, const void* d_points, int64_t n, int k, 
   q.features = k > 0 ? reinterpret_cast<float4*>(d_features) : nullptr;
   q.n = n;
   q.k = k;
-  q.nodes = sc->nodes; q.unit_prim = sc->unit_prim;
-  q.spheres = sc->spheres; q.tris = sc->tris; q.tri_verts = sc->tri_verts;
-  q.planes = sc->planes; q.num_planes = sc->d.num_planes;
-  q.root_ref = sc->root_ref; q.prim_base16 = sc->prim_base / 16u;
-  q.coord_max = sc->coord_max;
-  q.lds_depth = query_lds_depth(sc);
-  // the smallest instance that holds k (occupancy is per kernel: a cached grid size each)
-  if (k == 0) return launch<0>(sc, q, &sc->contacts_blocks[0], stream);
-  if (k == 1) return launch<1>(sc, q, &sc->contacts_blocks[1], stream);
-  if (k <= 4) return launch<4>(sc, q, &sc->contacts_blocks[2], stream);
-  return launch<8>(sc, q, &sc->contacts_blocks[3], stream);
+  fill_scene_args(q, sc);
+  q.spheres = sc->spheres; q.tris = sc->tris;
+  // the smallest instance that holds k
+  return with_capacity(k, [&](auto cap, int slot) {
+    constexpr int CAP = decltype(cap)::value;
+    return launch_rows(sc, contacts_kernel<CAP>, contacts_waves(CAP), &sc->contacts_blocks[slot], n, q, stream);
+  });
 }
 
 } // namespace mirt

@@ -2,6 +2,10 @@
 // rewritten around the POD structs of include/mirt.h.  Same grammar, same defaults, same arithmetic
 // (fp32, one rounding per operation; the library is built with -ffp-contract=off).
 #include "host_scene.h"
+#include "../../include/mirt_multihit.h"
+#include "../../include_ext/mirt_contacts.h"
+#include "../../include_ext/mirt_overlap.h"
+#include "../../include_ext/mirt_spherecast.h"
 
 #include <cmath>
 #include <cstdio>
@@ -68,6 +72,122 @@ int check_table_query(const char* who, const char* mask_name, const void* d_feat
   if (!built) { set_error(w + "call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
   *go = n > 0;
   return MIRT_OK;
+}
+
+bool any_overlap(const ByteRange* r, int count)
+{
+  for (int x = 0; x < count; ++x) {
+    for (int y = x + 1; y < count; ++y) {
+      if (r[x].bytes && r[y].bytes && overlaps(r[x].ptr, r[x].bytes, r[y].ptr, r[y].bytes)) return true;
+    }
+  }
+  return false;
+}
+
+int check_row_query(const char* who, uint32_t unknown_flags, int64_t n, const char* n_name, std::initializer_list<ArgRule> rules,
+                    std::initializer_list<QueryBuf> bufs, const char* null_msg, const char* align_msg, const char* overlap_msg, bool built, bool* go)
+{
+  *go = false;
+  const std::string w = std::string(who) + ": ";
+  if (unknown_flags != 0u) { set_error(w + "unknown flag bits"); return MIRT_ERR_ARG; }
+  if (n < 0) { set_error(w + "negative " + n_name); return MIRT_ERR_ARG; }
+  for (const ArgRule& r : rules) {
+    if (r.bad) { set_error(w + r.msg); return MIRT_ERR_ARG; }
+  }
+  for (const QueryBuf& b : bufs) {
+    if (b.required && !b.ptr) { set_error(w + null_msg); return MIRT_ERR_ARG; }
+  }
+  for (const QueryBuf& b : bufs) {
+    if (!is_aligned(b.align, (const char*)b.ptr)) { set_error(w + align_msg); return MIRT_ERR_ARG; }
+  }
+  ByteRange ranges[8];
+  int count = 0;
+  for (const QueryBuf& b : bufs) ranges[count++] = ByteRange{b.ptr, b.ptr ? b.bytes : 0};
+  if (any_overlap(ranges, count)) { set_error(w + overlap_msg); return MIRT_ERR_ARG; }
+  if (!built) { set_error(w + "call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
+  *go = n > 0;
+  return MIRT_OK;
+}
+
+int check_closest_points(const void* d_points, int64_t n, const void* d_hits, const void* d_features, uint32_t flags, bool built, bool* go)
+{
+  const size_t rows = (size_t)n;
+  return check_row_query("mirt_closest_points", flags, n, "n", {},
+                         {{d_points, 16 * rows, 16, n > 0}, {d_hits, 24 * rows, 4, n > 0}, {d_features, 32 * rows, 16, false}}, "null buffer",
+                         "d_points and d_features must be 16-byte aligned, d_hits 4-byte aligned",
+                         "d_hits and d_features must not overlap d_points or each other", built, go);
+}
+
+int check_closest_points_multi(const void* d_points, int64_t n, int k, const void* d_hits, const void* d_counts, const void* d_features, uint32_t flags,
+                               bool built, bool* go)
+{
+  // (a range of no bytes -- k == 0, or a null pointer -- overlaps nothing)
+  const size_t rows = (size_t)n, per_row = k > 0 ? (size_t)k : 0;
+  return check_row_query("mirt_closest_points_multi", flags, n, "n", {{k < 0 || k > MIRT_CONTACTS_MAX_K, "k must be 0 to MIRT_CONTACTS_MAX_K (8)"}},
+                         {{d_points, 16 * rows, 16, n > 0}, {d_hits, 24 * rows * per_row, 4, n > 0 && k > 0}, {d_counts, 4 * rows, 4, n > 0 && k == 0},
+                          {d_features, 32 * rows * per_row, 16, false}},
+                         "null buffer (d_points; d_hits unless k is 0; d_counts when k is 0)",
+                         "d_points and d_features must be 16-byte aligned, d_hits and d_counts 4-byte aligned",
+                         "d_points, d_hits, d_counts and d_features must not overlap each other", built, go);
+}
+
+int check_cast_spheres(const void* d_casts, int64_t n, const void* d_hits, const void* d_features, uint32_t flags, bool built, bool* go)
+{
+  const size_t rows = (size_t)n;
+  return check_row_query("mirt_cast_spheres", flags & ~MIRT_CAST_ANY_HIT, n, "n", {},
+                         {{d_casts, 32 * rows, 16, n > 0}, {d_hits, 24 * rows, 4, n > 0}, {d_features, 32 * rows, 16, false}}, "null buffer",
+                         "d_casts and d_features must be 16-byte aligned, d_hits 4-byte aligned",
+                         "d_hits and d_features must not overlap d_casts or each other", built, go);      // (built also with n == 0: the header)
+}
+
+int check_overlap_boxes(const void* d_boxes, int64_t n, int k, const void* d_hits, const void* d_counts, const void* d_features, uint32_t flags,
+                        bool built, bool* go)
+{
+  // (a range of no bytes -- k == 0, or a null pointer -- overlaps nothing)
+  const size_t rows = (size_t)n, per_row = k > 0 ? (size_t)k : 0;
+  return check_row_query("mirt_overlap_boxes", flags & ~MIRT_OVERLAP_ANY, n, "n",
+                         {{k < 0 || k > MIRT_OVERLAP_MAX_K, "k must be 0 to MIRT_OVERLAP_MAX_K (8)"},
+                          {(flags & MIRT_OVERLAP_ANY) != 0u && k != 0, "MIRT_OVERLAP_ANY needs k == 0"}},
+                         {{d_boxes, 32 * rows, 16, n > 0}, {d_hits, 24 * rows * per_row, 4, n > 0 && k > 0}, {d_counts, 4 * rows, 4, n > 0 && k == 0},
+                          {d_features, 32 * rows * per_row, 16, false}},
+                         "null buffer (d_boxes; d_hits unless k is 0; d_counts when k is 0)",
+                         "d_boxes and d_features must be 16-byte aligned, d_hits and d_counts 4-byte aligned",
+                         "d_boxes, d_hits, d_counts and d_features must not overlap each other", built, go);
+}
+
+int check_list_offsets(const void* d_counts, int64_t n, const void* d_offsets, const void* d_work, size_t work_bytes, bool* go)
+{
+  const size_t rows = n > 0 ? (size_t)n : 0;
+  // (d_work is looked at only by a call that uses it)
+  return check_row_query("mirt_list_offsets", 0u, n, "n", {{n > (1ll << 40), "n above 2^40"}},
+                         {{d_offsets, 8 * (rows + 1), 8, true}, {d_counts, 4 * rows, 4, n > 0}, {work_bytes ? d_work : nullptr, work_bytes, 8, work_bytes > 0}},
+                         "null buffer (d_offsets; d_counts when n > 0; d_work when mirt_list_offsets_work_bytes(n) > 0)",
+                         "d_counts must be 4-byte aligned, d_offsets and d_work 8-byte aligned", "d_counts, d_offsets and d_work must not overlap each other",
+                         true, go);
+}
+
+int check_overlap_list(const void* d_boxes, int64_t n, const void* d_offsets, const void* d_words, int64_t capacity, bool built, bool* go)
+{
+  // (a range of no bytes -- n == 0, capacity == 0 -- overlaps nothing)
+  const size_t rows = (size_t)n;
+  const int rc = check_row_query("mirt_overlap_list", 0u, n, "n", {{capacity < 0, "negative capacity"}},
+                                 {{d_boxes, 32 * rows, 16, n > 0}, {d_offsets, n > 0 ? 8 * (rows + 1) : 0, 8, n > 0}, {d_words, 4 * (size_t)capacity, 4, capacity > 0}},
+                                 "null buffer (d_boxes and d_offsets when n > 0; d_words when capacity > 0)",
+                                 "d_boxes must be 16-byte aligned, d_offsets 8-byte aligned, d_words 4-byte aligned",
+                                 "d_boxes, d_offsets and d_words must not overlap each other", built, go);
+  *go = *go && capacity > 0;      // (no row, or no word any row could write)
+  return rc;
+}
+
+int check_trace_rays_multi(const void* d_rays, int64_t num_rays, int k, const void* d_hits, const void* d_counts, uint32_t flags, bool built, bool* go)
+{
+  const size_t rows = (size_t)num_rays, per_row = k > 0 ? (size_t)k : 0;
+  return check_row_query("mirt_trace_rays_multi", flags, num_rays, "num_rays", {{k < 0 || k > MIRT_MULTIHIT_MAX_K, "k must be 0 to MIRT_MULTIHIT_MAX_K (8)"}},
+                         {{d_rays, 32 * rows, 16, num_rays > 0}, {d_hits, 24 * rows * per_row, 4, num_rays > 0 && k > 0},
+                          {d_counts, 4 * rows, 4, num_rays > 0 && k == 0}},
+                         "null buffer (d_rays; d_hits unless k is 0; d_counts when k is 0)",
+                         "d_rays must be 16-byte aligned, d_hits and d_counts 4-byte aligned", "d_hits and d_counts must not overlap d_rays or each other",
+                         built, go);
 }
 
 namespace {

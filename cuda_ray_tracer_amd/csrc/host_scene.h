@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 #include <istream>
 #include <string>
 #include <vector>
@@ -38,6 +39,32 @@ int check_frame(const char* who, const MirtRenderParams* p, int64_t npix, bool* 
 // tree.  MIRT_OK with *go = false: nothing to do (n == 0).
 int check_table_query(const char* who, const char* mask_name, const void* d_features, int64_t n, const void* d_dirs, int num_dirs, const void* d_rot,
                       float radius, const void* d_out_f32, const uint64_t* d_mask, uint32_t flags, bool built, bool* go);
+
+// do any two of the byte ranges share a byte (a range of no bytes overlaps nothing)
+struct ByteRange { const void* ptr; size_t bytes; };
+bool any_overlap(const ByteRange* ranges, int count);
+
+// The arguments of a query with one lane per row.  A buffer as its entry point describes it: the bytes the call reads or writes
+// there (a null pointer's count as none), the alignment, and whether this call needs it.  A rule is an argument test of the entry
+// point's own with its message.
+struct QueryBuf { const void* ptr; size_t bytes; size_t align; bool required; };
+struct ArgRule { bool bad; const char* msg; };
+// The checks in the order every row query makes them -- unknown flag bits, a negative n (n_name: the parameter's own name), the
+// rules, a required buffer that is null, alignment, overlap, the scene's tree (built) -- each with who + ": " in front of its
+// message.  MIRT_OK with *go = false: nothing to do (n == 0).
+int check_row_query(const char* who, uint32_t unknown_flags, int64_t n, const char* n_name, std::initializer_list<ArgRule> rules,
+                    std::initializer_list<QueryBuf> bufs, const char* null_msg, const char* align_msg, const char* overlap_msg, bool built, bool* go);
+// ... of the seven entry points (closest.hip, closest_multi.hip, spherecast.hip, overlap.hip, overlap_list.hip, multihit.hip)
+int check_closest_points(const void* d_points, int64_t n, const void* d_hits, const void* d_features, uint32_t flags, bool built, bool* go);
+int check_closest_points_multi(const void* d_points, int64_t n, int k, const void* d_hits, const void* d_counts, const void* d_features, uint32_t flags,
+                               bool built, bool* go);
+int check_cast_spheres(const void* d_casts, int64_t n, const void* d_hits, const void* d_features, uint32_t flags, bool built, bool* go);
+int check_overlap_boxes(const void* d_boxes, int64_t n, int k, const void* d_hits, const void* d_counts, const void* d_features, uint32_t flags,
+                        bool built, bool* go);
+// (work_bytes: mirt_list_offsets_work_bytes(n); no scene is read, so there is no `built`)
+int check_list_offsets(const void* d_counts, int64_t n, const void* d_offsets, const void* d_work, size_t work_bytes, bool* go);
+int check_overlap_list(const void* d_boxes, int64_t n, const void* d_offsets, const void* d_words, int64_t capacity, bool built, bool* go);
+int check_trace_rays_multi(const void* d_rays, int64_t num_rays, int k, const void* d_hits, const void* d_counts, uint32_t flags, bool built, bool* go);
 
 class HostScene {
 public:

@@ -151,52 +151,25 @@ __global__ void __launch_bounds__(QUERY_BLOCK, multihit_waves(CAP)) multihit_ker
   }
 }
 
-template <int CAP>
-int launch(MirtScene* sc, const MultiArgs& q, int* cache, hipStream_t stream)
-{
-  const int grid = query_grid_blocks(sc, multihit_kernel<CAP>, multihit_waves(CAP), cache);
-  const int blocks = row_launch(q.num_rays, grid);
-  hipLaunchKernelGGL(multihit_kernel<CAP>, dim3(blocks), dim3(QUERY_BLOCK), 0, stream, q);
-  MIRT_HIP(hipGetLastError());
-  return MIRT_OK;
-}
-
 } // namespace
 
 int trace_rays_multi(MirtScene* sc, const void* d_rays, int64_t num_rays, int k, void* d_hits, uint32_t* d_counts, uint32_t flags, hipStream_t stream)
 {
-  const char* const who = "mirt_trace_rays_multi";
-  if (flags != 0u) { set_error(std::string(who) + ": unknown flag bits"); return MIRT_ERR_ARG; }
-  if (num_rays < 0) { set_error(std::string(who) + ": negative num_rays"); return MIRT_ERR_ARG; }
-  if (k < 0 || k > MIRT_MULTIHIT_MAX_K) { set_error(std::string(who) + ": k must be 0 to MIRT_MULTIHIT_MAX_K (8)"); return MIRT_ERR_ARG; }
-  if (num_rays > 0 && (!d_rays || (k > 0 && !d_hits) || (k == 0 && !d_counts))) {
-    set_error(std::string(who) + ": null buffer (d_rays; d_hits unless k is 0; d_counts when k is 0)"); return MIRT_ERR_ARG;
-  }
-  if (!is_aligned(16, (const char*)d_rays) || !is_aligned(4, (const char*)d_hits, (const char*)d_counts)) {
-    set_error(std::string(who) + ": d_rays must be 16-byte aligned, d_hits and d_counts 4-byte aligned"); return MIRT_ERR_ARG;
-  }
-  const size_t rows = (size_t)num_rays, hit_bytes = 24 * rows * (size_t)k;
-  if (num_rays > 0 && ((d_hits && hit_bytes && overlaps(d_hits, hit_bytes, d_rays, 32 * rows)) ||
-                       (d_counts && (overlaps(d_counts, 4 * rows, d_rays, 32 * rows) || (d_hits && hit_bytes && overlaps(d_counts, 4 * rows, d_hits, hit_bytes)))))) {
-    set_error(std::string(who) + ": d_hits and d_counts must not overlap d_rays or each other"); return MIRT_ERR_ARG;
-  }
-  if (!sc->built) { set_error(std::string(who) + ": call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
-  if (num_rays == 0) return MIRT_OK;
+  bool go = false;
+  const int rc = check_trace_rays_multi(d_rays, num_rays, k, d_hits, d_counts, flags, sc->built, &go);
+  if (rc != MIRT_OK || !go) return rc;
   MultiArgs q;
   q.rays = reinterpret_cast<const float4*>(d_rays);
   q.hits = reinterpret_cast<uint32_t*>(d_hits);
   q.counts = d_counts;
   q.num_rays = num_rays;
   q.k = k;
-  q.nodes = sc->nodes; q.unit_prim = sc->unit_prim;
-  q.planes = sc->planes; q.num_planes = sc->d.num_planes;
-  q.root_ref = sc->root_ref; q.prim_base16 = sc->prim_base / 16u;
-  q.lds_depth = query_lds_depth(sc);
-  // the smallest instance that holds k (occupancy is per kernel: a cached grid size each)
-  if (k == 0) return launch<0>(sc, q, &sc->multihit_blocks[0], stream);
-  if (k == 1) return launch<1>(sc, q, &sc->multihit_blocks[1], stream);
-  if (k <= 4) return launch<4>(sc, q, &sc->multihit_blocks[2], stream);
-  return launch<8>(sc, q, &sc->multihit_blocks[3], stream);
+  fill_walk_args(q, sc);
+  // the smallest instance that holds k
+  return with_capacity(k, [&](auto cap, int slot) {
+    constexpr int CAP = decltype(cap)::value;
+    return launch_rows(sc, multihit_kernel<CAP>, multihit_waves(CAP), &sc->multihit_blocks[slot], num_rays, q, stream);
+  });
 }
 
 } // namespace mirt

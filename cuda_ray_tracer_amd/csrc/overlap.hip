@@ -28,7 +28,6 @@
 #include "../../include_ext/mirt_overlap.h"
 
 #include <cmath>
-#include <string>
 
 namespace mirt {
 namespace {
@@ -90,7 +89,10 @@ __global__ void __launch_bounds__(QUERY_BLOCK, overlap_waves(CAP)) overlap_kerne
       }
     }
     if (live && a.root_ref != REF_NONE && !(ANY && count != 0u)) {
-      const float sigma = (fmaxf(max3(fabsf(lo.x), fabsf(lo.y), fabsf(lo.z)), max3(fabsf(hi.x), fabsf(hi.y), fabsf(hi.z))) + a.coord_max) * SLACK;
+      // The walk of overlap_walk.h (overlap_list.hip uses it), written out: as a call the count-only and the record instances run
+      // 0.8 to 1.8 % slower on the voxel grids of tools/overlap_bench.py, more than the parent's run spread.
+      // A change to the pruning or to the degenerate-triangle rule goes into both.
+      const float sigma = row_sigma(fmaxf(largest_abs(lo), largest_abs(hi)), a.coord_max);
       uint32_t cur = a.root_ref;
       int sp = 0;
       for (;;) {
@@ -194,46 +196,14 @@ __global__ void __launch_bounds__(QUERY_BLOCK, overlap_waves(CAP)) overlap_kerne
   }
 }
 
-template <int CAP, bool ANY>
-int launch(MirtScene* sc, const OverlapArgs& q, int* cache, hipStream_t stream)
-{
-  const int grid = query_grid_blocks(sc, overlap_kernel<CAP, ANY>, overlap_waves(CAP), cache);
-  const int blocks = row_launch(q.n, grid);
-  hipLaunchKernelGGL((overlap_kernel<CAP, ANY>), dim3(blocks), dim3(QUERY_BLOCK), 0, stream, q);
-  MIRT_HIP(hipGetLastError());
-  return MIRT_OK;
-}
-
 } // namespace
 
 int overlap_boxes(MirtScene* sc, const void* d_boxes, int64_t n, int k, void* d_hits, uint32_t* d_counts, void* d_features, uint32_t flags,
                   hipStream_t stream)
 {
-  const char* const who = "mirt_overlap_boxes";
-  if ((flags & ~MIRT_OVERLAP_ANY) != 0u) { set_error(std::string(who) + ": unknown flag bits"); return MIRT_ERR_ARG; }
-  if (n < 0) { set_error(std::string(who) + ": negative n"); return MIRT_ERR_ARG; }
-  if (k < 0 || k > MIRT_OVERLAP_MAX_K) { set_error(std::string(who) + ": k must be 0 to MIRT_OVERLAP_MAX_K (8)"); return MIRT_ERR_ARG; }
-  const bool any = (flags & MIRT_OVERLAP_ANY) != 0u;
-  if (any && k != 0) { set_error(std::string(who) + ": MIRT_OVERLAP_ANY needs k == 0"); return MIRT_ERR_ARG; }
-  if (n > 0 && (!d_boxes || (k > 0 && !d_hits) || (k == 0 && !d_counts))) {
-    set_error(std::string(who) + ": null buffer (d_boxes; d_hits unless k is 0; d_counts when k is 0)"); return MIRT_ERR_ARG;
-  }
-  if (!is_aligned(16, (const char*)d_boxes, (const char*)d_features) || !is_aligned(4, (const char*)d_hits, (const char*)d_counts)) {
-    set_error(std::string(who) + ": d_boxes and d_features must be 16-byte aligned, d_hits and d_counts 4-byte aligned"); return MIRT_ERR_ARG;
-  }
-  // (a range of no bytes -- k == 0, or a null pointer -- overlaps nothing)
-  const size_t rows = (size_t)n;
-  const void* const ptr[4] = {d_boxes, d_hits, d_counts, d_features};
-  const size_t bytes[4] = {32 * rows, d_hits ? 24 * rows * (size_t)k : 0, d_counts ? 4 * rows : 0, d_features ? 32 * rows * (size_t)k : 0};
-  for (int x = 0; x < 4; ++x) {
-    for (int y = x + 1; y < 4; ++y) {
-      if (bytes[x] && bytes[y] && overlaps(ptr[x], bytes[x], ptr[y], bytes[y])) {
-        set_error(std::string(who) + ": d_boxes, d_hits, d_counts and d_features must not overlap each other"); return MIRT_ERR_ARG;
-      }
-    }
-  }
-  if (!sc->built) { set_error(std::string(who) + ": call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
-  if (n == 0) return MIRT_OK;
+  bool go = false;
+  const int rc = check_overlap_boxes(d_boxes, n, k, d_hits, d_counts, d_features, flags, sc->built, &go);
+  if (rc != MIRT_OK || !go) return rc;
   OverlapArgs q;
   q.boxes = reinterpret_cast<const float4*>(d_boxes);
   q.hits = reinterpret_cast<uint32_t*>(d_hits);
@@ -241,18 +211,14 @@ int overlap_boxes(MirtScene* sc, const void* d_boxes, int64_t n, int k, void* d_
   q.features = k > 0 ? reinterpret_cast<float4*>(d_features) : nullptr;
   q.n = n;
   q.k = k;
-  q.nodes = sc->nodes; q.unit_prim = sc->unit_prim;
-  q.spheres = sc->spheres; q.tris = sc->tris; q.tri_verts = sc->tri_verts;
-  q.planes = sc->planes; q.num_planes = sc->d.num_planes;
-  q.root_ref = sc->root_ref; q.prim_base16 = sc->prim_base / 16u;
-  q.coord_max = sc->coord_max;
-  q.lds_depth = query_lds_depth(sc);
-  // the smallest instance that holds k (occupancy is per kernel: a cached grid size each)
-  if (any) return launch<0, true>(sc, q, &sc->overlap_blocks[1], stream);
-  if (k == 0) return launch<0, false>(sc, q, &sc->overlap_blocks[0], stream);
-  if (k == 1) return launch<1, false>(sc, q, &sc->overlap_blocks[2], stream);
-  if (k <= 4) return launch<4, false>(sc, q, &sc->overlap_blocks[3], stream);
-  return launch<8, false>(sc, q, &sc->overlap_blocks[4], stream);
+  fill_scene_args(q, sc);
+  q.spheres = sc->spheres; q.tris = sc->tris;
+  if (flags & MIRT_OVERLAP_ANY) return launch_rows(sc, overlap_kernel<0, true>, overlap_waves(0), &sc->overlap_blocks[1], n, q, stream);
+  // the smallest instance that holds k (overlap_blocks: count, any, capacity 1, 4, 8)
+  return with_capacity(k, [&](auto cap, int slot) {
+    constexpr int CAP = decltype(cap)::value;
+    return launch_rows(sc, overlap_kernel<CAP, false>, overlap_waves(CAP), &sc->overlap_blocks[slot ? slot + 1 : 0], n, q, stream);
+  });
 }
 
 } // namespace mirt

@@ -7,9 +7,9 @@
 //                           totals scanned by one block that loops over them with a carry; then every block again, writing
 //                           offsets[j] for its counts and, the block of the last count, offsets[n].  A batch of one tile is the
 //                           third launch alone.  Sums of the counts in index order: no order of arrival is observable.
-// overlap_list_kernel       overlap.hip's count-only walk -- the planes from scalar loads, the stack walk over the exact records,
-//                           left child first, the same sigma, stack and leaf tests (overlap_tests.h) and the same dist == dist
-//                           admission -- with a write cursor in place of the counter.  Left child first is what the ORDER of a
+// overlap_list_kernel       overlap.hip's walk (overlap_walk.h: the planes from scalar loads, the stack walk over the exact
+//                           records, left child first, sigma, the leaf tests of overlap_tests.h and the dist == dist admission)
+//                           with a write cursor in place of the counter.  Left child first is what the ORDER of a
 //                           row's words depends on: it is the scene's leaf order.  The cursor a lane carries across the walk is
 //                           a pointer to the row's next word and the room left in its segment [offsets[i], min(offsets[i + 1],
 //                           capacity)), read once per row: three registers where the count-only kernel has one, and still that
@@ -23,11 +23,10 @@
 #include "query_walk.h"
 #include "point_query.h"
 #include "block_scan.h"
-#include "overlap_tests.h"
+#include "overlap_walk.h"
 #include "../../include_ext/mirt_overlap_list.h"
 
 #include <cmath>
-#include <string>
 
 namespace mirt {
 namespace {
@@ -103,7 +102,22 @@ struct OverlapListArgs {
 // A row's cursor: where its next word goes and how many more its segment [beg, min(lim, capacity)) takes -- none if the segment
 // begins below 0, at or beyond the capacity or after its own end.  (A row admits fewer than 2^32 candidates, so a longer
 // segment's room may stop there.)
-struct Cursor { uint32_t* out; uint32_t room; };
+// It is the walk's action (overlap_walk.h): an admitted candidate's word kind << 30 | id goes to the cursor.
+struct Cursor {
+  uint32_t* out; uint32_t room;
+  const uint32_t* unit_prim; uint32_t prim_base16;
+  MIRT_DEV void emit(uint32_t word)
+  {
+    if (room) { *out++ = word; --room; }
+  }
+  MIRT_DEV void plane(float, uint32_t j) { emit(((uint32_t)MIRT_HIT_PLANE << 30) | j); }
+  MIRT_DEV bool leaf(float, uint32_t cur, uint32_t id)
+  {
+    if (!(cur & REF_TRI)) id = unit_prim[(cur & REF_OFFMASK) - prim_base16] & 0x7fffffffu;
+    emit(((cur & REF_TRI) ? ((uint32_t)MIRT_HIT_TRIANGLE << 30) : ((uint32_t)MIRT_HIT_SPHERE << 30)) | id);
+    return false;
+  }
+};
 MIRT_DEV Cursor row_cursor(const OverlapListArgs& a, long long i)
 {
   const long long beg = a.offsets[i], lim = a.offsets[i + 1];
@@ -111,11 +125,8 @@ MIRT_DEV Cursor row_cursor(const OverlapListArgs& a, long long i)
   Cursor c;
   c.room = (beg >= 0 && beg < end) ? (uint32_t)(end - beg > 0xffffffffll ? 0xffffffffll : end - beg) : 0u;
   c.out = a.words + (c.room ? beg : 0);
+  c.unit_prim = a.unit_prim; c.prim_base16 = a.prim_base16;
   return c;
-}
-MIRT_DEV void emit(Cursor& c, uint32_t word)
-{
-  if (c.room) { *c.out++ = word; --c.room; }
 }
 
 __global__ void __launch_bounds__(QUERY_BLOCK, LIST_WAVES) overlap_list_kernel(const OverlapListArgs a)
@@ -127,71 +138,12 @@ __global__ void __launch_bounds__(QUERY_BLOCK, LIST_WAVES) overlap_list_kernel(c
   const unsigned char* const heap = reinterpret_cast<const unsigned char*>(a.nodes);
   const ConstPlanes planes = const_planes(a.planes);
   for (long long i = (long long)blockIdx.x * QUERY_BLOCK + tid; i < a.n; i += stride) {
-    const float4 r0 = a.boxes[2 * i], r1 = a.boxes[2 * i + 1];
-    const f3 lo = mk3(r0.x, r0.y, r0.z), hi = mk3(r1.x, r1.y, r1.z);
-    // (x - x is 0 for a finite x and NaN for an infinity or a NaN)
-    const bool live = (lo.x - lo.x) == 0.0f && (lo.y - lo.y) == 0.0f && (lo.z - lo.z) == 0.0f && (hi.x - hi.x) == 0.0f && (hi.y - hi.y) == 0.0f &&
-                      (hi.z - hi.z) == 0.0f && lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z;
-    if (!live) continue;             // (a dead row writes nothing)
-    const f3 m = (lo + hi) * 0.5f, h = (hi - lo) * 0.5f;
+    const BoxRow b = box_row(a.boxes, i);
+    if (!b.live) continue;           // (a dead row writes nothing)
     Cursor at = row_cursor(a, i);
-    for (int j = 0; j < a.num_planes; ++j) {
-      const f3 N = normalize(mk3(planes[j].nx, planes[j].ny, planes[j].nz));
-      const float s = dot(N, m - mk3(planes[j].px, planes[j].py, planes[j].pz));
-      const float e = (h.x * fabsf(N.x) + h.y * fabsf(N.y)) + h.z * fabsf(N.z);
-      if (fabsf(s) <= e) emit(at, ((uint32_t)MIRT_HIT_PLANE << 30) | (uint32_t)j);      // (s is then no NaN, and dist = fabsf(s) is none)
-    }
+    at =overlap_planes(planes, a.num_planes, b.m, b.h, at);
     if (a.root_ref == REF_NONE) continue;
-    const float sigma = (fmaxf(max3(fabsf(lo.x), fabsf(lo.y), fabsf(lo.z)), max3(fabsf(hi.x), fabsf(hi.y), fabsf(hi.z))) + a.coord_max) * SLACK;
-    uint32_t cur = a.root_ref;
-    int sp = 0;
-    for (;;) {
-      const float4* rec = reinterpret_cast<const float4*>(heap + (cur << 4));
-      bool pop;
-      if (cur & REF_LEAF) {
-        float dist = 0.0f;
-        uint32_t id = 0u;
-        bool pass;
-        if (cur & REF_TRI) {
-          id = a.unit_prim[(cur & REF_OFFMASK) - a.prim_base16] & 0x7fffffffu;
-          const float4* v = a.tri_verts + 3 * (size_t)id;
-          const float4 pa = v[0], pb = v[1], pc = v[2];
-          const f3 ta = mk3(pa.x, pa.y, pa.z), tb = mk3(pb.x, pb.y, pb.z), tc = mk3(pc.x, pc.y, pc.z);
-          pass = triangle_overlaps(m, h, ta, tb, tc);
-          if (pass) {
-            // (the vertices are loaded again, through an id the compiler cannot see through, as in overlap.hip: section 6w)
-            asm volatile("" : "+v"(id));
-            dist = length(m - triangle_point(a.tri_verts, id, m));
-          }
-        } else {
-          const float4 s = rec[0];
-          const f3 c = mk3(s.x, s.y, s.z);
-          pass = sphere_overlaps(lo, hi, c, s.w);
-          if (pass) dist = fabsf(length(m - c) - s.w);
-        }
-        if (pass && dist == dist) {          // (a NaN dist is not admitted)
-          if (!(cur & REF_TRI)) id = a.unit_prim[(cur & REF_OFFMASK) - a.prim_base16] & 0x7fffffffu;
-          emit(at, ((cur & REF_TRI) ? ((uint32_t)MIRT_HIT_TRIANGLE << 30) : ((uint32_t)MIRT_HIT_SPHERE << 30)) | id);
-        }
-        pop = true;
-      } else {
-        const float4 b0 = rec[0], b1 = rec[1], b2 = rec[2];
-        const uint2 ch = *reinterpret_cast<const uint2*>(rec + 3);
-        // (hi + sigma and lo - sigma made here from a copy of sigma the compiler cannot see through, as in overlap.hip: section 6w)
-        float sg = sigma;
-        asm volatile("" : "+v"(sg));
-        const f3 los = mk3(lo.x - sg, lo.y - sg, lo.z - sg), his = mk3(hi.x + sg, hi.y + sg, hi.z + sg);
-        const bool hl = !(b0.x > his.x) && !(b0.y < los.x) && !(b0.z > his.y) && !(b0.w < los.y) && !(b1.x > his.z) && !(b1.y < los.z);
-        const bool hr = !(b1.z > his.x) && !(b1.w < los.x) && !(b2.x > his.y) && !(b2.y < los.y) && !(b2.z > his.z) && !(b2.w < los.z);
-        if (hl && hr) stack_push(lds_stack, spill, a.lds_depth, tid, sp, ch.y);
-        cur = hl ? ch.x : ch.y;
-        pop = !(hl || hr);
-      }
-      if (pop) {
-        if (sp == 0) break;
-        cur = stack_pop(lds_stack, spill, a.lds_depth, tid, sp);
-      }
-    }
+    overlap_walk(heap, a.unit_prim, a.tri_verts, a.prim_base16, a.root_ref, a.coord_max, a.lds_depth, lds_stack, spill, tid, b.lo, b.hi, b.m, b.h, at);
   }
 }
 
@@ -205,27 +157,13 @@ int64_t list_offsets_work_bytes(int64_t n)
 int list_offsets(MirtScene* sc, const uint32_t* d_counts, int64_t n, int64_t* d_offsets, void* d_work, hipStream_t stream)
 {
   (void)sc;      // (the device and the error conventions: api.hip has made the device current)
-  const char* const who = "mirt_list_offsets";
-  if (n < 0) { set_error(std::string(who) + ": negative n"); return MIRT_ERR_ARG; }
-  if (n > (1ll << 40)) { set_error(std::string(who) + ": n above 2^40"); return MIRT_ERR_ARG; }
-  const size_t work = (size_t)list_offsets_work_bytes(n);
-  if (!d_offsets || (n > 0 && !d_counts) || (work && !d_work)) {
-    set_error(std::string(who) + ": null buffer (d_offsets; d_counts when n > 0; d_work when mirt_list_offsets_work_bytes(n) > 0)"); return MIRT_ERR_ARG;
-  }
-  if (!is_aligned(4, (const char*)d_counts) || !is_aligned(8, (const char*)d_offsets, (const char*)(work ? d_work : nullptr))) {
-    set_error(std::string(who) + ": d_counts must be 4-byte aligned, d_offsets and d_work 8-byte aligned"); return MIRT_ERR_ARG;
-  }
-  const void* const ptr[3] = {d_counts, d_offsets, d_work};
-  const size_t bytes[3] = {4 * (size_t)n, 8 * ((size_t)n + 1), work};
-  for (int x = 0; x < 3; ++x) {
-    for (int y = x + 1; y < 3; ++y) {
-      if (bytes[x] && bytes[y] && overlaps(ptr[x], bytes[x], ptr[y], bytes[y])) {
-        set_error(std::string(who) + ": d_counts, d_offsets and d_work must not overlap each other"); return MIRT_ERR_ARG;
-      }
-    }
-  }
+  // (a count the checks refuse has no work bytes: nothing is computed from it)
+  const size_t work = (n >= 0 && n <= (1ll << 40)) ? (size_t)list_offsets_work_bytes(n) : 0;
+  bool go = false;
+  const int rc = check_list_offsets(d_counts, n, d_offsets, d_work, work, &go);
+  if (rc != MIRT_OK) return rc;
   long long* const offsets = reinterpret_cast<long long*>(d_offsets);
-  if (n == 0) { MIRT_HIP(hipMemsetAsync(d_offsets, 0, sizeof(int64_t), stream)); return MIRT_OK; }      // (the total alone)
+  if (!go) { MIRT_HIP(hipMemsetAsync(d_offsets, 0, sizeof(int64_t), stream)); return MIRT_OK; }      // (n == 0: the total alone)
   const long long nb = list_blocks(n);
   u64* const sums = work ? reinterpret_cast<u64*>(d_work) : nullptr;
   if (sums) {
@@ -239,43 +177,17 @@ int list_offsets(MirtScene* sc, const uint32_t* d_counts, int64_t n, int64_t* d_
 
 int overlap_list(MirtScene* sc, const void* d_boxes, int64_t n, const int64_t* d_offsets, uint32_t* d_words, int64_t capacity, hipStream_t stream)
 {
-  const char* const who = "mirt_overlap_list";
-  if (n < 0) { set_error(std::string(who) + ": negative n"); return MIRT_ERR_ARG; }
-  if (capacity < 0) { set_error(std::string(who) + ": negative capacity"); return MIRT_ERR_ARG; }
-  if ((n > 0 && (!d_boxes || !d_offsets)) || (capacity > 0 && !d_words)) {
-    set_error(std::string(who) + ": null buffer (d_boxes and d_offsets when n > 0; d_words when capacity > 0)"); return MIRT_ERR_ARG;
-  }
-  if (!is_aligned(16, (const char*)d_boxes) || !is_aligned(8, (const char*)d_offsets) || !is_aligned(4, (const char*)d_words)) {
-    set_error(std::string(who) + ": d_boxes must be 16-byte aligned, d_offsets 8-byte aligned, d_words 4-byte aligned"); return MIRT_ERR_ARG;
-  }
-  // (a range of no bytes -- n == 0, capacity == 0 -- overlaps nothing)
-  const void* const ptr[3] = {d_boxes, d_offsets, d_words};
-  const size_t bytes[3] = {32 * (size_t)n, n > 0 ? 8 * ((size_t)n + 1) : 0, 4 * (size_t)capacity};
-  for (int x = 0; x < 3; ++x) {
-    for (int y = x + 1; y < 3; ++y) {
-      if (bytes[x] && bytes[y] && overlaps(ptr[x], bytes[x], ptr[y], bytes[y])) {
-        set_error(std::string(who) + ": d_boxes, d_offsets and d_words must not overlap each other"); return MIRT_ERR_ARG;
-      }
-    }
-  }
-  if (!sc->built) { set_error(std::string(who) + ": call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
-  if (n == 0 || capacity == 0) return MIRT_OK;      // (no row, or no word any row could write)
+  bool go = false;
+  const int rc = check_overlap_list(d_boxes, n, d_offsets, d_words, capacity, sc->built, &go);
+  if (rc != MIRT_OK || !go) return rc;
   OverlapListArgs q;
   q.boxes = reinterpret_cast<const float4*>(d_boxes);
   q.offsets = reinterpret_cast<const long long*>(d_offsets);
   q.words = d_words;
   q.capacity = capacity;
   q.n = n;
-  q.nodes = sc->nodes; q.unit_prim = sc->unit_prim;
-  q.tri_verts = sc->tri_verts;
-  q.planes = sc->planes; q.num_planes = sc->d.num_planes;
-  q.root_ref = sc->root_ref; q.prim_base16 = sc->prim_base / 16u;
-  q.coord_max = sc->coord_max;
-  q.lds_depth = query_lds_depth(sc);
-  const int grid = query_grid_blocks(sc, overlap_list_kernel, LIST_WAVES, &sc->overlap_list_blocks);
-  hipLaunchKernelGGL(overlap_list_kernel, dim3(row_launch(n, grid)), dim3(QUERY_BLOCK), 0, stream, q);
-  MIRT_HIP(hipGetLastError());
-  return MIRT_OK;
+  fill_scene_args(q, sc);
+  return launch_rows(sc, overlap_list_kernel, LIST_WAVES, &sc->overlap_list_blocks, n, q, stream);
 }
 
 } // namespace mirt

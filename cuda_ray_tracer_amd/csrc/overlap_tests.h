@@ -1,4 +1,4 @@
-// Device code the box-overlap kernels share (overlap.hip, overlap_list.hip; DESIGN.md sections 6w, 6x): the walk's slack and a
+// Device code the box-overlap kernels share (overlap.hip, overlap_list.hip, through overlap_walk.h; DESIGN.md sections 6w, 6x): a
 // sphere's and a triangle's overlap test against a box, by the operations include_ext/mirt_overlap.h fixes.  Everything here is
 // inlined into its caller, so the results' bits do not depend on who calls it.
 #ifndef MIRT_OVERLAP_TESTS_H
@@ -7,8 +7,6 @@
 #include "device_common.h"
 
 namespace mirt {
-
-constexpr float SLACK = 3.814697265625e-06f;         // 2^-18 (mirt_overlap.h, "Pruning")
 
 MIRT_DEV float min3(float x, float y, float z) { return fminf(fminf(x, y), z); }
 MIRT_DEV float max3(float x, float y, float z) { return fmaxf(fmaxf(x, y), z); }

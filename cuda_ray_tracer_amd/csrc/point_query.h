@@ -1,5 +1,6 @@
-// Device code the point queries share (closest.hip, closest_multi.hip; DESIGN.md sections 6o, 6s): a point's squared distance to a
-// box and its closest point on a triangle, by the operations include/mirt_closest.h fixes.  Everything here is inlined into its
+// Device code the point, cast and box queries share (closest.hip, closest_multi.hip, spherecast.hip, overlap.hip, overlap_list.hip;
+// DESIGN.md sections 6o, 6s, 6v, 6w, 6y): the walks' slack, a point's squared distance to a box, its closest point on a triangle and
+// the tie rule of the single-winner walks, by the operations include/mirt_closest.h fixes.  Everything here is inlined into its
 // caller, so the results' bits do not depend on who calls it.
 #ifndef MIRT_POINT_QUERY_H
 #define MIRT_POINT_QUERY_H
@@ -7,6 +8,13 @@
 #include "device_common.h"
 
 namespace mirt {
+
+constexpr float SLACK = 3.814697265625e-06f;         // 2^-18 ("Pruning" in mirt_closest.h, mirt_spherecast.h and mirt_overlap.h)
+
+MIRT_DEV float largest_abs(const f3& p) { return fmaxf(fmaxf(fabsf(p.x), fabsf(p.y)), fabsf(p.z)); }
+// the headers' sigma, once per row: (the largest coordinate magnitude of the row + coord_max [+ r]) * SLACK
+MIRT_DEV float row_sigma(float largest, float coord_max) { return (largest + coord_max) * SLACK; }
+MIRT_DEV float row_sigma(float largest, float coord_max, float r) { return ((largest + coord_max) + r) * SLACK; }
 
 // squared distance of q to the box [x0, x1] x [y0, y1] x [z0, z1]
 MIRT_DEV float box_dist2(float x0, float x1, float y0, float y1, float z0, float z1, const f3& q)
@@ -46,6 +54,16 @@ MIRT_DEV f3 triangle_point(const float4* tri_verts, uint32_t id, const f3& q)
   const float4* v = tri_verts + 3 * (size_t)id;
   const float4 a = v[0], b = v[1], c = v[2];
   return closest_on_triangle(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), q);
+}
+
+// A candidate at the winner's distance (closest.hip, spherecast.hip): (kind, id) decides -- a primitive before a plane, a sphere
+// before a triangle, the lower index.  cur is the candidate's record and id its file-order id if it is a triangle (a sphere's is
+// loaded here); the winner is a plane (plane_id >= 0) or the record refbest.
+MIRT_DEV bool wins_tie(uint32_t cur, uint32_t id, int plane_id, uint32_t refbest, const uint32_t* unit_prim, uint32_t prim_base16)
+{
+  if (plane_id >= 0 || (cur & REF_TRI) != (refbest & REF_TRI)) return plane_id >= 0 || !(cur & REF_TRI);
+  if (!(cur & REF_TRI)) id = unit_prim[(cur & REF_OFFMASK) - prim_base16] & 0x7fffffffu;
+  return id < (unit_prim[(refbest & REF_OFFMASK) - prim_base16] & 0x7fffffffu);
 }
 
 } // namespace mirt

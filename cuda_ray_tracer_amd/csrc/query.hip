@@ -162,20 +162,14 @@ int trace_rays(MirtScene* sc, const void* d_rays, int64_t num_rays, void* d_hits
   }
   if (!sc->built) { set_error("mirt_trace_rays: call mirt_build_lbvh first"); return MIRT_ERR_STATE; }
   if (num_rays == 0) return MIRT_OK;
-  const int grid = query_grid_blocks(sc, trace_rays_kernel<false>, QWAVES_PER_SIMD, &sc->query_blocks);
+  query_grid_blocks(sc, trace_rays_kernel<false>, QWAVES_PER_SIMD, &sc->query_blocks);      // (both instances run on the closest-hit instance's grid)
   QueryArgs q;
   q.rays = reinterpret_cast<const float4*>(d_rays);
   q.hits = reinterpret_cast<uint32_t*>(d_hits);
   q.num_rays = num_rays;
-  q.nodes = sc->nodes; q.unit_prim = sc->unit_prim;
-  q.planes = sc->planes; q.num_planes = sc->d.num_planes;
-  q.root_ref = sc->root_ref; q.prim_base16 = sc->prim_base / 16u;
-  q.lds_depth = query_lds_depth(sc);
-  const int blocks = row_launch(num_rays, grid);
-  if (flags & MIRT_QUERY_ANY_HIT) hipLaunchKernelGGL(trace_rays_kernel<true>, dim3(blocks), dim3(QUERY_BLOCK), 0, stream, q);
-  else hipLaunchKernelGGL(trace_rays_kernel<false>, dim3(blocks), dim3(QUERY_BLOCK), 0, stream, q);
-  MIRT_HIP(hipGetLastError());
-  return MIRT_OK;
+  fill_walk_args(q, sc);
+  return (flags & MIRT_QUERY_ANY_HIT) ? launch_rows(sc, trace_rays_kernel<true>, QWAVES_PER_SIMD, &sc->query_blocks, num_rays, q, stream)
+                                      : launch_rows(sc, trace_rays_kernel<false>, QWAVES_PER_SIMD, &sc->query_blocks, num_rays, q, stream);
 }
 
 int camera_rays(MirtScene* sc, const MirtRenderParams* p, void* d_rays, hipStream_t stream)

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mirt.h"
@@ -405,7 +406,8 @@ hipError_t persistent_grid_blocks(int device, K kernel, int block, int per_cu_fa
   return hipSuccess;
 }
 
-// The query kernels' host side (query.hip, light.hip, visibility.hip, indirect.hip, closest.hip, closest_multi.hip, spherecast.hip, overlap.hip, overlap_list.hip, multihit.hip; launch arithmetic: query_launch.h).
+// The query kernels' host side (query.hip, light.hip, visibility.hip, indirect.hip, closest.hip, closest_multi.hip, spherecast.hip,
+// overlap.hip, overlap_list.hip, multihit.hip; launch arithmetic: query_launch.h; argument checks: host_scene.h).
 // Stack entries their walk keeps in LDS: the compiled size, unless the option names a smaller one (tests force the spill path).
 inline int query_lds_depth(const MirtScene* sc)
 {
@@ -420,6 +422,46 @@ int query_grid_blocks(const MirtScene* sc, K kernel, int waves_per_simd, int* ca
 {
   if (!*cache && persistent_grid_blocks(sc->device, kernel, QUERY_BLOCK, waves_per_simd * 4 * 64 / QUERY_BLOCK, cache) != hipSuccess) *cache = 1024;
   return *cache;
+}
+
+// One launch of a kernel with one lane per row: its persistent grid, as many blocks of it as n rows need (row_launch), the launch
+// and its error.
+template <class K, class A>
+int launch_rows(const MirtScene* sc, K kernel, int waves_per_simd, int* cache, long long n, const A& args, hipStream_t stream)
+{
+  const int grid = query_grid_blocks(sc, kernel, waves_per_simd, cache);
+  hipLaunchKernelGGL(kernel, dim3(row_launch(n, grid)), dim3(QUERY_BLOCK), 0, stream, args);
+  MIRT_HIP(hipGetLastError());
+  return MIRT_OK;
+}
+
+// The scene fields of a row kernel's *Args struct: what every walk over the exact records reads ...
+template <class A>
+void fill_walk_args(A& q, const MirtScene* sc)
+{
+  q.nodes = sc->nodes; q.unit_prim = sc->unit_prim;
+  q.planes = sc->planes; q.num_planes = sc->d.num_planes;
+  q.root_ref = sc->root_ref; q.prim_base16 = sc->prim_base / 16u;
+  q.lds_depth = query_lds_depth(sc);
+}
+// ... and what the point, cast and box queries read beside it
+template <class A>
+void fill_scene_args(A& q, const MirtScene* sc)
+{
+  fill_walk_args(q, sc);
+  q.tri_verts = sc->tri_verts;
+  q.coord_max = sc->coord_max;
+}
+
+// The list kernels' capacity ladder: f(the smallest of the capacities 0, 1, 4, 8 that holds k, as a std::integral_constant; its
+// index 0..3 -- the slot of the instance's cached grid size, since occupancy is per kernel).
+template <class F>
+int with_capacity(int k, F f)
+{
+  if (k == 0) return f(std::integral_constant<int, 0>(), 0);
+  if (k == 1) return f(std::integral_constant<int, 1>(), 1);
+  if (k <= 4) return f(std::integral_constant<int, 4>(), 2);
+  return f(std::integral_constant<int, 8>(), 3);
 }
 
 // the frame, camera and partition block of RenderArgs (what a primary ray is made from, apart from spp and the rng tables)

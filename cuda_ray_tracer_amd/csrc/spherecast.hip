@@ -25,8 +25,7 @@ namespace {
 // the compiler's report decides: at 5 waves per SIMD both instances take the 96 VGPRs there are and spill
 // nothing; at 6 (80 VGPRs) they spill 11 and 12 registers, at 8 (64) about 30
 constexpr int SWAVES_PER_SIMD = 5;
-constexpr float SLACK = 3.814697265625e-06f;         // 2^-18 (mirt_spherecast.h, "Pruning")
-constexpr float TAU = 9.5367431640625e-07f;          // 2^-20
+constexpr float TAU = 9.5367431640625e-07f;          // 2^-20 (mirt_spherecast.h, "Pruning"; SLACK: point_query.h)
 
 struct CastArgs {
   const float4* casts;            // (o, tmax), (d, r)
@@ -186,7 +185,7 @@ __global__ void __launch_bounds__(QUERY_BLOCK, SWAVES_PER_SIMD) sphere_cast_kern
     // (a cast for any contact that a plane already answers needs no walk)
     if (live && a.root_ref != REF_NONE && !(ANY && plane_id >= 0)) {
       const f3 inv = mk3(1.0f / k.d.x, 1.0f / k.d.y, 1.0f / k.d.z);
-      const float sigma = ((fmaxf(fmaxf(fabsf(k.o.x), fabsf(k.o.y)), fabsf(k.o.z)) + a.coord_max) + k.r) * SLACK;
+      const float sigma = row_sigma(largest_abs(k.o), a.coord_max, k.r);
       const float grow = k.r + sigma;
       float bound = best + best * TAU;     // a box the centre enters later than this holds nothing that wins or ties
       uint32_t cur = a.root_ref;
@@ -207,15 +206,8 @@ __global__ void __launch_bounds__(QUERY_BLOCK, SWAVES_PER_SIMD) sphere_cast_kern
             t = sphere_cast(rec[0], k);
           }
           bool better = t >= 0.0f && t < best;
-          if (t == best && (plane_id >= 0 || refbest != REF_NONE)) {
-            // a tie with the winner: (kind, id) decides -- a primitive before a plane, a sphere before a triangle, the lower index
-            if (plane_id >= 0 || (cur & REF_TRI) != (refbest & REF_TRI)) {
-              better = plane_id >= 0 || !(cur & REF_TRI);
-            } else {
-              if (!(cur & REF_TRI)) id = a.unit_prim[(cur & REF_OFFMASK) - a.prim_base16] & 0x7fffffffu;
-              better = id < (a.unit_prim[(refbest & REF_OFFMASK) - a.prim_base16] & 0x7fffffffu);
-            }
-          }
+          // (a tie with the winner: (kind, id) decides)
+          if (t == best && (plane_id >= 0 || refbest != REF_NONE)) better = wins_tie(cur, id, plane_id, refbest, a.unit_prim, a.prim_base16);
           if (better) {
             best = t; refbest = cur; plane_id = -1;
             bound = best + best * TAU;
@@ -282,45 +274,21 @@ __global__ void __launch_bounds__(QUERY_BLOCK, SWAVES_PER_SIMD) sphere_cast_kern
   }
 }
 
-template <bool ANY>
-int launch(MirtScene* sc, const CastArgs& q, int64_t n, hipStream_t stream)
-{
-  const int grid = query_grid_blocks(sc, sphere_cast_kernel<ANY>, SWAVES_PER_SIMD, &sc->spherecast_blocks[ANY ? 1 : 0]);
-  hipLaunchKernelGGL(sphere_cast_kernel<ANY>, dim3(row_launch(n, grid)), dim3(QUERY_BLOCK), 0, stream, q);
-  MIRT_HIP(hipGetLastError());
-  return MIRT_OK;
-}
-
 } // namespace
 
 int cast_spheres(MirtScene* sc, const void* d_casts, int64_t n, void* d_hits, void* d_features, uint32_t flags, hipStream_t stream)
 {
-  const char* const who = "mirt_cast_spheres";
-  if (flags & ~MIRT_CAST_ANY_HIT) { set_error(std::string(who) + ": unknown flag bits"); return MIRT_ERR_ARG; }
-  if (n < 0) { set_error(std::string(who) + ": negative n"); return MIRT_ERR_ARG; }
-  if (n > 0 && (!d_casts || !d_hits)) { set_error(std::string(who) + ": null buffer"); return MIRT_ERR_ARG; }
-  if (!is_aligned(16, (const char*)d_casts, (const char*)d_features) || !is_aligned(4, (const char*)d_hits)) {
-    set_error(std::string(who) + ": d_casts and d_features must be 16-byte aligned, d_hits 4-byte aligned"); return MIRT_ERR_ARG;
-  }
-  const size_t rows = (size_t)n;
-  if (n > 0 && (overlaps(d_hits, 24 * rows, d_casts, 32 * rows) ||
-                (d_features && (overlaps(d_features, 32 * rows, d_casts, 32 * rows) || overlaps(d_features, 32 * rows, d_hits, 24 * rows))))) {
-    set_error(std::string(who) + ": d_hits and d_features must not overlap d_casts or each other"); return MIRT_ERR_ARG;
-  }
-  if (!sc->built) { set_error(std::string(who) + ": call mirt_build_lbvh first"); return MIRT_ERR_STATE; }      // (also with n == 0: the header)
-  if (n == 0) return MIRT_OK;
+  bool go = false;
+  const int rc = check_cast_spheres(d_casts, n, d_hits, d_features, flags, sc->built, &go);
+  if (rc != MIRT_OK || !go) return rc;
   CastArgs q;
   q.casts = reinterpret_cast<const float4*>(d_casts);
   q.hits = reinterpret_cast<uint32_t*>(d_hits);
   q.features = reinterpret_cast<float4*>(d_features);
   q.n = n;
-  q.nodes = sc->nodes; q.unit_prim = sc->unit_prim;
-  q.tri_verts = sc->tri_verts;
-  q.planes = sc->planes; q.num_planes = sc->d.num_planes;
-  q.root_ref = sc->root_ref; q.prim_base16 = sc->prim_base / 16u;
-  q.coord_max = sc->coord_max;
-  q.lds_depth = query_lds_depth(sc);
-  return (flags & MIRT_CAST_ANY_HIT) ? launch<true>(sc, q, n, stream) : launch<false>(sc, q, n, stream);
+  fill_scene_args(q, sc);
+  return (flags & MIRT_CAST_ANY_HIT) ? launch_rows(sc, sphere_cast_kernel<true>, SWAVES_PER_SIMD, &sc->spherecast_blocks[1], n, q, stream)
+                                     : launch_rows(sc, sphere_cast_kernel<false>, SWAVES_PER_SIMD, &sc->spherecast_blocks[0], n, q, stream);
 }
 
 } // namespace mirt

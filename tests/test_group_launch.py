@@ -1,6 +1,7 @@
 """The launch arithmetic the query kernels share (csrc/query_launch.h: group_launch, used by light.hip, visibility.hip and
-indirect.hip; row_launch, used by query.hip, closest.hip and multihit.hip) needs no GPU: a stand-alone probe, tests/group_launch_probe.cpp, is compiled with the host compiler (address +
-undefined sanitizers where they link) and prints gshift and the block counts of every case it reads.  Checked here against the
+indirect.hip; row_launch, used through scene_dev.h's launch_rows by query.hip, closest.hip, closest_multi.hip, spherecast.hip,
+overlap.hip, overlap_list.hip and multihit.hip) needs no GPU: a stand-alone probe, tests/group_launch_probe.cpp, is compiled with
+the host compiler (address + undefined sanitizers where they link) and prints gshift and the block counts of every case it reads.  Checked here against the
 expressions each of the files had of its own before they were shared, restated below."""
 import os
 import shutil

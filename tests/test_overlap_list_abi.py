@@ -123,18 +123,25 @@ def test_the_build_depends_on_the_header_and_the_kernel():
 
 
 def test_the_shared_device_code_has_one_copy():
-    """The scan and the overlap tests moved to headers: overlap.hip, overlap_list.hip and lbvh_build.hip include them and define
-    none of them."""
+    """The scan, the overlap tests and the walks' slack are in headers: overlap.hip, overlap_list.hip and lbvh_build.hip include them
+    and define none of them.  The fill kernel takes the tests through overlap_walk.h, which holds its walk (the leaf tests and the
+    register fences; overlap.hip keeps its own), and the slack is point_query.h's, the only one in csrc."""
     read = lambda name: open(os.path.join(B.CSRC, name)).read()
-    for src, header, words in (("overlap.hip", "overlap_tests.h", ("bool sphere_overlaps(", "bool triangle_overlaps(", "bool edge_axis(", "float SLACK")),
-                               ("overlap_list.hip", "overlap_tests.h", ("bool sphere_overlaps(", "bool triangle_overlaps(", "bool edge_axis(", "float SLACK")),
+    tests = ("bool sphere_overlaps(", "bool triangle_overlaps(", "bool edge_axis(")
+    walk = ("triangle_overlaps(m, h", "sphere_overlaps(lo, hi", "asm volatile", "stack_pop(")
+    for src, header, words in (("overlap.hip", "overlap_tests.h", tests + ("float SLACK",)),
+                               ("overlap.hip", "point_query.h", ()),
+                               ("overlap_list.hip", "overlap_walk.h", tests + walk + ("float SLACK",)),
+                               ("overlap_walk.h", "overlap_tests.h", tests + ("float SLACK",)),
                                ("overlap_list.hip", "block_scan.h", (" block_exclusive_scan(T v",)),
                                ("lbvh_build.hip", "block_scan.h", (" block_exclusive_scan(T v", "uint32_t block_exclusive_scan("))):
         text = read(src)
         assert '#include "%s"' % header in text, (src, header)
         for w in words:
             assert w not in text, (src, w)
-    assert all(w in read("overlap_tests.h") for w in ("bool sphere_overlaps(", "bool triangle_overlaps(", "bool edge_axis(", "float SLACK"))
+    assert all(w in read("overlap_tests.h") for w in tests)
+    assert all(w in read("overlap_walk.h") for w in walk)
+    assert [f for f in sorted(os.listdir(B.CSRC)) if "float SLACK" in read(f)] == ["point_query.h"]
     assert " block_exclusive_scan(T v" in read("block_scan.h")
 
 

@@ -3,7 +3,7 @@
 Host side: binding.py (include/mirt.h restated for ctypes) and api.py (the calls over it); lighting.py (include/mirt_light.h);
 visibility.py (include/mirt_visibility.h); indirect.py (include/mirt_indirect.h); closest.py (include/mirt_closest.h);
 multihit.py (include/mirt_multihit.h); contacts.py (include_ext/mirt_contacts.h); spherecast.py (include_ext/mirt_spherecast.h);
-overlap.py (include_ext/mirt_overlap.h); overlap_list.py (include_ext/mirt_overlap_list.h).
+overlap.py (include_ext/mirt_overlap.h); overlap_list.py (include_ext/mirt_overlap_list.h); query_lists.py (include_ext/mirt_query_lists.h).
 Device side: csrc/*.hip, built by build.py into _build/libmirt.so.
 """
 from .api import (MirtError, StlConfig, RawConfig, parseInput, parseText, syntheticScene, initRawConfigFromStl,
@@ -18,7 +18,8 @@ from .api import (MirtError, StlConfig, RawConfig, parseInput, parseText, synthe
                   indirect_light, indirect_light_frame, closest_points, pack_points, trace_rays_multi, count_hits,
                   closest_points_multi, count_within, cast_spheres, pack_casts,
                   overlap_boxes, count_overlaps, pack_boxes, voxel_rows, occupancy_grid,
-                  list_offsets, list_offsets_work_bytes, overlap_list, overlap_lists, unpack_words, voxel_lists)
+                  list_offsets, list_offsets_work_bytes, overlap_list, overlap_lists, unpack_words, voxel_lists,
+                  ray_list, ball_list, ray_lists, ball_lists)
 
 __all__ = ["MirtError", "StlConfig", "RawConfig", "parseInput", "parseText", "syntheticScene", "initRawConfigFromStl",
            "copyConfigDataToDevice", "freeRawConfigDeviceMemory", "build_lbvh_karas", "render", "render_params",
@@ -32,4 +33,5 @@ __all__ = ["MirtError", "StlConfig", "RawConfig", "parseInput", "parseText", "sy
            "indirect_light", "indirect_light_frame", "closest_points", "pack_points", "trace_rays_multi", "count_hits",
            "closest_points_multi", "count_within", "cast_spheres", "pack_casts",
            "overlap_boxes", "count_overlaps", "pack_boxes", "voxel_rows", "occupancy_grid",
-           "list_offsets", "list_offsets_work_bytes", "overlap_list", "overlap_lists", "unpack_words", "voxel_lists"]
+           "list_offsets", "list_offsets_work_bytes", "overlap_list", "overlap_lists", "unpack_words", "voxel_lists",
+           "ray_list", "ball_list", "ray_lists", "ball_lists"]

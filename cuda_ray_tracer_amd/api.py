@@ -941,6 +941,8 @@ from .spherecast import cast_spheres, pack_casts      # noqa: E402,F401
 from .overlap import overlap_boxes, count_overlaps, pack_boxes, voxel_rows, occupancy_grid      # noqa: E402,F401
 # Overlap lists (include_ext/mirt_overlap_list.h): overlap_list.py holds that header's signatures and calls
 from .overlap_list import list_offsets, list_offsets_work_bytes, overlap_list, overlap_lists, unpack_words, voxel_lists      # noqa: E402,F401
+# Ray and ball lists (include_ext/mirt_query_lists.h): query_lists.py holds that header's signatures and calls
+from .query_lists import ray_list, ball_list, ray_lists, ball_lists      # noqa: E402,F401
 
 
 def pack_rays(origins, dirs, tmax=float("inf")):

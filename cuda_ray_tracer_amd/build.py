@@ -17,7 +17,7 @@ LIB = os.path.join(OUT, "libmirt.so")
 CLI = os.path.join(OUT, "raytracer")
 ARCH = "gfx950"
 
-LIB_SOURCES = ["host_scene.cpp", "png_writer.cpp", "xorwow_tables.cpp", "multi.cpp", "lbvh_build.hip", "tree_readback.hip", "render.hip", "adaptive.hip", "denoise.hip", "temporal.hip", "wavefront.hip", "query.hip", "light.hip", "visibility.hip", "indirect.hip", "closest.hip", "closest_multi.hip", "spherecast.hip", "overlap.hip", "overlap_list.hip", "multihit.hip", "update.hip", "update_shading.hip", "api.hip"]
+LIB_SOURCES = ["host_scene.cpp", "png_writer.cpp", "xorwow_tables.cpp", "multi.cpp", "lbvh_build.hip", "tree_readback.hip", "render.hip", "adaptive.hip", "denoise.hip", "temporal.hip", "wavefront.hip", "query.hip", "light.hip", "visibility.hip", "indirect.hip", "closest.hip", "closest_multi.hip", "spherecast.hip", "overlap.hip", "overlap_list.hip", "query_lists.hip", "multihit.hip", "update.hip", "update_shading.hip", "api.hip"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
           f"--offload-arch={ARCH}", "-fno-gpu-flush-denormals-to-zero"]
 

@@ -422,6 +422,21 @@ int mirt_overlap_list(MirtScene* sc, const void* d_boxes, int64_t n, const int64
   return overlap_list(sc, d_boxes, n, d_offsets, d_words, capacity, (hipStream_t)stream);
 }
 
+// (include_ext/mirt_query_lists.h)
+int mirt_ray_list(MirtScene* sc, const void* d_rays, int64_t num_rays, const int64_t* d_offsets, uint32_t* d_words, float* d_t, int64_t capacity,
+                  uint32_t flags, void* stream)
+{
+  MIRT_TRY(enter_scene(sc, "mirt_ray_list"));
+  return ray_list(sc, d_rays, num_rays, d_offsets, d_words, d_t, capacity, flags, (hipStream_t)stream);
+}
+
+int mirt_ball_list(MirtScene* sc, const void* d_points, int64_t n, const int64_t* d_offsets, uint32_t* d_words, float* d_dist, int64_t capacity,
+                   uint32_t flags, void* stream)
+{
+  MIRT_TRY(enter_scene(sc, "mirt_ball_list"));
+  return ball_list(sc, d_points, n, d_offsets, d_words, d_dist, capacity, flags, (hipStream_t)stream);
+}
+
 size_t mirt_denoise_work_bytes(const MirtRenderParams* p) { return denoise_work_bytes(p); }
 
 int mirt_denoise(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, const void* d_features,

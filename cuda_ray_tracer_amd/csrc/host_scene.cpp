@@ -179,6 +179,35 @@ int check_overlap_list(const void* d_boxes, int64_t n, const void* d_offsets, co
   return rc;
 }
 
+int check_ray_list(const void* d_rays, int64_t num_rays, const void* d_offsets, const void* d_words, const void* d_t, int64_t capacity, uint32_t flags,
+                   bool built, bool* go)
+{
+  // (a range of no bytes -- num_rays == 0, capacity == 0, a null d_t -- overlaps nothing)
+  const size_t rows = (size_t)num_rays;
+  const int rc = check_row_query("mirt_ray_list", flags, num_rays, "num_rays", {{capacity < 0, "negative capacity"}},
+                                 {{d_rays, 32 * rows, 16, num_rays > 0}, {d_offsets, num_rays > 0 ? 8 * (rows + 1) : 0, 8, num_rays > 0},
+                                  {d_words, 4 * (size_t)capacity, 4, capacity > 0}, {d_t, 4 * (size_t)capacity, 4, false}},
+                                 "null buffer (d_rays and d_offsets when num_rays > 0; d_words when capacity > 0)",
+                                 "d_rays must be 16-byte aligned, d_offsets 8-byte aligned, d_words and d_t 4-byte aligned",
+                                 "d_rays, d_offsets, d_words and d_t must not overlap each other", built, go);
+  *go = *go && capacity > 0;      // (no row, or no word any row could write)
+  return rc;
+}
+
+int check_ball_list(const void* d_points, int64_t n, const void* d_offsets, const void* d_words, const void* d_dist, int64_t capacity, uint32_t flags,
+                    bool built, bool* go)
+{
+  const size_t rows = (size_t)n;
+  const int rc = check_row_query("mirt_ball_list", flags, n, "n", {{capacity < 0, "negative capacity"}},
+                                 {{d_points, 16 * rows, 16, n > 0}, {d_offsets, n > 0 ? 8 * (rows + 1) : 0, 8, n > 0},
+                                  {d_words, 4 * (size_t)capacity, 4, capacity > 0}, {d_dist, 4 * (size_t)capacity, 4, false}},
+                                 "null buffer (d_points and d_offsets when n > 0; d_words when capacity > 0)",
+                                 "d_points must be 16-byte aligned, d_offsets 8-byte aligned, d_words and d_dist 4-byte aligned",
+                                 "d_points, d_offsets, d_words and d_dist must not overlap each other", built, go);
+  *go = *go && capacity > 0;      // (no row, or no word any row could write)
+  return rc;
+}
+
 int check_trace_rays_multi(const void* d_rays, int64_t num_rays, int k, const void* d_hits, const void* d_counts, uint32_t flags, bool built, bool* go)
 {
   const size_t rows = (size_t)num_rays, per_row = k > 0 ? (size_t)k : 0;

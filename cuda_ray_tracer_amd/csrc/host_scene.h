@@ -54,7 +54,8 @@ struct ArgRule { bool bad; const char* msg; };
 // message.  MIRT_OK with *go = false: nothing to do (n == 0).
 int check_row_query(const char* who, uint32_t unknown_flags, int64_t n, const char* n_name, std::initializer_list<ArgRule> rules,
                     std::initializer_list<QueryBuf> bufs, const char* null_msg, const char* align_msg, const char* overlap_msg, bool built, bool* go);
-// ... of the seven entry points (closest.hip, closest_multi.hip, spherecast.hip, overlap.hip, overlap_list.hip, multihit.hip)
+// ... of the nine entry points (closest.hip, closest_multi.hip, spherecast.hip, overlap.hip, overlap_list.hip, query_lists.hip,
+// multihit.hip)
 int check_closest_points(const void* d_points, int64_t n, const void* d_hits, const void* d_features, uint32_t flags, bool built, bool* go);
 int check_closest_points_multi(const void* d_points, int64_t n, int k, const void* d_hits, const void* d_counts, const void* d_features, uint32_t flags,
                                bool built, bool* go);
@@ -64,6 +65,11 @@ int check_overlap_boxes(const void* d_boxes, int64_t n, int k, const void* d_hit
 // (work_bytes: mirt_list_offsets_work_bytes(n); no scene is read, so there is no `built`)
 int check_list_offsets(const void* d_counts, int64_t n, const void* d_offsets, const void* d_work, size_t work_bytes, bool* go);
 int check_overlap_list(const void* d_boxes, int64_t n, const void* d_offsets, const void* d_words, int64_t capacity, bool built, bool* go);
+// (d_values: the optional array of t or dist, null or `capacity` floats)
+int check_ray_list(const void* d_rays, int64_t num_rays, const void* d_offsets, const void* d_words, const void* d_t, int64_t capacity, uint32_t flags,
+                   bool built, bool* go);
+int check_ball_list(const void* d_points, int64_t n, const void* d_offsets, const void* d_words, const void* d_dist, int64_t capacity, uint32_t flags,
+                    bool built, bool* go);
 int check_trace_rays_multi(const void* d_rays, int64_t num_rays, int k, const void* d_hits, const void* d_counts, uint32_t flags, bool built, bool* go);
 
 class HostScene {

@@ -24,6 +24,7 @@
 #include "point_query.h"
 #include "block_scan.h"
 #include "overlap_walk.h"
+#include "list_cursor.h"
 #include "../../include_ext/mirt_overlap_list.h"
 
 #include <cmath>
@@ -99,9 +100,8 @@ struct OverlapListArgs {
   int lds_depth;                  // stack entries kept in LDS (<= QUERY_STACK_LDS)
 };
 
-// A row's cursor: where its next word goes and how many more its segment [beg, min(lim, capacity)) takes -- none if the segment
-// begins below 0, at or beyond the capacity or after its own end.  (A row admits fewer than 2^32 candidates, so a longer
-// segment's room may stop there.)
+// A row's cursor: where its next word goes and how many more its segment takes (list_cursor.h's list_room: the rule the ray and
+// ball fills of query_lists.hip share).
 // It is the walk's action (overlap_walk.h): an admitted candidate's word kind << 30 | id goes to the cursor.
 struct Cursor {
   uint32_t* out; uint32_t room;
@@ -120,11 +120,10 @@ struct Cursor {
 };
 MIRT_DEV Cursor row_cursor(const OverlapListArgs& a, long long i)
 {
-  const long long beg = a.offsets[i], lim = a.offsets[i + 1];
-  const long long end = lim < a.capacity ? lim : a.capacity;
+  const ListRoom r = list_room(a.offsets, a.capacity, i);
   Cursor c;
-  c.room = (beg >= 0 && beg < end) ? (uint32_t)(end - beg > 0xffffffffll ? 0xffffffffll : end - beg) : 0u;
-  c.out = a.words + (c.room ? beg : 0);
+  c.room = r.room;
+  c.out = a.words + r.beg;
   c.unit_prim = a.unit_prim; c.prim_base16 = a.prim_base16;
   return c;
 }

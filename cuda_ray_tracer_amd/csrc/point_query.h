@@ -1,4 +1,4 @@
-// Device code the point, cast and box queries share (closest.hip, closest_multi.hip, spherecast.hip, overlap.hip, overlap_list.hip;
+// Device code the point, cast and box queries share (closest.hip, closest_multi.hip, spherecast.hip, overlap.hip, overlap_list.hip, query_lists.hip;
 // DESIGN.md sections 6o, 6s, 6v, 6w, 6y): the walks' slack, a point's squared distance to a box, its closest point on a triangle and
 // the tie rule of the single-winner walks, by the operations include/mirt_closest.h fixes.  Everything here is inlined into its
 // caller, so the results' bits do not depend on who calls it.

@@ -1,5 +1,5 @@
 // Launch arithmetic of the query kernels (query.hip, light.hip, visibility.hip, indirect.hip, closest.hip, closest_multi.hip,
-// spherecast.hip, overlap.hip, overlap_list.hip, multihit.hip): no HIP and no scene, so that a stand-alone host program can include
+// spherecast.hip, overlap.hip, overlap_list.hip, query_lists.hip, multihit.hip): no HIP and no scene, so that a stand-alone host program can include
 // it (tests/group_launch_probe.cpp, as tests/plan_probe.cpp includes render_plan.h).
 #ifndef MIRT_QUERY_LAUNCH_H
 #define MIRT_QUERY_LAUNCH_H
@@ -29,7 +29,7 @@ inline GroupLaunch group_launch(long long n, int lanes_per_row, int cached_block
 }
 
 // A kernel with one lane per row (query.hip, closest.hip, closest_multi.hip, spherecast.hip, overlap.hip, overlap_list.hip,
-// multihit.hip, through scene_dev.h's launch_rows): as many blocks as n rows need, at most cached_blocks.
+// query_lists.hip, multihit.hip, through scene_dev.h's launch_rows): as many blocks as n rows need, at most cached_blocks.
 inline int row_launch(long long n, int cached_blocks)
 {
   const long long want = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;

@@ -1,6 +1,6 @@
 // Device code that query kernels share (DESIGN.md sections 6n, 6q): the walk over the exact 64-byte records (light.hip,
 // indirect.hip), the pieces every walk is made of -- the lane's stack, the live-ray rule, the planes' scalar loads, a MirtHit's
-// stores (also query.hip, multihit.hip, closest.hip, closest_multi.hip, spherecast.hip and overlap_walk.h, which write their own
+// stores (also query.hip, multihit.hip, query_lists.hip, closest.hip, closest_multi.hip, spherecast.hip and overlap_walk.h, which write their own
 // loops) --, hitNearest's choice between the tree's hit
 // and the planes' and the winner's normal (query.hip, indirect.hip), a light's shadow ray and a row's field of the wave's ballot
 // (light.hip).  Which file uses which piece was decided by measurement, kernel by kernel: sections 6n, 6q.  Everything here is

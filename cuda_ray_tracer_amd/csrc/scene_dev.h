@@ -279,6 +279,8 @@ struct MirtScene {
   int spherecast_blocks[2] = {0, 0};       // ... and of the sphere-cast kernel's instances (spherecast.hip: first contact, any contact)
   int overlap_blocks[5] = {0, 0, 0, 0, 0}; // ... and of the box-overlap kernel's instances (overlap.hip: count, any, capacity 1, 4, 8)
   int overlap_list_blocks = 0;             // ... and of the overlap-list fill kernel (overlap_list.hip)
+  int ray_list_blocks[2] = {0, 0};         // ... and of the ray-list fill kernel's instances (query_lists.hip: words, words and values)
+  int ball_list_blocks[2] = {0, 0};        // ... and of the ball-list fill kernel's instances (query_lists.hip: words, words and values)
   bool updated = false;                    // geometry updated in place since the last build (update.hip): mirt_camera_rays waits for the build like every other call
   // Shading values updated in place (update_shading.hip).  The three facts above are prim_flags | host_flags (MAT_* bits,
   // material_flags.h), by source: the primitives' materials -- after a material update known only to the device, until
@@ -354,6 +356,11 @@ int overlap_boxes(MirtScene* sc, const void* d_boxes, int64_t n, int k, void* d_
 int64_t list_offsets_work_bytes(int64_t n);
 int list_offsets(MirtScene* sc, const uint32_t* d_counts, int64_t n, int64_t* d_offsets, void* d_work, hipStream_t stream);
 int overlap_list(MirtScene* sc, const void* d_boxes, int64_t n, const int64_t* d_offsets, uint32_t* d_words, int64_t capacity, hipStream_t stream);
+// query_lists.hip
+int ray_list(MirtScene* sc, const void* d_rays, int64_t num_rays, const int64_t* d_offsets, uint32_t* d_words, float* d_t, int64_t capacity, uint32_t flags,
+             hipStream_t stream);
+int ball_list(MirtScene* sc, const void* d_points, int64_t n, const int64_t* d_offsets, uint32_t* d_words, float* d_dist, int64_t capacity, uint32_t flags,
+              hipStream_t stream);
 // multihit.hip
 int trace_rays_multi(MirtScene* sc, const void* d_rays, int64_t num_rays, int k, void* d_hits, uint32_t* d_counts, uint32_t flags, hipStream_t stream);
 // denoise.hip
@@ -407,7 +414,7 @@ hipError_t persistent_grid_blocks(int device, K kernel, int block, int per_cu_fa
 }
 
 // The query kernels' host side (query.hip, light.hip, visibility.hip, indirect.hip, closest.hip, closest_multi.hip, spherecast.hip,
-// overlap.hip, overlap_list.hip, multihit.hip; launch arithmetic: query_launch.h; argument checks: host_scene.h).
+// overlap.hip, overlap_list.hip, query_lists.hip, multihit.hip; launch arithmetic: query_launch.h; argument checks: host_scene.h).
 // Stack entries their walk keeps in LDS: the compiled size, unless the option names a smaller one (tests force the spill path).
 inline int query_lds_depth(const MirtScene* sc)
 {

@@ -1,4 +1,5 @@
-"""What the query benches share (query_bench, light_bench, visibility_bench, indirect_bench, closest_bench, multihit_bench, contacts_bench, spherecast_bench, overlap_bench):
+"""What the query benches share (query_bench, light_bench, visibility_bench, indirect_bench, closest_bench, multihit_bench, contacts_bench, spherecast_bench, overlap_bench,
+overlap_list_bench, query_lists_bench):
 the timing loop, the scenes, the rays and rows they start from, and the JSON line they end with.  Imported by them, not run."""
 import argparse
 import json

@@ -50,7 +50,7 @@ const OptionDesc OPTIONS[] = {
   {"bounds_as_shipped", &Options::bounds_as_shipped, 0, 1, true},
   {"traversal", &Options::traversal, 0, 2, true}, {"wavefront", &Options::wavefront, 0, 1, true},
   {"qnodes", &Options::qnodes, 0, 2, true}, {"shadow_anyhit", &Options::shadow_anyhit, 0, 1, true}, {"skip_unlit", &Options::skip_unlit, 0, 1, true},
-  {"stack_lds_depth", &Options::stack_lds_depth, -1, 64, false}, {"refill_k", &Options::refill_k, 0, 64, false}, {"batch_k", &Options::batch_k, 1, 64, false},
+  {"stack_lds_depth", &Options::stack_lds_depth, -1, 64, false}, {"refill_k", &Options::refill_k, 0, 64, false}, {"batch_k", &Options::batch_k, 0, 64, false},
   {"leaf_k", &Options::leaf_k, 0, 64, false}, {"init_k", &Options::init_k, 0, 64, false}, {"reps", &Options::reps, 0, 8, false}, {"drain_lanes", &Options::drain_lanes, 0, 64, false},
   {"chunk_shift", &Options::chunk_shift, 0, 12, false}, {"trace_waves", &Options::trace_waves, 0, 1 << 20, false}, {"sched", &Options::sched, 0, 2, false},
   {"specialise", &Options::specialise, 0, 1, false}, {"ray_start_lds", &Options::ray_start_lds, 0, 1, false}, {"slab_log2", &Options::slab_log2, 8, 30, false},
@@ -116,6 +116,10 @@ int mirt_scene_get_option(const MirtScene* sc, const char* name, int* value)
   if (strcmp(name, "stack_lds_capacity") == 0) { *value = STACK_LDS_CAPACITY; return MIRT_OK; }
   if (strcmp(name, "stack_lds_only") == 0) { *value = sc->last_lds_only ? 1 : 0; return MIRT_OK; }
   if (strcmp(name, "stack_lds_slots") == 0) { *value = sc->last_stack_slots; return MIRT_OK; }
+  // ... and about the scene's rays: primitive tests per internal-node visit as the plan of the next render would read it, the
+  // bits of a float (negative: not known).  What the scene holds, nothing polled: a finished measurement is taken by the next
+  // render call or by mirt_get_sample_order, not here
+  if (strcmp(name, "prim_ratio_bits") == 0) { static_assert(sizeof(float) == sizeof(int), "float bits in an int"); memcpy(value, &sc->so_ratio, sizeof(float)); return MIRT_OK; }
   set_error(std::string("mirt_scene_get_option: unknown option ") + name);
   return MIRT_ERR_ARG;
 }

@@ -754,11 +754,29 @@ struct RenderCall {
 // The first thing that plans a call: it settles the facts -- after a material update in place the primitives' share of
 // any_trans / any_rough / colors_finite is known only to the device, and this waits, once, for the update's reduction
 // (update_shading.hip) -- and recombines them with the host's share (planes, lights, exposure).
+// The measurement of a sample order in flight (sample_table_finish), once its event has passed: the order is usable, and the
+// counts its call copied to the pinned words give the scene's primitive tests per internal-node visit.  No wait: a call that
+// finds the event still pending goes on without the order and without the ratio.  `wait`: mirt_get_sample_order.
+static int sample_order_landed(MirtScene* sc, bool wait = false)
+{
+  if (!sc->so_busy) return MIRT_OK;
+  if (wait) MIRT_HIP(hipEventSynchronize(sc->so_ev));
+  else if (hipEventQuery(sc->so_ev) != hipSuccess) return MIRT_OK;
+  sc->so_busy = false;
+  const unsigned long long* n = sc->so_counts_host;      // internal visits, sphere tests, triangle tests
+  sc->so_ratio = (n && !sc->so_ratio_stale && n[0] > 0) ? (float)((double)(n[1] + n[2]) / (double)n[0]) : -1.0f;
+  sc->so_ratio_stale = false;
+  return MIRT_OK;
+}
+
 static int scene_facts(MirtScene* sc, SceneFacts* out)
 {
-  const int rc = settle_facts(sc);
+  int rc = settle_facts(sc);
+  if (rc != MIRT_OK) return rc;
+  rc = sample_order_landed(sc);
   if (rc != MIRT_OK) return rc;
   SceneFacts f;
+  f.prim_ratio = sc->so_ratio;
   f.N = sc->N; f.Nt = sc->Nt; f.grid_ok = sc->grid_ok; f.tree_depth = sc->tree_depth;
   f.has_quantised = sc->root_ref_q != REF_NONE; f.has_wide = sc->root_ref_w != REF_NONE;
   f.colors_finite = sc->colors_finite; f.any_trans = sc->any_trans; f.any_rough = sc->any_rough;
@@ -889,7 +907,7 @@ static int fill_args(const RenderCall& c, RenderCtx& cx, const CallPlan& pl, int
   a.work_counter = cx.counters + 8;
   a.lds_depth = pl.lds_depth;
   a.refill_k = opt.wavefront != 0 ? opt.wf_refill_k : pl.refill_k;
-  a.drain_lanes = opt.drain_lanes; a.init_k = pl.init_k; a.batch_k = opt.batch_k;
+  a.drain_lanes = opt.drain_lanes; a.init_k = pl.init_k; a.batch_k = pl.batch_k;
   a.chunk_shift = chunk_shift;
   h.nodes = a.nodes; h.root_ref = a.root_ref; h.swap_mask = a.swap_mask; h.qparams = a.qparams;
   h.planes = a.planes; h.num_planes = a.num_planes; h.suns = a.suns; h.num_suns = a.num_suns; h.bulbs = a.bulbs; h.num_bulbs = a.num_bulbs; h.shadow_anyhit = a.shadow_anyhit;
@@ -952,7 +970,7 @@ static int sample_table_find(MirtScene* sc, const CallPlan& pl, long long okey, 
 {
   const size_t total = (size_t)pl.total_samples, slab = (size_t)pl.slab_samples_max;
   *ordered = *measure = false;
-  if (sc->so_busy && hipEventQuery(sc->so_ev) == hipSuccess) sc->so_busy = false;      // the measurement in flight has landed
+  MIRT_TRY(sample_order_landed(sc));      // (the measurement in flight has landed?)
   if (sc->so_busy) return MIRT_OK;
   // (the table is a permutation of every launch's sample range: valid for exactly this total and this slab size)
   if (sc->so_key == okey && sc->so_total == pl.total_samples) { *ordered = true; return MIRT_OK; }
@@ -969,8 +987,12 @@ static int sample_table_find(MirtScene* sc, const CallPlan& pl, long long okey, 
       return MIRT_OK;
     }
   }
+  // (the counts behind the scene's ratio of primitive tests to node visits travel with the order: without the two small
+  // buffers for them the order is measured alone)
+  if (!sc->so_counters.get() && sc->so_counters.alloc_raw(12) != hipSuccess) { (void)hipGetLastError(); sc->so_counters.reset(); }
+  if (!sc->so_counts_host.get() && sc->so_counts_host.alloc_raw(3) != hipSuccess) { (void)hipGetLastError(); sc->so_counts_host.reset(); }
   *measure = true;
-  sc->so_key = -1;
+  sc->so_key = -1; sc->so_ratio = -1.0f;      // (another shape: the old order goes, and the ratio with it)
   sc->so_pending_key = okey; sc->so_total = pl.total_samples;
   return MIRT_OK;
 }
@@ -986,7 +1008,7 @@ static int sample_table_finish(MirtScene* sc, hipStream_t stream)
 // measurement in flight is waited for.  (The table outlives camera, geometry and shading updates, as the hand-out does.)
 int get_sample_order(MirtScene* sc, MirtSampleOrderInfo* info, uint32_t* order, uint32_t* keys, uint32_t* sorted_keys)
 {
-  if (sc->so_busy) { MIRT_HIP(hipEventSynchronize(sc->so_ev)); sc->so_busy = false; }
+  MIRT_TRY(sample_order_landed(sc, true));
   if (sc->so_key < 0 || !sc->so_order.get()) {
     set_error("mirt_get_sample_order: the scene has no sample order (the first call of a shape measures one under sched = 2)");
     return MIRT_ERR_STATE;
@@ -1121,6 +1143,11 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
     rc = sample_table_find(sc, pl, okey, &ordered_samples, &measure_samples);
   }
   if (rc != MIRT_OK) return rc;
+  // The call that measures the sample order runs the counting kernels: its node visits and primitive tests are kept as well,
+  // in the scene's own counters where the caller asked for none (RenderArgs::counters; zeroed below, copied out after the last slab).
+  unsigned long long* ratio_counts = nullptr;
+  if (measure_samples && sc->so_counts_host.get()) ratio_counts = count ? cx.counters.get() : sc->so_counters.get();
+  if (ratio_counts && !count) a.counters = ratio_counts;
   const TraceKernel kernel = trace_kernel_for(count || measure_chunks || measure_samples,      // (measure: cost stamps need the step counter)
                                               a.needs_rng && a.rng.mode == 0 && a.rng.chunk_bits == 8, pl);
 
@@ -1128,6 +1155,7 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
   MIRT_HIP(hipEventRecord(cx.ev0, stream));
   if (measure_chunks) MIRT_HIP(hipMemsetAsync(cx.chunk_cost, 0, 4 * nchunks, stream));
   if (count) { MIRT_HIP(hipMemsetAsync(cx.counters, 0, 8 * sizeof(unsigned long long), stream)); MIRT_HIP(hipMemsetAsync(cx.counters + 11, 0, sizeof(unsigned long long), stream)); }
+  else if (ratio_counts) MIRT_HIP(hipMemsetAsync(ratio_counts, 0, 12 * sizeof(unsigned long long), stream));
   cx.wf_trace_ms = -1.0f;
   cx.launches = pl.nslabs;
   cx.node_bytes = pl.node_bytes;
@@ -1155,7 +1183,12 @@ static int render_impl(MirtScene* sc, const MirtRenderParams* p, void* d_rgba8, 
     }
     if (rc != MIRT_OK) return rc;
   }
-  if (measure_samples) rc = sample_table_finish(sc, stream);
+  if (measure_samples) {
+    // (words 3..5 of the counters: internal visits, sphere tests, triangle tests -- flush_counters, shade_common.h)
+    if (ratio_counts) MIRT_HIP(hipMemcpyAsync(sc->so_counts_host.get(), ratio_counts + 3, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    sc->so_ratio_stale = !ratio_counts;
+    rc = sample_table_finish(sc, stream);
+  }
   else if (measure_chunks) rc = chunk_order_finish(cx, nchunks, okey, stream);
   if (rc != MIRT_OK) return rc;
   ++cx.uses;

@@ -45,9 +45,10 @@ struct Options {
   int wavefront = 0;           // 1: the trace / shade kernel pair instead of the single kernel
   int stack_lds_depth = -1;    // traversal-stack entries kept in LDS (-1: the compiled size); tests force the spill path with it
   int refill_k = 0;            // leave the traversal loop when this many lanes wait to shade; 0 = by kind of kernel (plan_call)
-  int batch_k = 8, drain_lanes = 16;
+  int batch_k = 0;             // lanes whose batch ray finished start their next one once this many wait; 0 = by kind of kernel and scene (plan_call: 8)
+  int drain_lanes = 16;
   int leaf_k = 0;              // primitive tests are held back until this many lanes have one pending; 0 = by kind of kernel (8; exact records 4)
-  int reps = 0;                // traversal steps per pass through the loop header; 0 = by kind of kernel (4; wide records 5)
+  int reps = 0;                // traversal steps per pass through the loop header; 0 = by kind of kernel and scene (plan_call: 4; wide records 5)
   int init_k = 0;              // lanes without a sample are refilled once this many wait (1: at every shade phase); 0 = by kind of kernel (plan_call)
   int chunk_shift = 0;         // 0: by frame size
   int trace_waves = 0;         // 0: fill the device
@@ -71,7 +72,27 @@ struct SceneFacts {
   int gi = 0, bounces = 0;
   int num_suns = 0, num_bulbs = 0;
   int tree_depth = -1;                     // D: the most internal nodes on a root-to-leaf path of the built tree (lbvh_build.hip); -1: not known
+  // r: primitive tests per internal-node visit of the scene's rays, (sphere tests + triangle tests) / internal visits, as the
+  // measuring call of the sample order counted them (render.hip, sample_table_find); negative: not known (yet)
+  float prim_ratio = -1.0f;
 };
+
+// Pass length and batch threshold of the sphere-only quantised kernels by r (plan_call).  Primitives are tested in the first
+// step of a pass only, so a lane that reached one waits out the pass: rays that test many primitives per node visit want short
+// passes, rays that walk long chains of nodes between two primitives want the loop header amortised over more steps.  A monotone
+// step function: the first row with r < below.  Two columns: the kernel that starts rays from LDS (start_lds: tenthousand.txt,
+// spiral.txt) and the other sphere-only quantised kernels (deeper trees; measured on synthetic scenes of 1 M and 8 M spheres).
+// Measured, 1920 x 1080 (profiles/r09_ab_runs.txt): r = 0.0013 nothing moves; 0.010 best at 6 / 8; 0.046 and
+// 0.067 (deep trees) at 5 / 8; 0.065 (tenthousand.txt) at 6 / 12; 0.28 (spiral.txt) at 3 / 8.  Nothing was measured between 0.067
+// and 0.28: from 0.1, half again above the largest r that wants long passes, to 0.2, the same margin below spiral.txt's, the
+// values stay the ones from before the rule, as they do above 0.2 for the kernels spiral.txt does not run.
+// What rests on no run: the 0.1 and 0.2 bounds themselves (placed by margin; no syntheticScene(n, 0) has r between 0.067 and
+// 0.28), 5 / 8 below 0.03 in the deep-tree column (its two scenes have r = 0.046 and 0.067; taken over from the row above it), and
+// every kernel but the first column's above 0.067.  A scene measured there moves the bound or the row, nothing else.
+struct PassStep { float below; int reps, batch_k, reps_other, batch_k_other; };
+constexpr int PASS_REPS_DEFAULT = 4, PASS_BATCH_K_DEFAULT = 8;
+constexpr PassStep PASS_STEPS[] = {{0.03f, 6, 8, 5, 8}, {0.1f, 6, 12, 5, 8}, {0.2f, PASS_REPS_DEFAULT, PASS_BATCH_K_DEFAULT, PASS_REPS_DEFAULT, PASS_BATCH_K_DEFAULT},
+                                   {3.0e38f, 3, 8, PASS_REPS_DEFAULT, PASS_BATCH_K_DEFAULT}};
 
 struct CallShape {
   long long npix = 0;                      // pixels of the part (> 0)
@@ -111,7 +132,7 @@ struct CallPlan {
   bool need_pending = false; int pending_slots = 0;
   int skip_unlit = 0, shadow_anyhit = 0;
   // thresholds by kind of kernel
-  int refill_k = 0, init_k = 0, leaf_k = 0, reps = 0, lds_depth = 0;
+  int refill_k = 0, init_k = 0, leaf_k = 0, reps = 0, batch_k = 0, lds_depth = 0;
   bool lds_only = false;                   // the trace kernel compiled without the spill arm of push and pop (SPEC_LDS_STACK)
   bool start_lds = false;                  // ... and with the loop header's ray-start values in LDS, the stack one slot shorter (SPEC_START_LDS)
   HandOut hand_out = HAND_FRAME;
@@ -186,7 +207,16 @@ inline CallPlan plan_call(const SceneFacts& s, const Options& opt, const CallSha
   const int init_k = opt.init_k > 0 ? opt.init_k : (pl.qn ? (pl.notri ? 10 : 8) : 64);
   pl.init_k = init_k < pl.refill_k ? init_k : pl.refill_k;      // (<= refill_k: lanes waiting for a sample count as waiting in the loop header)
   pl.leaf_k = opt.leaf_k > 0 ? opt.leaf_k : (pl.qn ? 8 : 4);      // (exact records, redchair.txt: 4 is 1.3 % better than 8)
-  pl.reps = opt.reps > 0 ? opt.reps : ((pl.qn && !pl.notri) ? 5 : 4);      // (wide records: 5 is 1 % better on the 2 M-primitive scene, worse elsewhere)
+  // Pass length and batch threshold.  By kind of kernel: 4 steps a pass (wide records: 5 is 1 % better on the 2 M-primitive
+  // scene, worse elsewhere), a batch transition once 8 lanes wait for one.  The sphere-only quantised kernels, once the scene's
+  // rays have been counted (prim_ratio >= 0): by PASS_STEPS.  An explicit option wins, each on its own.
+  int reps = (pl.qn && !pl.notri) ? 5 : PASS_REPS_DEFAULT, batch_k = PASS_BATCH_K_DEFAULT;
+  if (pl.qn && pl.notri && s.prim_ratio >= 0.0f) {
+    for (const PassStep& st : PASS_STEPS)
+      if (s.prim_ratio < st.below) { reps = pl.start_lds ? st.reps : st.reps_other; batch_k = pl.start_lds ? st.batch_k : st.batch_k_other; break; }
+  }
+  pl.reps = opt.reps > 0 ? opt.reps : reps;
+  pl.batch_k = opt.batch_k > 0 ? opt.batch_k : batch_k;
 
   // A sparse call is handed out in list order: it neither measures an order nor uses one, and leaves the chunk orders and the
   // scene's by-sample table -- which belong to the dense shape rendered last -- as they are.

@@ -262,6 +262,14 @@ struct MirtScene {
   mirt::DevBuf<uint32_t> so_order, so_keys, so_keys2, so_ws;      // [call's samples], [slab's samples] x 2, the sort's workspace
   long long so_key = -1, so_pending_key = -1, so_total = -1; mirt::Event so_ev; bool so_busy = false;
   long long so_last = 0;                   // samples of the last launch measured: what so_keys / so_keys2 hold (mirt_get_sample_order)
+  // ... and what the measuring call's rays did: primitive tests per internal-node visit (SceneFacts::prim_ratio; negative: not
+  // known).  The measuring call runs the counting kernels; its counters -- the scene's own so_counters where the caller asked for
+  // none -- are copied to so_counts_host ahead of so_ev, and the first call to find so_ev passed takes the ratio (render.hip,
+  // sample_order_landed).  Discarded with the order, and by a geometry update (update.hip, begin_update).
+  float so_ratio = -1.0f;
+  bool so_ratio_stale = false;             // the geometry changed while the measurement was in flight: its counts are not kept
+  mirt::DevBuf<unsigned long long> so_counters;      // device: laid out as RenderCtx::counters, words [0..11]
+  mirt::PinnedBuf<unsigned long long> so_counts_host; // pinned: internal visits, sphere tests, triangle tests of the measuring call
   // rng tables cache
   mirt::RngCache rng;
   // LBVH build timing

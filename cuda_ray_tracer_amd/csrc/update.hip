@@ -55,6 +55,10 @@ int begin_update(MirtScene* sc)
   if (rc != MIRT_OK) return rc;
   sc->built = false;
   sc->updated = true;
+  // What the scene's rays did on the old geometry says nothing about the new one: the ratio behind the plan's pass length goes
+  // (render_plan.h, prim_ratio), until a call measures a sample order again.  The order itself serves any content and stays.
+  sc->so_ratio = -1.0f;
+  sc->so_ratio_stale = sc->so_ratio_stale || sc->so_busy;      // (a measurement in flight counted the old geometry)
   return MIRT_OK;
 }
 

@@ -129,7 +129,8 @@ void mirt_scene_destroy(MirtScene* sc);
  *                         (the scene is immutable): 2 by sample (every sample in its cost class, expensive classes first, positions
  *                         within a class kept; 4 B per sample), 1 by chunk of 64..256 samples (one-slab calls), 0 frame order
  *     "stack_lds_depth", "refill_k", "init_k", "batch_k", "leaf_k", "reps", "drain_lanes", "chunk_shift", "trace_waves",
- *     "wf_pool", "wf_refill_k": tuning (defaults are the measured optima)
+ *     "wf_pool", "wf_refill_k": tuning (defaults are the measured optima; "reps" and "batch_k" at 0, their default, are chosen per
+ *     call: by kind of kernel, and on a sphere-only scene by what its rays did in the call that measured the sample order)
  * Environment variables MIRT_<NAME> override the defaults of the TUNING values once, when the scene is created (the mode
  * switches -- bounds_as_shipped, traversal, wavefront, qnodes, shadow_anyhit, skip_unlit -- only with MIRT_ALLOW_ENV=1); nothing
  * reads the environment during a render.
@@ -142,7 +143,12 @@ void mirt_scene_destroy(MirtScene* sc);
  *                          D <= stack_lds_capacity, the walk is over two-child records (not the wide ones) and "stack_lds_depth"
  *                          is at its default, -1 -- any explicit value, the compiled size included, keeps the general kernel
  *     "stack_lds_slots"    LDS slots of the traversal stack of the kernel the most recent render call ran (0 before a render):
- *                          stack_lds_capacity, or one fewer when "ray_start_lds" chose its kernel */
+ *                          stack_lds_capacity, or one fewer when "ray_start_lds" chose its kernel
+ * ... and one about the scene's rays:
+ *     "prim_ratio_bits"    the bits of a float: primitive tests per internal-node visit, counted by the call that measured the
+ *                          sample order ("sched" = 2) and read by the calls after it; negative while not known -- until a render
+ *                          call or mirt_get_sample_order has found that call finished (the option itself polls nothing and
+ *                          changes nothing), after a geometry update, for a scene whose rays visit no node */
 #define MIRT_TRAVERSAL_REFERENCE 0
 #define MIRT_TRAVERSAL_ORDERED 1
 #define MIRT_TRAVERSAL_ORDERED_ALL 2

@@ -544,6 +544,39 @@ def _ray_tensors(d_rays, d_hits, *features):
     return n, tensors + _tensors((d_hits, "d_hits", _HIT, [n, 6]), *((x, name, _F32, [n, 8]) for x, name in features))
 
 
+def _record_tensors(rows, d_hits, d_counts, d_features=None, max_k=8, check_k=None):
+    """_tensors for a record query (trace_rays_multi, closest_points_multi, overlap_boxes), in this order: `rows` = (tensor, name,
+    width), float32 [n, width]; d_hits, a 4-byte dtype [n, k, 6] with k at most max_k (None: k = 0); d_counts, int32 [n], which a
+    call with k = 0 needs; check_k(k), the caller's own check; d_features, float32 [n, k, 8].  Returns the (tensor, name) pairs,
+    n and k."""
+    x, name, width = rows
+    tensors = _tensors((x, name, _F32, [None, width]))
+    n, k = x.shape[0], 0
+    if d_hits is not None:
+        tensors += _tensors((d_hits, "d_hits", _HIT, [n, None, 6]))
+        k = d_hits.shape[1]
+        if k > max_k:
+            raise ValueError(f"d_hits has shape {list(d_hits.shape)}; expected [n, k, 6] with k at most {max_k}")
+    if d_counts is not None:
+        tensors += _tensors((d_counts, "d_counts", _INT, [n]))
+    elif k == 0:
+        raise ValueError("a call without hit records (d_hits None or k = 0) needs d_counts")
+    if check_k is not None:
+        check_k(k)
+    if d_features is not None:
+        tensors += _tensors((d_features, "d_features", _F32, [n, k, 8]))
+    return tensors, n, k
+
+
+def _count_tensor(rows, d_counts=None):
+    """For the count wrappers: checks `rows` = (tensor, name, width) as _record_tensors does and returns d_counts or, without one, a
+    new int32 [n] tensor on the rows' device."""
+    import torch
+    x, name, width = rows
+    _tensors((x, name, _F32, [None, width]))
+    return d_counts if d_counts is not None else torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
+
+
 def trace_rays(raw, d_rays, d_hits, any_hit=False, stream=None):
     """mirt_trace_rays: closest hit (hitNearest, draw.cu:292-318) or, with any_hit, occlusion of every ray of d_rays (float32
     [n, 8], MirtRay rows: pack_rays) into d_hits (a 4-byte dtype, [n, 6], MirtHit rows: unpack_hits).  Both contiguous and on

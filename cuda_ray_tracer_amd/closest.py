@@ -6,12 +6,8 @@ tests/test_extension_abi.py holds the table to the header the way tests/test_bin
 
 Needs ctypes only: torch and numpy are imported when a call needs them.
 """
-import ctypes as C
-
 from . import binding
-from .binding import _check
-
-_int, _i64, _u32, _vp = C.c_int, C.c_int64, C.c_uint32, C.c_void_p
+from .binding import _check, _int, _i64, _u32, _vp
 
 # symbol -> (restype, argtypes): every entry point of include/mirt_closest.h, in the header's order
 CLOSEST_SIGNATURES = {

@@ -2,17 +2,13 @@
 
 mirt_contacts.h is an extension header like mirt_closest.h and mirt_multihit.h: binding.SIGNATURES stays the table of
 include/mirt.h, the other modules' tables those of their headers, and the one entry point more lives here.
-tests/test_contacts_abi.py holds the table to the header the way tests/test_binding_header.py holds binding.py to mirt.h.
+tests/test_extension_abi.py holds the table to the header the way tests/test_binding_header.py holds binding.py to mirt.h.
 
 Needs ctypes only: torch and numpy are imported when a call needs them.  The rows are closest.pack_points', the records are read
 by api.unpack_hits (d_hits.reshape(-1, 6)).
 """
-import ctypes as C
-
 from . import binding
-from .binding import _check
-
-_int, _i64, _u32, _vp = C.c_int, C.c_int64, C.c_uint32, C.c_void_p
+from .binding import _check, _int, _i64, _u32, _vp
 
 MIRT_CONTACTS_MAX_K = 8
 
@@ -35,20 +31,7 @@ def closest_points_multi(raw, d_points, d_hits, d_counts=None, d_features=None, 
     receives each record's closest point and normal in hit_features' layout.  d_hits None: a count-only call.  All tensors
     contiguous, distinct and on the scene's device.  Asynchronous on `stream` (default: torch's current stream)."""
     from . import api
-    tensors = api._tensors((d_points, "d_points", api._F32, [None, 4]))
-    n = d_points.shape[0]
-    k = 0
-    if d_hits is not None:
-        tensors += api._tensors((d_hits, "d_hits", api._HIT, [n, None, 6]))
-        k = d_hits.shape[1]
-        if k > MIRT_CONTACTS_MAX_K:
-            raise ValueError(f"d_hits has shape {list(d_hits.shape)}; expected [n, k, 6] with k at most {MIRT_CONTACTS_MAX_K}")
-    if d_counts is not None:
-        tensors += api._tensors((d_counts, "d_counts", api._INT, [n]))
-    elif k == 0:
-        raise ValueError("a call without hit records (d_hits None or k = 0) needs d_counts")
-    if d_features is not None:
-        tensors += api._tensors((d_features, "d_features", api._F32, [n, k, 8]))
+    tensors, n, k = api._record_tensors((d_points, "d_points", 4), d_hits, d_counts, d_features, max_k=MIRT_CONTACTS_MAX_K)
     api._on_device(tensors, raw.device)
     _check(lib().mirt_closest_points_multi(raw._h, api._ptr(d_points), n, k, api._ptr(d_hits), api._ptr(d_counts), api._ptr(d_features), 0,
                                            api._stream_ptr(stream)))
@@ -58,10 +41,7 @@ def count_within(raw, d_points, d_counts=None, stream=None):
     """The number of surfaces nearer than R to every row (qx, qy, qz, R) of d_points (float32 [n, 4]), into d_counts (int32 [n]; a new
     tensor on the rows' device if None), which is returned: closest_points_multi with k = 0.  A count with R = inf visits the
     whole scene."""
-    import torch
     from . import api
-    api._tensors((d_points, "d_points", api._F32, [None, 4]))
-    if d_counts is None:
-        d_counts = torch.empty(d_points.shape[0], dtype=torch.int32, device=d_points.device)
+    d_counts = api._count_tensor((d_points, "d_points", 4), d_counts)
     closest_points_multi(raw, d_points, None, d_counts, stream=stream)
     return d_counts

@@ -7,16 +7,12 @@ mirt.h.
 
 Needs ctypes only: torch and numpy are imported when a call needs them.
 """
-import ctypes as C
-
 from . import binding
-from .binding import _check
-
-_int, _i64, _u32, _vp, _float = C.c_int, C.c_int64, C.c_uint32, C.c_void_p, C.c_float
+from .binding import _check, _int, _i64, _u32, _vp, _f
 
 # symbol -> (restype, argtypes): every entry point of include/mirt_indirect.h, in the header's order
 INDIRECT_SIGNATURES = {
-    "mirt_indirect_light": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _float, _vp, _vp, _u32, _vp]),
+    "mirt_indirect_light": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _f, _vp, _vp, _u32, _vp]),
 }
 
 

@@ -6,14 +6,10 @@ to mirt.h.
 
 Needs ctypes only: torch is imported when a call needs it, numpy not at all.
 """
-import ctypes as C
-
 from . import binding
-from .binding import _check
+from .binding import _check, _int, _i64, _u32, _vp
 
 MIRT_LIGHT_RAW = 1
-
-_int, _i64, _u32, _vp = C.c_int, C.c_int64, C.c_uint32, C.c_void_p
 
 # symbol -> (restype, argtypes): every entry point of include/mirt_light.h, in the header's order
 LIGHT_SIGNATURES = {

@@ -6,12 +6,8 @@ tests/test_extension_abi.py holds the table to the header the way tests/test_bin
 
 Needs ctypes only: torch and numpy are imported when a call needs them.
 """
-import ctypes as C
-
 from . import binding
-from .binding import _check
-
-_int, _i64, _u32, _vp = C.c_int, C.c_int64, C.c_uint32, C.c_void_p
+from .binding import _check, _int, _i64, _u32, _vp
 
 MIRT_MULTIHIT_MAX_K = 8
 
@@ -33,18 +29,7 @@ def trace_rays_multi(raw, d_rays, d_hits, d_counts=None, stream=None):
     d_counts (int32 or uint32 [n]) is given, the number of all its hits, which may exceed k.  d_hits None: a count-only call.  All
     tensors contiguous, distinct and on the scene's device.  Asynchronous on `stream` (default: torch's current stream)."""
     from . import api
-    tensors = api._tensors((d_rays, "d_rays", api._F32, [None, 8]))
-    n = d_rays.shape[0]
-    k = 0
-    if d_hits is not None:
-        tensors += api._tensors((d_hits, "d_hits", api._HIT, [n, None, 6]))
-        k = d_hits.shape[1]
-        if k > MIRT_MULTIHIT_MAX_K:
-            raise ValueError(f"d_hits has shape {list(d_hits.shape)}; expected [n, k, 6] with k at most {MIRT_MULTIHIT_MAX_K}")
-    if d_counts is not None:
-        tensors += api._tensors((d_counts, "d_counts", api._INT, [n]))
-    elif k == 0:
-        raise ValueError("a call without hit records (d_hits None or k = 0) needs d_counts")
+    tensors, n, k = api._record_tensors((d_rays, "d_rays", 8), d_hits, d_counts, max_k=MIRT_MULTIHIT_MAX_K)
     api._on_device(tensors, raw.device)
     _check(lib().mirt_trace_rays_multi(raw._h, api._ptr(d_rays), n, k, api._ptr(d_hits), api._ptr(d_counts), 0, api._stream_ptr(stream)))
 
@@ -52,9 +37,7 @@ def trace_rays_multi(raw, d_rays, d_hits, d_counts=None, stream=None):
 def count_hits(raw, d_rays, stream=None):
     """The number of hits of every ray of d_rays (float32 [n, 8]) before its tmax, as a new int32 [n] tensor on the rays' device:
     trace_rays_multi with k = 0."""
-    import torch
     from . import api
-    api._tensors((d_rays, "d_rays", api._F32, [None, 8]))
-    counts = torch.empty(d_rays.shape[0], dtype=torch.int32, device=d_rays.device)
+    counts = api._count_tensor((d_rays, "d_rays", 8))
     trace_rays_multi(raw, d_rays, None, counts, stream=stream)
     return counts

@@ -2,17 +2,13 @@
 
 mirt_overlap.h is an extension header like mirt_contacts.h and mirt_spherecast.h: binding.SIGNATURES stays the table of
 include/mirt.h, the other modules' tables those of their headers, and the one entry point more lives here.
-tests/test_overlap_abi.py holds the table to the header the way tests/test_binding_header.py holds binding.py to mirt.h.
+tests/test_extension_abi.py holds the table to the header the way tests/test_binding_header.py holds binding.py to mirt.h.
 
 Needs ctypes only: torch and numpy are imported when a call needs them.  The records are read by api.unpack_hits
 (d_hits.reshape(-1, 6)).
 """
-import ctypes as C
-
 from . import binding
-from .binding import _check
-
-_int, _i64, _u32, _vp = C.c_int, C.c_int64, C.c_uint32, C.c_void_p
+from .binding import _check, _int, _i64, _u32, _vp
 
 MIRT_OVERLAP_MAX_K = 8
 MIRT_OVERLAP_ANY = 1
@@ -38,22 +34,12 @@ def overlap_boxes(raw, d_boxes, d_hits, d_counts=None, d_features=None, any_over
     (does the box touch anything) and the walk ends at the first surface found.  All tensors contiguous, distinct and on the
     scene's device.  Asynchronous on `stream` (default: torch's current stream)."""
     from . import api
-    tensors = api._tensors((d_boxes, "d_boxes", api._F32, [None, 8]))
-    n = d_boxes.shape[0]
-    k = 0
-    if d_hits is not None:
-        tensors += api._tensors((d_hits, "d_hits", api._HIT, [n, None, 6]))
-        k = d_hits.shape[1]
-        if k > MIRT_OVERLAP_MAX_K:
-            raise ValueError(f"d_hits has shape {list(d_hits.shape)}; expected [n, k, 6] with k at most {MIRT_OVERLAP_MAX_K}")
-    if d_counts is not None:
-        tensors += api._tensors((d_counts, "d_counts", api._INT, [n]))
-    elif k == 0:
-        raise ValueError("a call without hit records (d_hits None or k = 0) needs d_counts")
-    if any_overlap and k != 0:
-        raise ValueError("any_overlap is a count-only call: d_hits must be None (or k = 0)")
-    if d_features is not None:
-        tensors += api._tensors((d_features, "d_features", api._F32, [n, k, 8]))
+
+    def count_only(k):
+        if any_overlap and k != 0:
+            raise ValueError("any_overlap is a count-only call: d_hits must be None (or k = 0)")
+
+    tensors, n, k = api._record_tensors((d_boxes, "d_boxes", 8), d_hits, d_counts, d_features, max_k=MIRT_OVERLAP_MAX_K, check_k=count_only)
     api._on_device(tensors, raw.device)
     _check(lib().mirt_overlap_boxes(raw._h, api._ptr(d_boxes), n, k, api._ptr(d_hits), api._ptr(d_counts), api._ptr(d_features),
                                     MIRT_OVERLAP_ANY if any_overlap else 0, api._stream_ptr(stream)))
@@ -62,11 +48,8 @@ def overlap_boxes(raw, d_boxes, d_hits, d_counts=None, d_features=None, any_over
 def count_overlaps(raw, d_boxes, d_counts=None, any_overlap=False, stream=None):
     """The number of surfaces every row of d_boxes (float32 [n, 8]) touches -- with any_overlap 1 or 0: whether it touches any --
     into d_counts (int32 [n]; a new tensor on the rows' device if None), which is returned: overlap_boxes with k = 0."""
-    import torch
     from . import api
-    api._tensors((d_boxes, "d_boxes", api._F32, [None, 8]))
-    if d_counts is None:
-        d_counts = torch.empty(d_boxes.shape[0], dtype=torch.int32, device=d_boxes.device)
+    d_counts = api._count_tensor((d_boxes, "d_boxes", 8), d_counts)
     overlap_boxes(raw, d_boxes, None, d_counts, any_overlap=any_overlap, stream=stream)
     return d_counts
 

@@ -1,7 +1,7 @@
 """Overlap lists on a built scene: include_ext/mirt_overlap_list.h restated for ctypes, and the calls over it.
 
 mirt_overlap_list.h is an extension header like mirt_overlap.h: binding.SIGNATURES stays the table of include/mirt.h, the other
-modules' tables those of their headers, and the three entry points more live here.  tests/test_overlap_list_abi.py holds the table
+modules' tables those of their headers, and the three entry points more live here.  tests/test_extension_abi.py holds the table
 to the header the way tests/test_binding_header.py holds binding.py to mirt.h.
 
 A list is count (overlap.count_overlaps), exclusive scan (list_offsets), fill (overlap_list); overlap_lists does the three.
@@ -12,12 +12,8 @@ The package exports this module's function overlap_list, so the attribute cuda_r
 module itself is importlib.import_module("cuda_ray_tracer_amd.overlap_list") (`from cuda_ray_tracer_amd.overlap_list import ...`
 works as usual).
 """
-import ctypes as C
-
 from . import binding
-from .binding import _check
-
-_int, _i64, _vp = C.c_int, C.c_int64, C.c_void_p
+from .binding import _check, _int, _i64, _vp
 
 # symbol -> (restype, argtypes): every entry point of include_ext/mirt_overlap_list.h, in the header's order
 OVERLAP_LIST_SIGNATURES = {

@@ -1,7 +1,7 @@
 """Ray and ball lists on a built scene: include_ext/mirt_query_lists.h restated for ctypes, and the calls over it.
 
 mirt_query_lists.h is an extension header like mirt_overlap_list.h: binding.SIGNATURES stays the table of include/mirt.h, the other
-modules' tables those of their headers, and the two entry points more live here.  tests/test_query_lists_abi.py holds the table to
+modules' tables those of their headers, and the two entry points more live here.  tests/test_extension_abi.py holds the table to
 the header the way tests/test_binding_header.py holds binding.py to mirt.h.
 
 A list is count (multihit.count_hits / contacts.count_within), exclusive scan (overlap_list.list_offsets), fill (ray_list /
@@ -9,12 +9,8 @@ ball_list); ray_lists and ball_lists do the three.  A word is kind << 30 | id (o
 
 Needs ctypes only: torch and numpy are imported when a call needs them.
 """
-import ctypes as C
-
 from . import binding
-from .binding import _check
-
-_int, _i64, _u32, _vp = C.c_int, C.c_int64, C.c_uint32, C.c_void_p
+from .binding import _check, _int, _i64, _u32, _vp
 
 # symbol -> (restype, argtypes): every entry point of include_ext/mirt_query_lists.h, in the header's order
 QUERY_LISTS_SIGNATURES = {

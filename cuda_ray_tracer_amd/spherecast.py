@@ -2,16 +2,12 @@
 
 mirt_spherecast.h is an extension header like mirt_closest.h and mirt_contacts.h: binding.SIGNATURES stays the table of
 include/mirt.h, the other modules' tables those of their headers, and the one entry point more lives here.
-tests/test_spherecast_abi.py holds the table to the header the way tests/test_binding_header.py holds binding.py to mirt.h.
+tests/test_extension_abi.py holds the table to the header the way tests/test_binding_header.py holds binding.py to mirt.h.
 
 Needs ctypes only: torch and numpy are imported when a call needs them.  The records are read by api.unpack_hits.
 """
-import ctypes as C
-
 from . import binding
-from .binding import _check
-
-_int, _i64, _u32, _vp = C.c_int, C.c_int64, C.c_uint32, C.c_void_p
+from .binding import _check, _int, _i64, _u32, _vp
 
 MIRT_CAST_ANY_HIT = 1
 

@@ -6,16 +6,12 @@ the table to the header the way tests/test_binding_header.py holds binding.py to
 
 Needs ctypes only: torch and numpy are imported when a call needs them.
 """
-import ctypes as C
-
 from . import binding
-from .binding import _check
-
-_int, _i64, _u32, _vp, _float = C.c_int, C.c_int64, C.c_uint32, C.c_void_p, C.c_float
+from .binding import _check, _int, _i64, _u32, _vp, _f
 
 # symbol -> (restype, argtypes): every entry point of include/mirt_visibility.h, in the header's order
 VISIBILITY_SIGNATURES = {
-    "mirt_hemisphere_visibility": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _float, _vp, _vp, _u32, _vp]),
+    "mirt_hemisphere_visibility": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _f, _vp, _vp, _u32, _vp]),
 }
 
 GOLDEN_ANGLE = 2.399963229728653

@@ -1,101 +1,38 @@
-"""Contact queries (include_ext/mirt_contacts.h: mirt_closest_points_multi): the header against contacts.py's signature table and
-the built library (what tests/test_extension_abi.py holds per row for the headers under include/), the wrappers' checks, the
+"""Contact queries (include_ext/mirt_contacts.h: mirt_closest_points_multi): what the header's text says, the wrappers' checks, the
 kernel's code generation, and the numpy restatement of the header (tests/contacts_ref.py) against itself over the oracle's tree:
 on the inputs the GPU tests use, the pruned walk with either bound rule gives the brute force's bits on every row, and the
-records, counts and order have the properties the header states.  No GPU needed."""
-import ctypes as C
+records, counts and order have the properties the header states.  The header against contacts.py's signature table and the built
+library is a row of tests/test_extension_abi.py.  No GPU needed."""
 import functools
 import os
 import re
-import subprocess
-import sys
 import types
 
 import numpy as np
 import pytest
 
 import cuda_ray_tracer_amd as m
-from cuda_ray_tracer_amd import api, binding, contacts
-from cuda_ray_tracer_amd import build as B
 import closest_ref as cr
 import contacts_ref as kr
 import edge_scenes
 import pyscene
-from codegen_lib import _kernel_body, _resource_usage, _strip
-from test_binding_header import compare_prototypes, constants, prototypes
+from codegen_lib import _kernel_body, _resource_usage
 from test_closest_abi import _oracle_tree, _points_about, with_tight_radii
 from test_multihit_abi import dense_scene_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include_ext", "mirt_contacts.h")
-SYMBOL = "mirt_closest_points_multi"
-PTR, I32, I64, U32 = "pointer", (4, True, False), (8, True, False), (4, False, False)
 f32 = np.float32
 u32 = np.uint32
-INF = float("inf")
 
 
-# ---- header, table, library ----------------------------------------------------------------------------------------------------------
-def test_the_header_agrees_with_the_signature_table():
-    header, table = _strip(HEADER), contacts.CONTACTS_SIGNATURES
-    assert [name for name, _, _ in prototypes(header)] == list(table) == [SYMBOL]
-    assert sorted(set(re.findall(r"\b(mirt_[a-z0-9_]+)\s*\(", header))) == [SYMBOL]
-    assert compare_prototypes(header, table) == []
-    assert prototypes(header)[0] == (SYMBOL, I32, [PTR, PTR, I64, I32, PTR, PTR, PTR, U32, PTR])
-    assert constants(header) == {"MIRT_CONTACTS_MAX_K": 8} and contacts.MIRT_CONTACTS_MAX_K == 8
-    assert re.search(r'^#include "\.\./include/mirt\.h"$', header, flags=re.M)
-    # a table that disagrees is a mismatch: in a parameter's type, and in the number of parameters
-    restype, argtypes = table[SYMBOL]
-    doctored = [C.c_int if t is C.c_int64 else t for t in argtypes]
-    assert compare_prototypes(header, {SYMBOL: (restype, doctored)}) == [f"{SYMBOL}: parameter 2 is (8, True, False), the table says (4, True, False)"]
-    assert compare_prototypes(header, {SYMBOL: (restype, argtypes[:-1])}) == [f"{SYMBOL}: 9 parameters, the table has 8"]
-    assert re.search(r"#define MIRT_VERSION 3\b", open(os.path.join(ROOT, "include", "mirt.h")).read())
-
-
+# ---- header, wrappers ----------------------------------------------------------------------------------------------------------------
 def test_the_header_adopts_the_candidates_of_mirt_closest_h_and_states_the_rules():
     text = " ".join(open(HEADER).read().replace(" *", " ").split())
     assert "Candidates are not redefined here" in text and "never by the tree" in text and "(dist, kind, id)" in text
     assert "bit for bit, on every row without exception" in text
     assert "B is R for the whole walk" in text and "until the list holds k entries" in text and "sigma = 2^-18" in text
     assert "R = +inf visits every leaf" in text
-
-
-def test_mirt_h_and_the_other_tables_do_not_know_the_extension():
-    assert SYMBOL not in open(os.path.join(ROOT, "include", "mirt.h")).read() and SYMBOL not in binding.SIGNATURES
-    assert not hasattr(binding, "MIRT_CONTACTS_MAX_K")
-    for name in os.listdir(os.path.join(ROOT, "include")):
-        assert SYMBOL not in open(os.path.join(ROOT, "include", name)).read(), name
-
-
-def test_library_exports_the_symbol_and_the_signature_is_applied():
-    out = subprocess.run(["nm", "-D", "--defined-only", B.LIB], capture_output=True, text=True, check=True).stdout
-    assert re.search(r"\bT %s$" % SYMBOL, out, flags=re.M)
-    f = getattr(contacts.lib(), SYMBOL)
-    assert f.restype is C.c_int and list(f.argtypes) == contacts.CONTACTS_SIGNATURES[SYMBOL][1]
-    for name in ("closest_points_multi", "count_within"):
-        assert getattr(m, name) is getattr(contacts, name) is getattr(api, name) and name in m.__all__, name
-
-
-def test_the_module_needs_neither_torch_nor_numpy():
-    code = "import sys; import cuda_ray_tracer_amd.contacts; assert 'torch' not in sys.modules and 'numpy' not in sys.modules, sorted(sys.modules)"
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-
-
-def test_the_build_depends_on_the_header_and_the_kernel():
-    deps = [os.path.normpath(d) for d in B._all_deps()]
-    assert HEADER in deps and os.path.join(B.CSRC, "closest_multi.hip") in deps
-    assert os.path.join(B.CSRC, "point_query.h") in deps and os.path.join(B.CSRC, "key_list.h") in deps
-    assert "closest_multi.hip" in B.LIB_SOURCES
-
-
-def test_null_scene_is_an_argument_error():
-    f = getattr(contacts.lib(), SYMBOL)
-    for args in [(None, 0, 0, None, None, None, 0, None), (None, 5, 4, None, None, None, 0, None)]:
-        # (another call's message first, so that the one read back is this call's)
-        assert m.lib().mirt_build_lbvh(None, None, None) == 3 and SYMBOL.encode() not in m.lib().mirt_last_error()
-        assert f(None, *args) == 3
-        assert m.lib().mirt_last_error() == SYMBOL.encode() + b": null scene"
 
 
 def test_wrappers_check_their_tensors_before_calling_the_library():

@@ -1,81 +1,25 @@
 """Direct light at surface points (include/mirt_light.h: mirt_direct_light): the wrappers' checks, the kernel's code generation,
 and tests/light_ref.py -- the numpy restatement of the header's text -- against the oracle's renders of matte-white scenes.  The
-header against lighting.py's signature table and the built library, as this file has held them since the first extension;
-tests/test_extension_abi.py holds every extension header, this one among them, by one table.  No GPU needed."""
-import ctypes as C
-import os
-import re
-import subprocess
-import sys
+header against lighting.py's signature table and the built library is a row of tests/test_extension_abi.py.  No GPU needed."""
 import types
 
 import numpy as np
 import pytest
 
 import cuda_ray_tracer_amd as m
-from cuda_ray_tracer_amd import api, binding, lighting
-from cuda_ray_tracer_amd import build as B
 import denoise_ref as dr
 import f64_arbiter as arb
 import light_ref
 import light_scenes
 import oracle_lib as ol
 import pyscene
-from test_binding_header import compare_prototypes, constants, prototypes
 from test_denoise_abi import _pinhole_rays
-from codegen_lib import _resource_usage, _strip
+from codegen_lib import _resource_usage
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
-HEADER = _strip(os.path.join(ROOT, "include", "mirt_light.h"))
 
 
-# ---- header, signature table, library ---------------------------------------------------------------------------------------------
-def test_the_extension_header_agrees_with_the_signature_table():
-    assert [name for name, _, _ in prototypes(HEADER)] == list(lighting.LIGHT_SIGNATURES) == ["mirt_direct_light"]
-    assert sorted(set(re.findall(r"\b(mirt_[a-z0-9_]+)\s*\(", HEADER))) == ["mirt_direct_light"]
-    assert compare_prototypes(HEADER, lighting.LIGHT_SIGNATURES) == []
-    assert prototypes(HEADER)[0] == ("mirt_direct_light", (4, True, False), ["pointer", "pointer", (8, True, False), "pointer", "pointer",
-                                                                             (4, False, False), "pointer"])
-    assert constants(HEADER) == {"MIRT_LIGHT_RAW": 1} and lighting.MIRT_LIGHT_RAW == 1 and api.MIRT_LIGHT_RAW == 1
-    assert re.search(r'^#include "mirt.h"$', HEADER, flags=re.M)
-    # a table that disagrees is a mismatch
-    restype, argtypes = lighting.LIGHT_SIGNATURES["mirt_direct_light"]
-    wrong = compare_prototypes(HEADER, {"mirt_direct_light": (restype, [C.c_int if t is C.c_int64 else t for t in argtypes])})
-    assert wrong == ["mirt_direct_light: parameter 2 is (8, True, False), the table says (4, True, False)"]
-
-
-def test_mirt_h_and_its_table_do_not_know_the_extension():
-    assert "mirt_direct_light" not in open(os.path.join(ROOT, "include", "mirt.h")).read()
-    assert "mirt_direct_light" not in binding.SIGNATURES and not hasattr(binding, "MIRT_LIGHT_RAW")
-
-
-def test_library_exports_the_symbol_and_the_signature_is_applied():
-    out = subprocess.run(["nm", "-D", "--defined-only", B.LIB], capture_output=True, text=True, check=True).stdout
-    assert re.search(r"\bT mirt_direct_light$", out, flags=re.M)
-    f = lighting.lib().mirt_direct_light
-    assert f.restype is C.c_int and list(f.argtypes) == lighting.LIGHT_SIGNATURES["mirt_direct_light"][1]
-    assert m.direct_light is lighting.direct_light is api.direct_light and m.pack_features is lighting.pack_features
-    assert m.direct_light_frame is lighting.direct_light_frame
-
-
-def test_the_lighting_module_needs_neither_torch_nor_numpy():
-    code = "import sys; import cuda_ray_tracer_amd.lighting; assert 'torch' not in sys.modules and 'numpy' not in sys.modules, sorted(sys.modules)"
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-
-
-def test_the_build_depends_on_the_extension_header():
-    deps = [os.path.normpath(d) for d in B._all_deps()]
-    assert os.path.join(ROOT, "include", "mirt_light.h") in deps and "light.hip" in B.LIB_SOURCES
-
-
-def test_null_scene_is_an_argument_error():
-    L = lighting.lib()
-    assert L.mirt_direct_light(None, None, 0, None, None, 0, None) == 3
-    assert L.mirt_direct_light(None, None, 5, None, None, 1, None) == 3
-
-
+# ---- wrappers ---------------------------------------------------------------------------------------------------------------------
 def test_wrappers_check_their_tensors_before_calling_the_library():
     import torch
     raw = types.SimpleNamespace(device=0, _h=None)

@@ -1,38 +1,30 @@
-"""Box overlap queries (include_ext/mirt_overlap.h: mirt_overlap_boxes): the header against overlap.py's signature table and the
-built library, the wrappers' checks, the kernel's code generation, and the numpy restatement of the header
-(tests/overlap_ref.py) against float64 by other methods and against itself over the oracle's tree: on the inputs the GPU tests
-use, the pruned walk gives the brute force's bits on every row in either child order, the any-overlap walk agrees on "non-empty",
-the counts are bracketed by the contact query's, and the records, counts and order have the properties the header states.
-No GPU needed."""
-import ctypes as C
+"""Box overlap queries (include_ext/mirt_overlap.h: mirt_overlap_boxes): what the header's text says, the wrappers' checks, the
+kernel's code generation, and the numpy restatement of the header (tests/overlap_ref.py) against float64 by other methods and
+against itself over the oracle's tree: on the inputs the GPU tests use, the pruned walk gives the brute force's bits on every row in
+either child order, the any-overlap walk agrees on "non-empty", the counts are bracketed by the contact query's, and the records,
+counts and order have the properties the header states.  The header against overlap.py's signature table and the built library is
+a row of tests/test_extension_abi.py.  No GPU needed."""
 import functools
 import os
 import re
-import subprocess
-import sys
 import types
 
 import numpy as np
 import pytest
 
 import cuda_ray_tracer_amd as m
-from cuda_ray_tracer_amd import api, binding, overlap
-from cuda_ray_tracer_amd import build as B
 import closest_ref as cr
 import contacts_ref as kr
 import edge_scenes
 import light_scenes
 import overlap_ref as ovr
 import pyscene
-from codegen_lib import _kernel_body, _resource_usage, _strip
-from test_binding_header import compare_prototypes, constants, prototypes
+from codegen_lib import _kernel_body, _resource_usage
 from test_closest_abi import _oracle_tree, _points_about, _well_shaped_scene
 from test_multihit_abi import dense_scene_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include_ext", "mirt_overlap.h")
-SYMBOL = "mirt_overlap_boxes"
-PTR, I32, I64, U32 = "pointer", (4, True, False), (8, True, False), (4, False, False)
 f32 = np.float32
 u32 = np.uint32
 u64 = np.uint64
@@ -40,23 +32,7 @@ INF = float("inf")
 NAN = float("nan")
 
 
-# ---- header, table, library ----------------------------------------------------------------------------------------------------------
-def test_the_header_agrees_with_the_signature_table():
-    header, table = _strip(HEADER), overlap.OVERLAP_SIGNATURES
-    assert [name for name, _, _ in prototypes(header)] == list(table) == [SYMBOL]
-    assert sorted(set(re.findall(r"\b(mirt_[a-z0-9_]+)\s*\(", header))) == [SYMBOL]
-    assert compare_prototypes(header, table) == []
-    assert prototypes(header)[0] == (SYMBOL, I32, [PTR, PTR, I64, I32, PTR, PTR, PTR, U32, PTR])
-    assert constants(header) == {"MIRT_OVERLAP_MAX_K": 8, "MIRT_OVERLAP_ANY": 1}
-    assert overlap.MIRT_OVERLAP_MAX_K == 8 and overlap.MIRT_OVERLAP_ANY == 1
-    assert re.search(r'^#include "\.\./include/mirt\.h"$', header, flags=re.M)
-    restype, argtypes = table[SYMBOL]
-    doctored = [C.c_int if t is C.c_int64 else t for t in argtypes]
-    assert compare_prototypes(header, {SYMBOL: (restype, doctored)}) == [f"{SYMBOL}: parameter 2 is (8, True, False), the table says (4, True, False)"]
-    assert compare_prototypes(header, {SYMBOL: (restype, argtypes[:-1])}) == [f"{SYMBOL}: 9 parameters, the table has 8"]
-    assert re.search(r"#define MIRT_VERSION 3\b", open(os.path.join(ROOT, "include", "mirt.h")).read())
-
-
+# ---- header, wrappers ----------------------------------------------------------------------------------------------------------------
 def test_the_header_spells_out_the_tests_and_states_the_rules():
     text = " ".join(open(HEADER).read().replace(" *", " ").split())
     assert "never by the tree" in text and "(dist, kind, id)" in text and "mirt_closest.h's, word for word" in text
@@ -65,49 +41,13 @@ def test_the_header_spells_out_the_tests_and_states_the_rules():
     assert "sigma = 2^-18" in text and "There is no shrinking bound" in text and "A box without volume" in text
 
 
-def test_mirt_h_and_the_other_tables_do_not_know_the_extension():
-    from cuda_ray_tracer_amd import closest, contacts, multihit, spherecast
-    assert SYMBOL not in open(os.path.join(ROOT, "include", "mirt.h")).read() and SYMBOL not in binding.SIGNATURES
-    assert not hasattr(binding, "MIRT_OVERLAP_MAX_K")
-    for name in os.listdir(os.path.join(ROOT, "include")):
-        assert SYMBOL not in open(os.path.join(ROOT, "include", name)).read(), name
-    for name in os.listdir(os.path.join(ROOT, "include_ext")):
-        if name != "mirt_overlap.h":
-            assert SYMBOL not in open(os.path.join(ROOT, "include_ext", name)).read(), name
-    for table in (contacts.CONTACTS_SIGNATURES, spherecast.SPHERECAST_SIGNATURES):
-        assert SYMBOL not in table
-    assert not any(SYMBOL in vars(mod).get(t, {}) for mod in (closest, multihit) for t in vars(mod) if t.endswith("_SIGNATURES"))
-
-
-def test_library_exports_the_symbol_and_the_signature_is_applied():
-    out = subprocess.run(["nm", "-D", "--defined-only", B.LIB], capture_output=True, text=True, check=True).stdout
-    assert re.search(r"\bT %s$" % SYMBOL, out, flags=re.M)
-    f = getattr(overlap.lib(), SYMBOL)
-    assert f.restype is C.c_int and list(f.argtypes) == overlap.OVERLAP_SIGNATURES[SYMBOL][1]
-    for name in ("overlap_boxes", "count_overlaps", "pack_boxes", "voxel_rows", "occupancy_grid"):
-        assert getattr(m, name) is getattr(overlap, name) is getattr(api, name) and name in m.__all__, name
-
-
-def test_the_module_needs_neither_torch_nor_numpy():
-    code = "import sys; import cuda_ray_tracer_amd.overlap; assert 'torch' not in sys.modules and 'numpy' not in sys.modules, sorted(sys.modules)"
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-
-
-def test_the_build_depends_on_the_header_and_the_kernel():
-    deps = [os.path.normpath(d) for d in B._all_deps()]
-    assert HEADER in deps and os.path.join(B.CSRC, "overlap.hip") in deps
-    assert os.path.join(B.CSRC, "point_query.h") in deps and os.path.join(B.CSRC, "key_list.h") in deps
-    assert "overlap.hip" in B.LIB_SOURCES
-
-
-def test_null_scene_is_an_argument_error():
-    f = getattr(overlap.lib(), SYMBOL)
-    for args in [(None, 0, 0, None, None, None, 0, None), (None, 5, 4, None, None, None, 1, None)]:
-        # (another call's message first, so that the one read back is this call's)
-        assert m.lib().mirt_build_lbvh(None, None, None) == 3 and SYMBOL.encode() not in m.lib().mirt_last_error()
-        assert f(None, *args) == 3
-        assert m.lib().mirt_last_error() == SYMBOL.encode() + b": null scene"
+def test_no_other_header_of_the_folder_names_the_entry_point_in_its_comments_either():
+    """(test_extension_abi.py lets a newer header speak of an older entry point in its comments; the two newer ones here do not)"""
+    folder = os.path.join(ROOT, "include_ext")
+    others = [name for name in os.listdir(folder) if name != "mirt_overlap.h"]
+    assert len(others) >= 4
+    for name in others:
+        assert "mirt_overlap_boxes" not in open(os.path.join(folder, name)).read(), name
 
 
 def test_wrappers_check_their_tensors_before_calling_the_library():

@@ -1,60 +1,32 @@
-"""Overlap lists (include_ext/mirt_overlap_list.h: mirt_list_offsets_work_bytes, mirt_list_offsets, mirt_overlap_list): the header
-against overlap_list.py's signature table and the built library, the wrappers' checks, the fill kernel's code generation, and the
-numpy restatement (tests/overlap_list_ref.py) against itself over the oracle's tree: on the inputs the GPU tests use, the left-first
-pruned walk emits the reference's words in the reference's order, every row's words are the brute force's admitted set, and the
-segment lengths are its counts.  No GPU needed."""
-import ctypes as C
-import importlib
+"""Overlap lists (include_ext/mirt_overlap_list.h: mirt_list_offsets_work_bytes, mirt_list_offsets, mirt_overlap_list): what the
+header's text says, the wrappers' checks, the fill kernel's code generation, and the numpy restatement (tests/overlap_list_ref.py)
+against itself over the oracle's tree: on the inputs the GPU tests use, the left-first pruned walk emits the reference's words in the
+reference's order, every row's words are the brute force's admitted set, and the segment lengths are its counts.  The header
+against overlap_list.py's signature table and the built library is a row of tests/test_extension_abi.py.  No GPU needed."""
 import functools
 import os
-import re
-import subprocess
-import sys
 import types
 
 import numpy as np
 import pytest
 
 import cuda_ray_tracer_amd as m
-from cuda_ray_tracer_amd import api, binding
 from cuda_ray_tracer_amd import build as B
 import overlap_list_ref as olr
 import overlap_ref as ovr
-from codegen_lib import _kernel_body, _resource_usage, _strip
-from test_binding_header import compare_prototypes, constants, prototypes
+from codegen_lib import _kernel_body, _resource_usage
 from test_closest_abi import _oracle_tree
+from test_extension_abi import EXTENSIONS, _module, other_entry_points
 from test_overlap_abi import CASES, CHOSEN_ROWS, case_keys, reference
-
-# (the package exports a function of the module's name, which `from cuda_ray_tracer_amd import overlap_list` would give)
-overlap_list = importlib.import_module("cuda_ray_tracer_amd.overlap_list")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include_ext", "mirt_overlap_list.h")
-SYMBOLS = ["mirt_list_offsets_work_bytes", "mirt_list_offsets", "mirt_overlap_list"]
-NAMES = ("list_offsets", "list_offsets_work_bytes", "overlap_list", "overlap_lists", "unpack_words", "voxel_lists")
-PTR, I32, I64 = "pointer", (4, True, False), (8, True, False)
+ROW = next(x for x in EXTENSIONS if x.module == "overlap_list")
 u32 = np.uint32
 u64 = np.uint64
 
 
-# ---- header, table, library ----------------------------------------------------------------------------------------------------------
-def test_the_header_agrees_with_the_signature_table():
-    header, table = _strip(HEADER), overlap_list.OVERLAP_LIST_SIGNATURES
-    assert [name for name, _, _ in prototypes(header)] == list(table) == SYMBOLS
-    assert sorted(set(re.findall(r"\b(mirt_[a-z0-9_]+)\s*\(", header))) == sorted(SYMBOLS)
-    assert compare_prototypes(header, table) == []
-    assert prototypes(header) == [(SYMBOLS[0], I64, [I64]), (SYMBOLS[1], I32, [PTR, PTR, I64, PTR, PTR, PTR]),
-                                  (SYMBOLS[2], I32, [PTR, PTR, I64, PTR, PTR, I64, PTR])]
-    assert constants(header) == {}      # (no record format and no constant of its own: a word is 32 bits)
-    assert re.search(r'^#include "\.\./include/mirt\.h"$', header, flags=re.M)
-    restype, argtypes = table[SYMBOLS[2]]
-    doctored = [C.c_int if t is C.c_int64 else t for t in argtypes]
-    assert compare_prototypes(header, {**table, SYMBOLS[2]: (restype, doctored)}) == [
-        f"{SYMBOLS[2]}: parameter 2 is (8, True, False), the table says (4, True, False)",
-        f"{SYMBOLS[2]}: parameter 5 is (8, True, False), the table says (4, True, False)"]
-    assert re.search(r"#define MIRT_VERSION 3\b", open(os.path.join(ROOT, "include", "mirt.h")).read())
-
-
+# ---- header, wrappers ----------------------------------------------------------------------------------------------------------------
 def test_the_header_states_the_order_and_the_bounded_writes():
     text = " ".join(open(HEADER).read().replace(" *", " ").split())
     assert "the count-only call of mirt_overlap.h" in text and "kind << 30 | id" in text
@@ -69,57 +41,11 @@ def test_the_header_states_the_order_and_the_bounded_writes():
     assert "dmin2" not in text and "fabsf" not in text
 
 
-def _signature_tables():
-    """{module name: its table} of every other module that holds a header's signatures."""
-    import importlib
-    out = {"binding": binding.SIGNATURES}
-    for name in ("lighting", "visibility", "indirect", "closest", "multihit", "contacts", "spherecast", "overlap"):
-        mod = importlib.import_module("cuda_ray_tracer_amd." + name)
-        tables = [v for k, v in vars(mod).items() if k.endswith("_SIGNATURES") and isinstance(v, dict) and v is not binding.SIGNATURES]
-        assert tables, name
-        out[name] = {k: v for t in tables for k, v in t.items()}
-    return out
-
-
-def test_mirt_h_the_other_headers_and_the_other_tables_do_not_know_the_extension():
-    tables = _signature_tables()
-    for sym in SYMBOLS:
-        for folder in ("include", "include_ext"):
-            for name in os.listdir(os.path.join(ROOT, folder)):
-                if name != "mirt_overlap_list.h":
-                    assert sym not in open(os.path.join(ROOT, folder, name)).read(), (sym, name)
-        for name, table in tables.items():
-            assert sym not in table, (sym, name)
-    # ... and this header names no other extension's entry point, in its comments either
-    raw = open(HEADER).read()
-    others = sorted(k for name, table in tables.items() if name != "binding" for k in table)
-    assert len(others) >= 8 and "mirt_overlap_boxes" in others
-    assert [k for k in others if re.search(r"\b%s\b" % k, raw)] == []
-    assert "mirt_overlap_boxes" not in raw and not any("mirt_overlap_boxes" in s for s in SYMBOLS)
-
-
-def test_library_exports_the_symbols_and_the_signatures_are_applied():
-    out = subprocess.run(["nm", "-D", "--defined-only", B.LIB], capture_output=True, text=True, check=True).stdout
-    for sym in SYMBOLS:
-        assert re.search(r"\bT %s$" % sym, out, flags=re.M), sym
-        f = getattr(overlap_list.lib(), sym)
-        restype, argtypes = overlap_list.OVERLAP_LIST_SIGNATURES[sym]
-        assert f.restype is restype and list(f.argtypes) == argtypes
-    for name in NAMES:
-        assert getattr(m, name) is getattr(overlap_list, name) is getattr(api, name) and name in m.__all__, name
-
-
-def test_the_module_needs_neither_torch_nor_numpy():
-    code = "import sys; import cuda_ray_tracer_amd.overlap_list; assert 'torch' not in sys.modules and 'numpy' not in sys.modules, sorted(sys.modules)"
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-
-
-def test_the_build_depends_on_the_header_and_the_kernel():
-    deps = [os.path.normpath(d) for d in B._all_deps()]
-    assert HEADER in deps and os.path.join(B.CSRC, "overlap_list.hip") in deps
-    assert os.path.join(B.CSRC, "overlap_tests.h") in deps and os.path.join(B.CSRC, "block_scan.h") in deps
-    assert "overlap_list.hip" in B.LIB_SOURCES
+def test_the_header_names_no_other_extensions_entry_point_in_its_comments_either():
+    raw, others = open(HEADER).read(), other_entry_points(ROW)
+    assert len(others) >= 10 and "mirt_overlap_boxes" in others
+    assert [k for k in others if k in raw] == []
+    assert "mirt_overlap_boxes" not in raw and not any("mirt_overlap_boxes" in s.name for s in ROW.symbols)
 
 
 def test_the_shared_device_code_has_one_copy():
@@ -145,15 +71,8 @@ def test_the_shared_device_code_has_one_copy():
     assert " block_exclusive_scan(T v" in read("block_scan.h")
 
 
-def test_null_scene_is_an_argument_error_and_the_work_bytes_are_host_arithmetic():
-    L = overlap_list.lib()
-    for sym, calls in (("mirt_list_offsets", [(None, 0, None, None, None), (None, 5, None, None, None)]),
-                       ("mirt_overlap_list", [(None, 0, None, None, 0, None), (None, 5, None, None, 7, None)])):
-        for args in calls:
-            # (another call's message first, so that the one read back is this call's)
-            assert m.lib().mirt_build_lbvh(None, None, None) == 3 and sym.encode() not in m.lib().mirt_last_error()
-            assert getattr(L, sym)(None, *args) == 3
-            assert m.lib().mirt_last_error() == sym.encode() + b": null scene"
+def test_the_work_bytes_are_host_arithmetic():
+    L = _module(ROW).lib()
     want = {-5: 0, 0: 0, 1: 0, 2048: 0, 2049: 16, 4096: 16, 4097: 24, 65537: 8 * 33, 1 << 33: 8 * (1 << 22)}
     assert {n: L.mirt_list_offsets_work_bytes(n) for n in want} == want
     assert {n: m.list_offsets_work_bytes(n) for n in want} == want

@@ -1,21 +1,18 @@
-"""Ray and ball lists (include_ext/mirt_query_lists.h: mirt_ray_list, mirt_ball_list): the header against query_lists.py's signature
-table and the built library, the wrappers' checks, the fill kernels' code generation, and the numpy restatement
-(tests/query_lists_ref.py) against itself over the oracle's tree: on the inputs the GPU tests use, the two left-first walks emit the
-reference's words and values in the reference's order, every row's length is the record reference's count, and every row sorted
-begins with the record reference's eight records.  No GPU needed."""
-import ctypes as C
+"""Ray and ball lists (include_ext/mirt_query_lists.h: mirt_ray_list, mirt_ball_list): what the header's text says, the wrappers'
+checks, the fill kernels' code generation, and the numpy restatement (tests/query_lists_ref.py) against itself over the oracle's
+tree: on the inputs the GPU tests use, the two left-first walks emit the reference's words and values in the reference's order, every
+row's length is the record reference's count, and every row sorted begins with the record reference's eight records.  The header
+against query_lists.py's signature table and the built library is a row of tests/test_extension_abi.py.  No GPU needed."""
 import functools
 import os
 import re
-import subprocess
-import sys
 import types
 
 import numpy as np
 import pytest
 
 import cuda_ray_tracer_amd as m
-from cuda_ray_tracer_amd import api, binding, query_lists
+from cuda_ray_tracer_amd import api, query_lists
 from cuda_ray_tracer_amd import build as B
 import contacts_ref as kr
 import multihit_ref as mr
@@ -24,38 +21,18 @@ import query_lists_ref as qlr
 import test_contacts_abi as tca
 import test_multihit_abi as tma
 from codegen_lib import _kernel_body, _resource_usage, _strip
-from test_binding_header import compare_prototypes, constants, prototypes
 from test_closest_abi import _oracle_tree
+from test_extension_abi import EXTENSIONS, other_entry_points
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include_ext", "mirt_query_lists.h")
-SYMBOLS = ["mirt_ray_list", "mirt_ball_list"]
-NAMES = ("ray_list", "ball_list", "ray_lists", "ball_lists")
-PTR, I32, U32, I64 = "pointer", (4, True, False), (4, False, False), (8, True, False)
+ROW = next(x for x in EXTENSIONS if x.module == "query_lists")
 u32 = np.uint32
 u64 = np.uint64
 f32 = np.float32
 
 
-# ---- header, table, library ----------------------------------------------------------------------------------------------------------
-def test_the_header_agrees_with_the_signature_table():
-    header, table = _strip(HEADER), query_lists.QUERY_LISTS_SIGNATURES
-    assert [name for name, _, _ in prototypes(header)] == list(table) == SYMBOLS
-    assert sorted(set(re.findall(r"\b(mirt_[a-z0-9_]+)\s*\(", header))) == sorted(SYMBOLS)
-    assert compare_prototypes(header, table) == []
-    fill = [PTR, PTR, I64, PTR, PTR, PTR, I64, U32, PTR]
-    assert prototypes(header) == [(SYMBOLS[0], I32, fill), (SYMBOLS[1], I32, fill)]
-    assert constants(header) == {}      # (no record format and no constant of its own: a word and a value are 32 bits each)
-    assert re.search(r'^#include "\.\./include/mirt\.h"$', header, flags=re.M)
-    assert len(re.findall(r"^#include", header, flags=re.M)) == 1
-    restype, argtypes = table[SYMBOLS[1]]
-    doctored = [C.c_int if t is C.c_int64 else t for t in argtypes]
-    assert compare_prototypes(header, {**table, SYMBOLS[1]: (restype, doctored)}) == [
-        f"{SYMBOLS[1]}: parameter 2 is (8, True, False), the table says (4, True, False)",
-        f"{SYMBOLS[1]}: parameter 6 is (8, True, False), the table says (4, True, False)"]
-    assert re.search(r"#define MIRT_VERSION 3\b", open(os.path.join(ROOT, "include", "mirt.h")).read())
-
-
+# ---- header, wrappers ----------------------------------------------------------------------------------------------------------------
 def test_the_header_refers_to_the_sets_and_states_the_order_the_values_and_the_bounded_writes():
     text = " ".join(open(HEADER).read().replace(" *", " ").split())
     assert "the count-only call of mirt_multihit.h" in text and "of mirt_contacts.h" in text and "the offsets call of the overlap-list extension" in text
@@ -75,57 +52,17 @@ def test_the_header_refers_to_the_sets_and_states_the_order_the_values_and_the_b
     assert "no allocation, no synchronisation, no atomics" in text and "One lane per row" in text
 
 
-def _signature_tables():
-    """{module name: its table} of every other module that holds a header's signatures."""
-    import importlib
-    out = {"binding": binding.SIGNATURES}
-    for name in ("lighting", "visibility", "indirect", "closest", "multihit", "contacts", "spherecast", "overlap", "overlap_list"):
-        mod = importlib.import_module("cuda_ray_tracer_amd." + name)
-        tables = [v for k, v in vars(mod).items() if k.endswith("_SIGNATURES") and isinstance(v, dict) and v is not binding.SIGNATURES]
-        assert tables, name
-        out[name] = {k: v for t in tables for k, v in t.items()}
-    return out
-
-
-def test_mirt_h_the_other_headers_and_the_other_tables_do_not_know_the_extension():
-    tables = _signature_tables()
-    for sym in SYMBOLS:
-        for folder in ("include", "include_ext"):
-            for name in os.listdir(os.path.join(ROOT, folder)):
-                if name != "mirt_query_lists.h":
-                    assert sym not in open(os.path.join(ROOT, folder, name)).read(), (sym, name)
-        for name, table in tables.items():
-            assert sym not in table, (sym, name)
-    # ... and this header names no other extension's entry point, in its comments either, nor the overlap-list header
-    raw = open(HEADER).read()
-    others = sorted(k for name, table in tables.items() if name != "binding" for k in table)
+def test_the_header_has_one_include_and_names_no_other_extensions_entry_point_in_its_comments_either():
+    """(nor the overlap-list header, whose file name is an entry point's name)"""
+    assert len(re.findall(r"^#include", _strip(HEADER), flags=re.M)) == 1
+    raw, others = open(HEADER).read(), other_entry_points(ROW)
     assert len(others) >= 11 and "mirt_trace_rays_multi" in others and "mirt_closest_points_multi" in others and "mirt_list_offsets" in others
     assert [k for k in others if k in raw] == []
     assert "mirt_overlap_list" not in raw and "mirt_trace_rays" not in raw and "mirt_closest_points" not in raw
 
 
-def test_library_exports_the_symbols_and_the_signatures_are_applied():
-    out = subprocess.run(["nm", "-D", "--defined-only", B.LIB], capture_output=True, text=True, check=True).stdout
-    for sym in SYMBOLS:
-        assert re.search(r"\bT %s$" % sym, out, flags=re.M), sym
-        f = getattr(query_lists.lib(), sym)
-        restype, argtypes = query_lists.QUERY_LISTS_SIGNATURES[sym]
-        assert f.restype is restype and list(f.argtypes) == argtypes
-    for name in NAMES:
-        assert getattr(m, name) is getattr(query_lists, name) is getattr(api, name) and name in m.__all__, name
+def test_unpack_words_is_the_overlap_lists():
     assert m.unpack_words is api.unpack_words and not hasattr(query_lists, "unpack_words")      # (the existing one)
-
-
-def test_the_module_needs_neither_torch_nor_numpy():
-    code = "import sys; import cuda_ray_tracer_amd.query_lists; assert 'torch' not in sys.modules and 'numpy' not in sys.modules, sorted(sys.modules)"
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-
-
-def test_the_build_depends_on_the_header_and_the_kernel():
-    deps = [os.path.normpath(d) for d in B._all_deps()]
-    assert HEADER in deps and os.path.join(B.CSRC, "query_lists.hip") in deps and os.path.join(B.CSRC, "list_cursor.h") in deps
-    assert "query_lists.hip" in B.LIB_SOURCES
 
 
 def test_the_bounded_write_rule_has_one_copy():
@@ -140,16 +77,6 @@ def test_the_bounded_write_rule_has_one_copy():
     # the walks are written out in the new file, and say whose copies they are
     text = read("query_lists.hip")
     assert "multihit_kernel<0>" in text and "contacts_kernel<0>" in text and text.count("stack_pop(") == 2 and "atomic" not in text
-
-
-def test_null_scene_is_an_argument_error():
-    L = query_lists.lib()
-    for sym in SYMBOLS:
-        for args in ((None, 0, None, None, None, 0, 0, None), (None, 5, None, None, None, 7, 0, None), (None, -1, None, None, None, -1, 9, None)):
-            # (another call's message first, so that the one read back is this call's)
-            assert m.lib().mirt_build_lbvh(None, None, None) == 3 and sym.encode() not in m.lib().mirt_last_error()
-            assert getattr(L, sym)(None, *args) == 3
-            assert m.lib().mirt_last_error() == sym.encode() + b": null scene"
 
 
 def test_wrappers_check_their_tensors_before_calling_the_library():

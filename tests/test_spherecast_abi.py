@@ -1,99 +1,39 @@
-"""Sphere casts (include_ext/mirt_spherecast.h: mirt_cast_spheres): the header against spherecast.py's signature table and the built
-library, the wrappers' checks, the kernel's code generation from the compiler's report, the numpy restatement of the header
-(tests/spherecast_ref.py) against a float64 brute force that shares no code with it, and the header's pruning rule checked on the
-CPU over the oracle's tree: on every input the GPU tests use the pruned walk gives the brute force's bits.  No GPU needed."""
-import ctypes as C
+"""Sphere casts (include_ext/mirt_spherecast.h: mirt_cast_spheres): what the header's text says, the wrappers' checks, the kernel's code
+generation from the compiler's report, the numpy restatement of the header (tests/spherecast_ref.py) against a float64 brute force
+that shares no code with it, and the header's pruning rule checked on the CPU over the oracle's tree: on every input the GPU tests
+use the pruned walk gives the brute force's bits.  The header against spherecast.py's signature table and the built library is a row
+of tests/test_extension_abi.py.  No GPU needed."""
 import functools
 import os
 import re
-import subprocess
-import sys
 import types
 
 import numpy as np
 import pytest
 
 import cuda_ray_tracer_amd as m
-from cuda_ray_tracer_amd import api, binding, spherecast
-from cuda_ray_tracer_amd import build as B
 import edge_scenes
 import light_scenes
 import pyscene
 import spherecast_ref as sr
-from codegen_lib import _resource_usage, _strip
-from test_binding_header import compare_prototypes, constants, prototypes
+from codegen_lib import _resource_usage
 from test_closest_abi import _oracle_tree, _points_about, _well_shaped_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include_ext", "mirt_spherecast.h")
-SYMBOL = "mirt_cast_spheres"
-PTR, I32, I64, U32 = "pointer", (4, True, False), (8, True, False), (4, False, False)
 f32 = np.float32
 u32 = np.uint32
 INF = float("inf")
 NAN = float("nan")
 
 
-# ---- header, table, library ----------------------------------------------------------------------------------------------------------
-def test_the_header_agrees_with_the_signature_table():
-    header, table = _strip(HEADER), spherecast.SPHERECAST_SIGNATURES
-    assert [name for name, _, _ in prototypes(header)] == list(table) == [SYMBOL]
-    assert sorted(set(re.findall(r"\b(mirt_[a-z0-9_]+)\s*\(", header))) == [SYMBOL]
-    assert compare_prototypes(header, table) == []
-    assert prototypes(header)[0] == (SYMBOL, I32, [PTR, PTR, I64, PTR, PTR, U32, PTR])
-    assert constants(header) == {"MIRT_CAST_ANY_HIT": 1} and spherecast.MIRT_CAST_ANY_HIT == 1
-    assert re.search(r'^#include "\.\./include/mirt\.h"$', header, flags=re.M)
-    restype, argtypes = table[SYMBOL]
-    doctored = [C.c_int if t is C.c_int64 else t for t in argtypes]
-    assert compare_prototypes(header, {SYMBOL: (restype, doctored)}) == [f"{SYMBOL}: parameter 2 is (8, True, False), the table says (4, True, False)"]
-    assert compare_prototypes(header, {SYMBOL: (restype, argtypes[:-1])}) == [f"{SYMBOL}: 7 parameters, the table has 6"]
-    assert re.search(r"#define MIRT_VERSION 3\b", open(os.path.join(ROOT, "include", "mirt.h")).read())
-
-
+# ---- header, wrappers ----------------------------------------------------------------------------------------------------------------
 def test_the_header_states_the_definition_and_the_pruning_rule():
     text = " ".join(open(HEADER).read().replace(" *", " ").split())
     assert "never by the tree" in text and "(t, kind, id)" in text and "0 <= t < tmax" in text
     assert "tie at t = 0" in text and "mirt_closest_points_multi" in text
     assert "closest-approach form" in text and "Pruning (informative" in text and "sigma = 2^-18" in text and "tau = 2^-20" in text
     assert sr.SLACK == f32(2.0 ** -18) and sr.TAU == f32(2.0 ** -20)
-
-
-def test_mirt_h_and_the_other_tables_do_not_know_the_extension():
-    assert SYMBOL not in open(os.path.join(ROOT, "include", "mirt.h")).read() and SYMBOL not in binding.SIGNATURES
-    assert not hasattr(binding, "MIRT_CAST_ANY_HIT")
-    for name in os.listdir(os.path.join(ROOT, "include")):
-        assert SYMBOL not in open(os.path.join(ROOT, "include", name)).read(), name
-
-
-def test_library_exports_the_symbol_and_the_signature_is_applied():
-    out = subprocess.run(["nm", "-D", "--defined-only", B.LIB], capture_output=True, text=True, check=True).stdout
-    assert re.search(r"\bT %s$" % SYMBOL, out, flags=re.M)
-    f = getattr(spherecast.lib(), SYMBOL)
-    assert f.restype is C.c_int and list(f.argtypes) == spherecast.SPHERECAST_SIGNATURES[SYMBOL][1]
-    for name in ("cast_spheres", "pack_casts"):
-        assert getattr(m, name) is getattr(spherecast, name) is getattr(api, name) and name in m.__all__, name
-
-
-def test_the_module_needs_neither_torch_nor_numpy():
-    code = "import sys; import cuda_ray_tracer_amd.spherecast; assert 'torch' not in sys.modules and 'numpy' not in sys.modules, sorted(sys.modules)"
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-
-
-def test_the_build_depends_on_the_header_and_the_kernel():
-    deps = [os.path.normpath(d) for d in B._all_deps()]
-    assert HEADER in deps and os.path.join(B.CSRC, "spherecast.hip") in deps
-    assert os.path.join(B.CSRC, "point_query.h") in deps and os.path.join(B.CSRC, "query_walk.h") in deps
-    assert "spherecast.hip" in B.LIB_SOURCES
-
-
-def test_null_scene_is_an_argument_error():
-    f = getattr(spherecast.lib(), SYMBOL)
-    for args in [(None, 0, None, None, 0, None), (None, 5, None, None, 1, None)]:
-        # (another call's message first, so that the one read back is this call's)
-        assert m.lib().mirt_build_lbvh(None, None, None) == 3 and SYMBOL.encode() not in m.lib().mirt_last_error()
-        assert f(None, *args) == 3
-        assert m.lib().mirt_last_error() == SYMBOL.encode() + b": null scene"
 
 
 def test_wrappers_check_their_tensors_before_calling_the_library():

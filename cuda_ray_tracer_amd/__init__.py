@@ -3,7 +3,8 @@
 Host side: binding.py (include/mirt.h restated for ctypes) and api.py (the calls over it); lighting.py (include/mirt_light.h);
 visibility.py (include/mirt_visibility.h); indirect.py (include/mirt_indirect.h); closest.py (include/mirt_closest.h);
 multihit.py (include/mirt_multihit.h); contacts.py (include_ext/mirt_contacts.h); spherecast.py (include_ext/mirt_spherecast.h);
-overlap.py (include_ext/mirt_overlap.h); overlap_list.py (include_ext/mirt_overlap_list.h); query_lists.py (include_ext/mirt_query_lists.h).
+overlap.py (include_ext/mirt_overlap.h); overlap_list.py (include_ext/mirt_overlap_list.h); query_lists.py (include_ext/mirt_query_lists.h);
+overlap_tris.py (include_ext2/mirt_overlap_tris.h).
 Device side: csrc/*.hip, built by build.py into _build/libmirt.so.
 """
 from .api import (MirtError, StlConfig, RawConfig, parseInput, parseText, syntheticScene, initRawConfigFromStl,
@@ -19,7 +20,8 @@ from .api import (MirtError, StlConfig, RawConfig, parseInput, parseText, synthe
                   closest_points_multi, count_within, cast_spheres, pack_casts,
                   overlap_boxes, count_overlaps, pack_boxes, voxel_rows, occupancy_grid,
                   list_offsets, list_offsets_work_bytes, overlap_list, overlap_lists, unpack_words, voxel_lists,
-                  ray_list, ball_list, ray_lists, ball_lists)
+                  ray_list, ball_list, ray_lists, ball_lists,
+                  overlap_triangles, triangle_list, triangle_lists, pack_triangles, scene_triangle_rows)
 
 __all__ = ["MirtError", "StlConfig", "RawConfig", "parseInput", "parseText", "syntheticScene", "initRawConfigFromStl",
            "copyConfigDataToDevice", "freeRawConfigDeviceMemory", "build_lbvh_karas", "render", "render_params",
@@ -34,4 +36,5 @@ __all__ = ["MirtError", "StlConfig", "RawConfig", "parseInput", "parseText", "sy
            "closest_points_multi", "count_within", "cast_spheres", "pack_casts",
            "overlap_boxes", "count_overlaps", "pack_boxes", "voxel_rows", "occupancy_grid",
            "list_offsets", "list_offsets_work_bytes", "overlap_list", "overlap_lists", "unpack_words", "voxel_lists",
-           "ray_list", "ball_list", "ray_lists", "ball_lists"]
+           "ray_list", "ball_list", "ray_lists", "ball_lists",
+           "overlap_triangles", "triangle_list", "triangle_lists", "pack_triangles", "scene_triangle_rows"]

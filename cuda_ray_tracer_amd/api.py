@@ -976,6 +976,8 @@ from .overlap import overlap_boxes, count_overlaps, pack_boxes, voxel_rows, occu
 from .overlap_list import list_offsets, list_offsets_work_bytes, overlap_list, overlap_lists, unpack_words, voxel_lists      # noqa: E402,F401
 # Ray and ball lists (include_ext/mirt_query_lists.h): query_lists.py holds that header's signatures and calls
 from .query_lists import ray_list, ball_list, ray_lists, ball_lists      # noqa: E402,F401
+# Triangle overlaps (include_ext2/mirt_overlap_tris.h): overlap_tris.py holds that header's signatures and calls
+from .overlap_tris import overlap_triangles, triangle_list, triangle_lists, pack_triangles, scene_triangle_rows      # noqa: E402,F401
 
 
 def pack_rays(origins, dirs, tmax=float("inf")):

@@ -441,6 +441,19 @@ int mirt_ball_list(MirtScene* sc, const void* d_points, int64_t n, const int64_t
   return ball_list(sc, d_points, n, d_offsets, d_words, d_dist, capacity, flags, (hipStream_t)stream);
 }
 
+// (include_ext2/mirt_overlap_tris.h)
+int mirt_overlap_triangles(MirtScene* sc, const void* d_tris, int64_t n, uint32_t* d_counts, uint32_t flags, void* stream)
+{
+  MIRT_TRY(enter_scene(sc, "mirt_overlap_triangles"));
+  return overlap_triangles(sc, d_tris, n, d_counts, flags, (hipStream_t)stream);
+}
+
+int mirt_triangle_list(MirtScene* sc, const void* d_tris, int64_t n, const int64_t* d_offsets, uint32_t* d_words, int64_t capacity, void* stream)
+{
+  MIRT_TRY(enter_scene(sc, "mirt_triangle_list"));
+  return triangle_list(sc, d_tris, n, d_offsets, d_words, capacity, (hipStream_t)stream);
+}
+
 size_t mirt_denoise_work_bytes(const MirtRenderParams* p) { return denoise_work_bytes(p); }
 
 int mirt_denoise(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, const void* d_features,

@@ -6,6 +6,7 @@
 #include "../../include_ext/mirt_contacts.h"
 #include "../../include_ext/mirt_overlap.h"
 #include "../../include_ext/mirt_spherecast.h"
+#include "../../include_ext2/mirt_overlap_tris.h"
 
 #include <cmath>
 #include <cstdio>
@@ -217,6 +218,26 @@ int check_trace_rays_multi(const void* d_rays, int64_t num_rays, int k, const vo
                          "null buffer (d_rays; d_hits unless k is 0; d_counts when k is 0)",
                          "d_rays must be 16-byte aligned, d_hits and d_counts 4-byte aligned", "d_hits and d_counts must not overlap d_rays or each other",
                          built, go);
+}
+
+int check_overlap_triangles(const void* d_tris, int64_t n, const void* d_counts, uint32_t flags, bool built, bool* go)
+{
+  const size_t rows = (size_t)n;
+  return check_row_query("mirt_overlap_triangles", flags & ~MIRT_TRIS_ANY, n, "n", {}, {{d_tris, 36 * rows, 4, n > 0}, {d_counts, 4 * rows, 4, n > 0}},
+                         "null buffer", "d_tris and d_counts must be 4-byte aligned", "d_tris and d_counts must not overlap each other", built, go);
+}
+
+int check_triangle_list(const void* d_tris, int64_t n, const void* d_offsets, const void* d_words, int64_t capacity, bool built, bool* go)
+{
+  // (a range of no bytes -- n == 0, capacity == 0 -- overlaps nothing)
+  const size_t rows = (size_t)n;
+  const int rc = check_row_query("mirt_triangle_list", 0u, n, "n", {{capacity < 0, "negative capacity"}},
+                                 {{d_tris, 36 * rows, 4, n > 0}, {d_offsets, n > 0 ? 8 * (rows + 1) : 0, 8, n > 0}, {d_words, 4 * (size_t)capacity, 4, capacity > 0}},
+                                 "null buffer (d_tris and d_offsets when n > 0; d_words when capacity > 0)",
+                                 "d_tris and d_words must be 4-byte aligned, d_offsets 8-byte aligned",
+                                 "d_tris, d_offsets and d_words must not overlap each other", built, go);
+  *go = *go && capacity > 0;      // (no row, or no word any row could write)
+  return rc;
 }
 
 namespace {

@@ -71,6 +71,9 @@ int check_ray_list(const void* d_rays, int64_t num_rays, const void* d_offsets, 
 int check_ball_list(const void* d_points, int64_t n, const void* d_offsets, const void* d_words, const void* d_dist, int64_t capacity, uint32_t flags,
                     bool built, bool* go);
 int check_trace_rays_multi(const void* d_rays, int64_t num_rays, int k, const void* d_hits, const void* d_counts, uint32_t flags, bool built, bool* go);
+// ... and of the two of include_ext2/mirt_overlap_tris.h (overlap_tris.hip): rows of 36 bytes, 4-byte aligned
+int check_overlap_triangles(const void* d_tris, int64_t n, const void* d_counts, uint32_t flags, bool built, bool* go);
+int check_triangle_list(const void* d_tris, int64_t n, const void* d_offsets, const void* d_words, int64_t capacity, bool built, bool* go);
 
 class HostScene {
 public:

@@ -287,6 +287,7 @@ struct MirtScene {
   int spherecast_blocks[2] = {0, 0};       // ... and of the sphere-cast kernel's instances (spherecast.hip: first contact, any contact)
   int overlap_blocks[5] = {0, 0, 0, 0, 0}; // ... and of the box-overlap kernel's instances (overlap.hip: count, any, capacity 1, 4, 8)
   int overlap_list_blocks = 0;             // ... and of the overlap-list fill kernel (overlap_list.hip)
+  int overlap_tris_blocks[3] = {0, 0, 0};  // ... and of the triangle-overlap kernels (overlap_tris.hip: count, any, fill)
   int ray_list_blocks[2] = {0, 0};         // ... and of the ray-list fill kernel's instances (query_lists.hip: words, words and values)
   int ball_list_blocks[2] = {0, 0};        // ... and of the ball-list fill kernel's instances (query_lists.hip: words, words and values)
   bool updated = false;                    // geometry updated in place since the last build (update.hip): mirt_camera_rays waits for the build like every other call
@@ -364,6 +365,9 @@ int overlap_boxes(MirtScene* sc, const void* d_boxes, int64_t n, int k, void* d_
 int64_t list_offsets_work_bytes(int64_t n);
 int list_offsets(MirtScene* sc, const uint32_t* d_counts, int64_t n, int64_t* d_offsets, void* d_work, hipStream_t stream);
 int overlap_list(MirtScene* sc, const void* d_boxes, int64_t n, const int64_t* d_offsets, uint32_t* d_words, int64_t capacity, hipStream_t stream);
+// overlap_tris.hip
+int overlap_triangles(MirtScene* sc, const void* d_tris, int64_t n, uint32_t* d_counts, uint32_t flags, hipStream_t stream);
+int triangle_list(MirtScene* sc, const void* d_tris, int64_t n, const int64_t* d_offsets, uint32_t* d_words, int64_t capacity, hipStream_t stream);
 // query_lists.hip
 int ray_list(MirtScene* sc, const void* d_rays, int64_t num_rays, const int64_t* d_offsets, uint32_t* d_words, float* d_t, int64_t capacity, uint32_t flags,
              hipStream_t stream);

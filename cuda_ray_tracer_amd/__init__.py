@@ -4,7 +4,7 @@ Host side: binding.py (include/mirt.h restated for ctypes) and api.py (the calls
 visibility.py (include/mirt_visibility.h); indirect.py (include/mirt_indirect.h); closest.py (include/mirt_closest.h);
 multihit.py (include/mirt_multihit.h); contacts.py (include_ext/mirt_contacts.h); spherecast.py (include_ext/mirt_spherecast.h);
 overlap.py (include_ext/mirt_overlap.h); overlap_list.py (include_ext/mirt_overlap_list.h); query_lists.py (include_ext/mirt_query_lists.h);
-overlap_tris.py (include_ext2/mirt_overlap_tris.h).
+overlap_tris.py (include_ext2/mirt_overlap_tris.h); cast_lists.py (include_ext3/mirt_cast_lists.h).
 Device side: csrc/*.hip, built by build.py into _build/libmirt.so.
 """
 from .api import (MirtError, StlConfig, RawConfig, parseInput, parseText, syntheticScene, initRawConfigFromStl,
@@ -21,7 +21,8 @@ from .api import (MirtError, StlConfig, RawConfig, parseInput, parseText, synthe
                   overlap_boxes, count_overlaps, pack_boxes, voxel_rows, occupancy_grid,
                   list_offsets, list_offsets_work_bytes, overlap_list, overlap_lists, unpack_words, voxel_lists,
                   ray_list, ball_list, ray_lists, ball_lists,
-                  overlap_triangles, triangle_list, triangle_lists, pack_triangles, scene_triangle_rows)
+                  overlap_triangles, triangle_list, triangle_lists, pack_triangles, scene_triangle_rows,
+                  count_casts, cast_list, cast_lists)
 
 __all__ = ["MirtError", "StlConfig", "RawConfig", "parseInput", "parseText", "syntheticScene", "initRawConfigFromStl",
            "copyConfigDataToDevice", "freeRawConfigDeviceMemory", "build_lbvh_karas", "render", "render_params",
@@ -37,4 +38,5 @@ __all__ = ["MirtError", "StlConfig", "RawConfig", "parseInput", "parseText", "sy
            "overlap_boxes", "count_overlaps", "pack_boxes", "voxel_rows", "occupancy_grid",
            "list_offsets", "list_offsets_work_bytes", "overlap_list", "overlap_lists", "unpack_words", "voxel_lists",
            "ray_list", "ball_list", "ray_lists", "ball_lists",
-           "overlap_triangles", "triangle_list", "triangle_lists", "pack_triangles", "scene_triangle_rows"]
+           "overlap_triangles", "triangle_list", "triangle_lists", "pack_triangles", "scene_triangle_rows",
+           "count_casts", "cast_list", "cast_lists"]

@@ -978,6 +978,8 @@ from .overlap_list import list_offsets, list_offsets_work_bytes, overlap_list, o
 from .query_lists import ray_list, ball_list, ray_lists, ball_lists      # noqa: E402,F401
 # Triangle overlaps (include_ext2/mirt_overlap_tris.h): overlap_tris.py holds that header's signatures and calls
 from .overlap_tris import overlap_triangles, triangle_list, triangle_lists, pack_triangles, scene_triangle_rows      # noqa: E402,F401
+# Cast lists (include_ext3/mirt_cast_lists.h): cast_lists.py holds that header's signatures and calls
+from .cast_lists import count_casts, cast_list, cast_lists      # noqa: E402,F401
 
 
 def pack_rays(origins, dirs, tmax=float("inf")):

@@ -17,7 +17,7 @@ LIB = os.path.join(OUT, "libmirt.so")
 CLI = os.path.join(OUT, "raytracer")
 ARCH = "gfx950"
 
-LIB_SOURCES = ["host_scene.cpp", "png_writer.cpp", "xorwow_tables.cpp", "multi.cpp", "lbvh_build.hip", "tree_readback.hip", "render.hip", "adaptive.hip", "denoise.hip", "temporal.hip", "wavefront.hip", "query.hip", "light.hip", "visibility.hip", "indirect.hip", "closest.hip", "closest_multi.hip", "spherecast.hip", "overlap.hip", "overlap_list.hip", "overlap_tris.hip", "query_lists.hip", "multihit.hip", "update.hip", "update_shading.hip", "api.hip"]
+LIB_SOURCES = ["host_scene.cpp", "png_writer.cpp", "xorwow_tables.cpp", "multi.cpp", "lbvh_build.hip", "tree_readback.hip", "render.hip", "adaptive.hip", "denoise.hip", "temporal.hip", "wavefront.hip", "query.hip", "light.hip", "visibility.hip", "indirect.hip", "closest.hip", "closest_multi.hip", "spherecast.hip", "overlap.hip", "overlap_list.hip", "overlap_tris.hip", "query_lists.hip", "cast_lists.hip", "multihit.hip", "update.hip", "update_shading.hip", "api.hip"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
           f"--offload-arch={ARCH}", "-fno-gpu-flush-denormals-to-zero"]
 
@@ -38,7 +38,7 @@ def _stale(target, deps):
 
 def _all_deps():
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
-    for name in ("include", "include_ext", "include_ext2"):      # (include_ext: DESIGN.md section 6s; include_ext2: section 6aa)
+    for name in ("include", "include_ext", "include_ext2", "include_ext3"):      # (include_ext: DESIGN.md section 6s; include_ext2: section 6aa; include_ext3: section 6ab)
         include = os.path.join(HERE, "..", name)
         deps += [os.path.join(include, f) for f in os.listdir(include) if f.startswith("mirt") and f.endswith(".h")]
     deps.append(os.path.abspath(__file__))

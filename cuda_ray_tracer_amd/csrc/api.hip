@@ -454,6 +454,20 @@ int mirt_triangle_list(MirtScene* sc, const void* d_tris, int64_t n, const int64
   return triangle_list(sc, d_tris, n, d_offsets, d_words, capacity, (hipStream_t)stream);
 }
 
+// (include_ext3/mirt_cast_lists.h)
+int mirt_cast_counts(MirtScene* sc, const void* d_casts, int64_t n, uint32_t* d_counts, uint32_t flags, void* stream)
+{
+  MIRT_TRY(enter_scene(sc, "mirt_cast_counts"));
+  return cast_counts(sc, d_casts, n, d_counts, flags, (hipStream_t)stream);
+}
+
+int mirt_cast_list(MirtScene* sc, const void* d_casts, int64_t n, const int64_t* d_offsets, uint32_t* d_words, float* d_t, int64_t capacity, uint32_t flags,
+                   void* stream)
+{
+  MIRT_TRY(enter_scene(sc, "mirt_cast_list"));
+  return cast_list(sc, d_casts, n, d_offsets, d_words, d_t, capacity, flags, (hipStream_t)stream);
+}
+
 size_t mirt_denoise_work_bytes(const MirtRenderParams* p) { return denoise_work_bytes(p); }
 
 int mirt_denoise(const MirtRenderParams* p, const void* d_accum_f32, const void* d_accum_sq_f32, const uint32_t* d_counts, const void* d_features,

@@ -240,6 +240,28 @@ int check_triangle_list(const void* d_tris, int64_t n, const void* d_offsets, co
   return rc;
 }
 
+int check_cast_counts(const void* d_casts, int64_t n, const void* d_counts, uint32_t flags, bool built, bool* go)
+{
+  const size_t rows = (size_t)n;
+  return check_row_query("mirt_cast_counts", flags, n, "n", {}, {{d_casts, 32 * rows, 16, n > 0}, {d_counts, 4 * rows, 4, n > 0}}, "null buffer",
+                         "d_casts must be 16-byte aligned, d_counts 4-byte aligned", "d_casts and d_counts must not overlap each other", built, go);
+}
+
+int check_cast_list(const void* d_casts, int64_t n, const void* d_offsets, const void* d_words, const void* d_t, int64_t capacity, uint32_t flags, bool built,
+                    bool* go)
+{
+  // (a range of no bytes -- n == 0, capacity == 0, a null d_t -- overlaps nothing)
+  const size_t rows = (size_t)n;
+  const int rc = check_row_query("mirt_cast_list", flags, n, "n", {{capacity < 0, "negative capacity"}},
+                                 {{d_casts, 32 * rows, 16, n > 0}, {d_offsets, n > 0 ? 8 * (rows + 1) : 0, 8, n > 0},
+                                  {d_words, 4 * (size_t)capacity, 4, capacity > 0}, {d_t, 4 * (size_t)capacity, 4, false}},
+                                 "null buffer (d_casts and d_offsets when n > 0; d_words when capacity > 0)",
+                                 "d_casts must be 16-byte aligned, d_offsets 8-byte aligned, d_words and d_t 4-byte aligned",
+                                 "d_casts, d_offsets, d_words and d_t must not overlap each other", built, go);
+  *go = *go && capacity > 0;      // (no row, or no word any row could write)
+  return rc;
+}
+
 namespace {
 
 inline MirtVec3 v3(float x, float y, float z) { MirtVec3 v; v.x = x; v.y = y; v.z = z; return v; }

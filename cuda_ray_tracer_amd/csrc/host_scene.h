@@ -74,6 +74,10 @@ int check_trace_rays_multi(const void* d_rays, int64_t num_rays, int k, const vo
 // ... and of the two of include_ext2/mirt_overlap_tris.h (overlap_tris.hip): rows of 36 bytes, 4-byte aligned
 int check_overlap_triangles(const void* d_tris, int64_t n, const void* d_counts, uint32_t flags, bool built, bool* go);
 int check_triangle_list(const void* d_tris, int64_t n, const void* d_offsets, const void* d_words, int64_t capacity, bool built, bool* go);
+// ... and of the two of include_ext3/mirt_cast_lists.h (cast_lists.hip): mirt_cast_spheres' rows
+int check_cast_counts(const void* d_casts, int64_t n, const void* d_counts, uint32_t flags, bool built, bool* go);
+int check_cast_list(const void* d_casts, int64_t n, const void* d_offsets, const void* d_words, const void* d_t, int64_t capacity, uint32_t flags, bool built,
+                    bool* go);
 
 class HostScene {
 public:

@@ -290,6 +290,7 @@ struct MirtScene {
   int overlap_tris_blocks[3] = {0, 0, 0};  // ... and of the triangle-overlap kernels (overlap_tris.hip: count, any, fill)
   int ray_list_blocks[2] = {0, 0};         // ... and of the ray-list fill kernel's instances (query_lists.hip: words, words and values)
   int ball_list_blocks[2] = {0, 0};        // ... and of the ball-list fill kernel's instances (query_lists.hip: words, words and values)
+  int cast_list_blocks[3] = {0, 0, 0};     // ... and of the cast-list kernels (cast_lists.hip: count, words, words and values)
   bool updated = false;                    // geometry updated in place since the last build (update.hip): mirt_camera_rays waits for the build like every other call
   // Shading values updated in place (update_shading.hip).  The three facts above are prim_flags | host_flags (MAT_* bits,
   // material_flags.h), by source: the primitives' materials -- after a material update known only to the device, until
@@ -372,6 +373,10 @@ int triangle_list(MirtScene* sc, const void* d_tris, int64_t n, const int64_t* d
 int ray_list(MirtScene* sc, const void* d_rays, int64_t num_rays, const int64_t* d_offsets, uint32_t* d_words, float* d_t, int64_t capacity, uint32_t flags,
              hipStream_t stream);
 int ball_list(MirtScene* sc, const void* d_points, int64_t n, const int64_t* d_offsets, uint32_t* d_words, float* d_dist, int64_t capacity, uint32_t flags,
+              hipStream_t stream);
+// cast_lists.hip
+int cast_counts(MirtScene* sc, const void* d_casts, int64_t n, uint32_t* d_counts, uint32_t flags, hipStream_t stream);
+int cast_list(MirtScene* sc, const void* d_casts, int64_t n, const int64_t* d_offsets, uint32_t* d_words, float* d_t, int64_t capacity, uint32_t flags,
               hipStream_t stream);
 // multihit.hip
 int trace_rays_multi(MirtScene* sc, const void* d_rays, int64_t num_rays, int k, void* d_hits, uint32_t* d_counts, uint32_t flags, hipStream_t stream);
